@@ -10,6 +10,14 @@ One step = forward (DropPath + dropout on, as in training) + CE loss + backward 
 HIP kernel + (N>1: RCCL gradient all-reduce overlapped with backward) + global-norm clip +
 AdamW.  Prints ONE JSON line on rank 0.  `--frames-pass` adds the reference's as-released
 no-grad B*T single-frame pass (tools/train_net.py:105-110); it is off for the headline metric.
+
+A plain run sets up, warms up, times --steps steps and prints the line.  `--full` adds the side
+measurements that take runs of their own: the per-kernel HIP-event trace of one eager step with its
+roofline figures, the fp32 CPU oracle baseline and the stock-ATen GPU baseline.  `--dump-outputs DIR`
+writes what the last timed step computed (loss, logits, the head's extra outputs, and a fixed seeded
+sample of the updated parameters and their gradients) as DIR/<name>.npy, float32, at most 64 MB.  That
+step starts from the benchmark's initial weights and optimizer state (restored outside the timed window),
+so that its inputs are the same on every run and its outputs agree between runs to rounding.
 """
 import argparse
 import json
@@ -164,6 +172,41 @@ def aten_gpu_baseline(frames, crop, batch, timed_steps=3):
             "peak_mem_gb": round(peak_gb, 1)}
 
 
+DUMP_BYTES = 64 << 20          # --dump-outputs: cap on the bytes written
+DUMP_SAMPLE = 1 << 22           # elements kept of an output larger than this (fixed seeded sample)
+
+
+def _named_tensors(prefix, obj):
+    if torch.is_tensor(obj):
+        yield prefix, obj
+    elif isinstance(obj, dict):
+        for k in sorted(obj):
+            yield from _named_tensors("%s_%s" % (prefix, k), obj[k])
+    elif isinstance(obj, (list, tuple)):
+        for i, v in enumerate(obj):
+            yield from _named_tensors("%s_%d" % (prefix, i), v)
+
+
+def dump_outputs(path, outputs):
+    """Write [(name, tensor)] as path/<name>.npy in float32.  A tensor of more than DUMP_SAMPLE elements is
+    replaced by its values at DUMP_SAMPLE indices drawn from a generator seeded with 0 (the same indices on
+    every run and build of the same arguments); the total stays within DUMP_BYTES."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    written = 0
+    for name, t in outputs:
+        t = t.detach()
+        if t.numel() > DUMP_SAMPLE:
+            g = torch.Generator(device="cpu").manual_seed(0)
+            idx = torch.randint(0, t.numel(), (DUMP_SAMPLE,), generator=g).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        arr = t.float().cpu().numpy()
+        written += arr.nbytes
+        if written > DUMP_BYTES:
+            raise SystemExit("--dump-outputs: the outputs exceed %d bytes" % DUMP_BYTES)
+        np.save(os.path.join(path, name + ".npy"), arr)
+
+
 def kernel_report(trace, batch):
     """Aggregate the HIP-event trace of one profiled step per C-ABI entry point."""
     torch.cuda.synchronize()
@@ -256,6 +299,13 @@ def main():
     ap.add_argument("--u8", action="store_true",
                     help="feed decoded uint8 frames [B,T,S,S,3]; normalisation fused into the patch "
                          "embedding (svit_amd/input.py; SURVEY 8(f) rank 4)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements: per-kernel trace + roofline of one eager step, the CPU "
+                         "oracle baseline and the stock-ATen GPU baseline (--no-kernel-trace / --no-cpu-baseline "
+                         "drop one of them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32, <= 64 MB); that step "
+                         "starts from the initial weights and optimizer state, restored outside the timed window")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-trace", action="store_true")
     ap.add_argument("--eager", action="store_true",
@@ -263,6 +313,8 @@ def main():
     ap.add_argument("--nt-cfg", type=int, default=None,
                     help="A/B knob for measurements: svit_debug_set(1, N) -- 8 = the NT GEMM heuristic without the ring kernels")
     args = ap.parse_args()
+    if not args.full:       # a plain run measures the headline only
+        args.no_cpu_baseline = args.no_kernel_trace = True
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # plain `python bench.py --gpus N`: become the launcher.  N fresh child processes, one rank
@@ -357,11 +409,14 @@ def main():
             torch.cuda.synchronize()
             launch_note = "eager (graph capture failed: %s)" % type(exc).__name__
 
+    last = {}
+
     def step(it, eager=False):
         optim.set_lr(opt, optim.get_lr_at_epoch(cfg, it / 1000.0))
         if graphed is not None and not eager:
-            loss, _ = graphed([x], y)       # fwd + CE + bwd (+ all-reduce launches) replayed
+            loss, (logits, extra) = graphed([x], y)       # fwd + CE + bwd (+ all-reduce launches) replayed
             opt.step()
+            last.update(loss=loss, logits=logits, extra=extra)
             return loss
         logits, extra = model([x], {})
         if frames_pass:
@@ -371,8 +426,17 @@ def main():
         opt.zero_grad()
         loss.backward()
         opt.step()
+        last.update(loss=loss, logits=logits, extra=extra)
         return loss
 
+    # --dump-outputs: the default engine's split reductions meet in fp32 atomics, so one step is reproducible only to
+    # rounding, and the optimizer carries that rounding from step to step until whole updates differ between runs.  The
+    # dumped (last timed) step therefore starts from the state the benchmark began with -- the initial weights and zero
+    # AdamW moments -- restored outside the timed window: its inputs are the same on every run.
+    start_state = None
+    if args.dump_outputs:
+        start_state = [(t, t.clone()) for t in (core.flat.data, opt.exp_avg, opt.exp_avg_sq)]
+        start_count = opt.step_count
     for it in range(args.warmup):
         loss = step(it)
     if world > 1:
@@ -380,6 +444,14 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for it in range(args.steps):
+        if start_state is not None and it == args.steps - 1:
+            torch.cuda.synchronize()
+            paused = time.perf_counter()
+            for t, saved in start_state:
+                t.copy_(saved)
+            opt.step_count = start_count
+            torch.cuda.synchronize()
+            t0 += time.perf_counter() - paused
         loss = step(args.warmup + it)
     torch.cuda.synchronize()
     if world > 1:
@@ -391,6 +463,14 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t)
     ms_per_step = dt / args.steps * 1e3
+    if args.dump_outputs and rank == 0:
+        # the last timed step's results, before anything else runs on the model
+        outs = list(_named_tensors("loss", last["loss"])) + list(_named_tensors("logits", last["logits"]))
+        outs += list(_named_tensors("extra", last["extra"]))
+        if getattr(core, "flat", None) is not None:
+            outs += [("params", core.flat.data), ("grads", core.flat.grad)]
+        dump_outputs(args.dump_outputs, outs)
+        torch.cuda.synchronize()
     ranks_seen = dist.get_world_size() if (world > 1 or force_dp) else 1
     n_vid = world - args.image_ranks
     clips_per_s = args.batch * n_vid * args.steps / dt

@@ -12,7 +12,7 @@ TEST INFRASTRUCTURE ONLY (run by tests/test_integration_cpu.py in a child proces
      `svit_amd.model.SViT`, with the same 405 names / order / shapes / dtypes, the same POOL_KV_STRIDE
      written into the cfg, the same no_weight_decay(), and it must load the reference model's
      state_dict with strict=True (and hand it back bit for bit).
-Prints one JSON line."""
+Prints one JSON line.  `--record` also writes the reference side to tests/golden/integration_a.json."""
 import json
 import os
 import sys
@@ -72,4 +72,17 @@ try:
     out["cpu_forward"] = "ran (WRONG: there must be no CPU path)"
 except Exception as e:  # noqa: BLE001
     out["cpu_forward"] = type(e).__name__
+if "--record" in sys.argv:
+    # tests/golden/integration_a.json: the reference side of the check as data (class names, the 405 names
+    # in order, shapes, dtypes, the cfg the constructor leaves, no_weight_decay(), the optimizer groups of
+    # the reference's construct_optimizer on both models) -- what tests/test_integration_cpu.py compares
+    # the HIP model against where the reference is not importable
+    rec = {k: out[k] for k in ("ref_class", "cfg_class", "n_ref", "numel", "pool_kv_stride_ref",
+                               "no_weight_decay_ref", "optimizer_groups_ref", "optimizer_groups_hip")}
+    rec.update({"names": list(ref_sd.keys()), "shapes": [list(v.shape) for v in ref_sd.values()],
+                "dtypes": [str(v.dtype) for v in ref_sd.values()], "num_gpus": cfg_ref.NUM_GPUS,
+                "num_frames": cfg_ref.DATA.NUM_FRAMES, "crop": cfg_ref.DATA.TRAIN_CROP_SIZE})
+    with open(os.path.join(ROOT, "tests", "golden", "integration_a.json"), "w") as f:
+        json.dump(rec, f, indent=1)
+        f.write("\n")
 print(json.dumps(out))

@@ -393,17 +393,15 @@ def test_cfg_schema_pinned_to_reference(manifest, golden_dir, tmp_path):
     assert c2.SOLVER.BASE_LR == t["SOLVER.BASE_LR"]["merged"] and isinstance(c2.SOLVER.BASE_LR, float)
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/configs/ssv2.yaml"),
-                    reason="reference checkout only exists in the build container")
 def test_reference_yaml_merges_to_the_recorded_tree(golden_dir):
-    """svit_amd.config.get_cfg().merge_from_file(<the reference's own configs/ssv2.yaml>) gives the
-    tree the reference's get_cfg() + merge gave (tests/golden/cfg.json); sections this build does
-    not know (AUG, MIXUP, DATA_LOADER, ...) merge without error."""
+    """svit_amd.config.get_cfg().merge_from_file(<the reference's own configs/ssv2.yaml, kept as
+    tests/golden/ssv2.yaml>) gives the tree the reference's get_cfg() + merge gave (tests/golden/cfg.json);
+    sections this build does not know (AUG, MIXUP, DATA_LOADER, ...) merge without error."""
     import json
     from svit_amd import config
     ref = json.load(open(os.path.join(golden_dir, "cfg.json")))
     cfg = config.get_cfg()
-    cfg.merge_from_file("/root/reference/configs/ssv2.yaml")
+    cfg.merge_from_file(os.path.join(golden_dir, "ssv2.yaml"))
     want = config.ssv2_cfg(num_gpus=ref["top_level"]["NUM_GPUS"])
     for sec in ref["sections"]:
         for k, v in ref["merged"][sec].items():

@@ -13,7 +13,8 @@ python tools/pmc_summary.py $F $W > gpurun_out/rNN_pmc_traffic.txt
 cp profiles/pmc_traffic.json gpurun_out/pmc_traffic_prev.json 2>/dev/null || true
 python tools/pmc_to_json.py gpurun_out/rNN_pmc_traffic.txt "${GIT_HEAD:-unknown}" > /dev/null && cp profiles/pmc_traffic.json gpurun_out/pmc_traffic.json
 echo "[collect] bench lines"
-python bench.py --steps 30 --warmup 5 > gpurun_out/bN.log 2>gpurun_out/bN.err
+O=${F%%/*}     # the output folder of the PMC passes above
+python bench.py --full --steps 30 --warmup 5 > $O/bN.log 2>$O/bN.err
 python bench.py --steps 20 --warmup 5 --frames-pass --no-cpu-baseline --no-kernel-trace > gpurun_out/bNf.log 2>gpurun_out/bNf.err
 echo "[collect] kernel trace"
 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/profN -- python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-kernel-trace > gpurun_out/profN.log 2>&1

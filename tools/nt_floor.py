@@ -24,7 +24,7 @@ def dump_metas(path, rest):
         json.dump([list(m) for n, e0, e1, m in trace if n == "svit_gemm_nt"], open(path, "w"))
         return orig(trace, batch)      # (sets kernel_report.phases on the module-level name, i.e. on this wrapper)
     bench.kernel_report = wrapper
-    sys.argv = ["bench.py"] + rest
+    sys.argv = ["bench.py", "--full"] + rest
     bench.main()
 
 

@@ -6,7 +6,8 @@ echo "[final] step breakdown"
 bash tools/step_breakdown.sh > gpurun_out/r06_step_breakdown.txt 2>&1
 head -10 gpurun_out/r06_step_breakdown.txt
 echo "[final] C4 32x224^2 B=4 with the kernel trace (roofline_attn_* on record)"
-python bench.py --frames 32 --batch 4 --steps 20 --warmup 5 --no-cpu-baseline > gpurun_out/r06_c4.json 2> gpurun_out/r06_c4.err
+O=$(dirname "$(ls -d */r06_step_breakdown.txt | head -1)")     # the output folder of the steps above
+python bench.py --full --frames 32 --batch 4 --steps 20 --warmup 5 --no-cpu-baseline > $O/r06_c4.json 2> $O/r06_c4.err
 tail -1 gpurun_out/r06_c4.json | cut -c1-200
 echo "[final] C1 8x224^2 B=8"
 python bench.py --frames 8 --batch 8 --steps 20 --warmup 5 --no-cpu-baseline --no-kernel-trace > gpurun_out/r06_c1.json 2> gpurun_out/r06_c1.err
