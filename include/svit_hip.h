@@ -343,7 +343,9 @@ int svit_attn_fwd(const svit_attn_fwd_args* a, void* stream);
 typedef struct {
   const void* qa; const void* ka; const void* v; const void* ctx; const void* dctx;
   const float* lse2; float* delta;  /* delta: f32 [B,h,2,Nq] scratch (-lse2/c and -rowsum(dO*O) planes) */
-  void* dqa;                        /* bf16 [B,h,Nq,DA]                                  */
+  void* dqa;                        /* bf16 [B,h,Nq,DA], every column written: dqa = ln 2 * dS ka over ALL DA columns of
+                                     * ka, so the columns past 96 + bias_cols are zero exactly when ka carries
+                                     * zeros there (as the pooling kernel writes them)   */
   float* dk; float* dv;             /* f32 [parts,B,h,Nk,96], OVERWRITTEN: parts = svit_attn_bwd_parts(args)
                                      * partial planes (one per chunk of the query range) whose SUM is the
                                      * gradient; svit_pool_ln_bwd adds them while it reads (main_parts) */

@@ -1071,6 +1071,14 @@ def test_pool_forward_one_plane_volumes(ops, B, h, hw, sq, skv, n_obj, save):
 KSC = (96 ** -0.5) * math.log2(math.e)   # what the pooling kernel multiplies the keys by (engine.K_SCALE)
 
 
+def _attn_only_within_bar(ctx, qa, ka, v, J=0):
+    """the attention-only part (ctx - residual) against float64, bar from the rounding-point emulation
+    (tests/attn_reference.py; tests/test_attention_parity_gpu.py is the thorough version of this)"""
+    from tests import attn_reference as AR
+    got, bar = AR.attn_only_vs_bar(ctx, qa, ka, v, J)
+    return got <= bar
+
+
 def _attn_ref(qa, ka, v, scale):
     """operand convention of svit_attn_fwd (include/svit_hip.h): qa . ka^T is the score in the
     log2 domain (the keys arrive multiplied by scale * log2 e)."""
@@ -1096,6 +1104,7 @@ def test_attention_fwd_bwd(ops, Nq, Nk, DA, h):
     vr = v.float().cpu().requires_grad_(True)
     ref, s = _attn_ref(qr, kr, vr, scale)
     assert rel_err(ctx, ref) < 2e-2 and cos(ctx, ref) > 0.9999
+    assert _attn_only_within_bar(ctx, qa, ka, v)
     lse_ref = torch.logsumexp(s, dim=-1) * math.log2(math.e)
     assert rel_err(lse2, lse_ref) < 1e-3
     dctx = rnd("ad%d" % Nq, (B, Nq, h * 96), 1.0, BF16)
@@ -1133,6 +1142,7 @@ def test_attention_fwd_eight_wave_path(ops, Nk):
     ctx, lse2 = ops.attn_fwd(qa, ka, v, scale)
     ref, s = _attn_ref(qa.cpu(), ka.cpu(), v.cpu(), scale)
     assert rel_err(ctx, ref) < 2e-2 and cos(ctx, ref) > 0.9999
+    assert _attn_only_within_bar(ctx, qa, ka, v)
     assert rel_err(lse2, torch.logsumexp(s, dim=-1) * math.log2(math.e)) < 1e-3
 
 
@@ -1161,6 +1171,7 @@ def test_attention_fwd_pipelined_kernel(ops, B, h, Nq, Nk, DA, J):
     ctx, lse2 = ops.attn_fwd(qa, ka, v, scale, bias_cols=J)
     ref, s = _attn_ref(qa.float().cpu(), ka.float().cpu(), v.float().cpu(), scale)
     assert rel_err(ctx, ref) < 2e-2 and cos(ctx, ref) > 0.9999
+    assert _attn_only_within_bar(ctx, qa, ka, v, J)
     assert rel_err(lse2, torch.logsumexp(s, dim=-1) * math.log2(math.e)) < 1e-3
 
 
@@ -1201,6 +1212,7 @@ def test_attention_fwd_short_key_tile(ops, B, h, Nq, Nk, J):
     assert torch.equal(ctx, ctx0) and torch.equal(lse2, lse0)
     ref, s = _attn_ref(qa.float().cpu(), ka.float().cpu(), v.float().cpu(), scale)
     assert rel_err(ctx, ref) < 2e-2 and cos(ctx, ref) > 0.9999
+    assert _attn_only_within_bar(ctx, qa, ka, v, J)
     assert rel_err(lse2, torch.logsumexp(s, dim=-1) * math.log2(math.e)) < 1e-3
 
 
@@ -1241,6 +1253,7 @@ def test_attention_large_scores(ops):
     ctx, _ = ops.attn_fwd(qa, ka, v, scale)
     ref, _ = _attn_ref(qa.cpu(), ka.cpu(), v.cpu(), scale)
     assert rel_err(ctx, ref) < 2e-2
+    assert _attn_only_within_bar(ctx, qa, ka, v)
 
 
 # ------------------------------------------------------------------- max-pool skip ------
