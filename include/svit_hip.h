@@ -78,6 +78,20 @@ int svit_gemm_tn_grouped(const svit_tn_problem* probs, int count, void* stream);
 /* ordered != 0: no split along the reduction rows -- one atomic add per dW element, i.e.
  * bit-reproducible weight gradients (regression-diff mode; slower). */
 int svit_gemm_tn_grouped_ex(const svit_tn_problem* probs, int count, int ordered, void* stream);
+/* Slab form of svit_gemm_tn_grouped (same problems, same `dW +=` / `dbias +=`, same row splits and speed class): every
+ * row split stores its fp32 tile and bias partials into its own slab of `workspace` with plain stores, and a second
+ * launch behind each group's GEMM sums the splits of every element in index order and adds the sum to dW / dbias with
+ * one plain read-modify-write -- no atomics.  Guarantee: for fixed shapes and a fixed knob table, the result depends
+ * only on the operands (not on scheduling: bit-reproducible run to run).  Groups past SVIT_TN_GROUP_MAX reuse the
+ * workspace in stream order, so a workspace belongs to ONE stream at a time.  A NULL workspace or workspace_floats
+ * below svit_gemm_tn_grouped_workspace(probs, count) is SVIT_ERR_ARG (-4), a workspace not 16-byte aligned
+ * SVIT_ERR_ALIGN, both before any launch. */
+int svit_gemm_tn_grouped_slab(const svit_tn_problem* probs, int count, float* workspace,
+                              int64_t workspace_floats, void* stream);
+/* floats of workspace that call needs (the largest of its groups); host-only arithmetic on the shapes and the knob
+ * table (no HIP call: works without a GPU), never smaller than what svit_gemm_tn_grouped_slab checks for; a negative
+ * SVIT_ERR_* for the argument errors that entry point reports. */
+int64_t svit_gemm_tn_grouped_workspace(const svit_tn_problem* probs, int count);
 /* dbias[N] (f32, atomically accumulated) += column sums of bf16 A[M,N]. */
 int svit_colsum_bf16(const void* A, int lda, float* out, int M, int N, void* stream);
 
@@ -419,6 +433,8 @@ typedef struct {
   const float* dlogits; const float* dboxes; const float* dcontact; const float* dxobj;
   float* dtokens;
   float* gw_proj; float* gb_proj; float* gw_box; float* gb_box; float* gw_bce; float* gb_bce; float* gw_con; float* gb_con;
+  int32_t ordered;   /* != 0: the box / objectness / contact gradients of ALL object rows are summed by one block per channel
+                        chunk in row order (no atomics: bit-reproducible when B*T*O exceeds one 32-row chunk); 0: a block per row chunk */
 } svit_head_bwd_args;
 int svit_head_bwd(const svit_head_bwd_args* g, void* stream);
 

@@ -1,6 +1,8 @@
 // bf16 MFMA weight-gradient GEMM for the nn.Linear family -- gfx950 only.
 //   svit_gemm_tn : dW[N,K] += A[M,N]^T * B[M,K]  (reduction over rows, operands consumed
 //                  through ds_read_b64_tr_b16 transposed LDS reads; fused bias gradient)
+//   svit_gemm_tn_grouped_slab : the grouped form with the row splits stored to slabs and summed in split order by a
+//                  second launch instead of meeting in fp32 atomics (bit-reproducible weight gradients)
 // (the forward / dgrad kernel svit_gemm_nt lives in gemm_nt.hip)
 #include <algorithm>
 #include <type_traits>
@@ -85,7 +87,12 @@ __device__ __forceinline__ void tn_read_tr(s16x4_t& d, unsigned addr) {
   asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=&v"(d) : "v"(addr), "i"(OFF) : "memory");
 }
 
-template <class C>
+// SLAB selects the flush.  false: the fp32 tile (and the bias column sums) meet the other row splits in atomicAdd on
+// dW / dbias.  true: dW is this workgroup's OWN slab of TN x lddw floats (lddw = the slab's column count) and dbias
+// its own TN bias partials; both are written with plain stores and summed in split order by tn_slab_reduce_kernel.
+// Slab element (row, col) of the tile sits at ((row / 4) * lddw + col) * 4 + row % 4: the four accumulator rows a lane
+// holds for one column are one 16-byte store, and the lanes of a half-wave cover 32 adjacent columns (512 B).
+template <class C, bool SLAB>
 __device__ __forceinline__ void tn_tile_dma(unsigned char* lds, const bf16_t* __restrict__ A, int lda,
                                             const bf16_t* __restrict__ B, int ldb,
                                             float* __restrict__ dW, int lddw, int M, int N, int K, int n0,
@@ -232,6 +239,22 @@ __device__ __forceinline__ void tn_tile_dma(unsigned char* lds, const bf16_t* __
       __builtin_amdgcn_sched_barrier(0);
     });
   }
+  if constexpr (SLAB) {
+#pragma unroll
+    for (int i = 0; i < RB; ++i)
+#pragma unroll
+      for (int j = 0; j < 3; ++j) {
+        const int tcol = wk * 96 + j * 32 + (lane & 31);
+        if (k0 + tcol >= K) continue;
+#pragma unroll
+        for (int r4 = 0; r4 < 4; ++r4) {
+          const int trow = wn * 32 * RB + i * 32 + acc_row(4 * r4, lane);      // first of four adjacent rows
+          if (n0 + trow < N)
+            *(float4*)(dW + ((size_t)(trow >> 2) * lddw + tcol) * 4) =
+                make_float4(acc[i][j][4 * r4], acc[i][j][4 * r4 + 1], acc[i][j][4 * r4 + 2], acc[i][j][4 * r4 + 3]);
+        }
+      }
+  } else {
 #pragma unroll
   for (int i = 0; i < RB; ++i)
 #pragma unroll
@@ -248,6 +271,7 @@ __device__ __forceinline__ void tn_tile_dma(unsigned char* lds, const bf16_t* __
 #endif
       }
     }
+  }
   if (do_bias) {  // RP threads share a column chunk: reduce through LDS, one atomic per column
     constexpr int CPR = C::TN / 8, RP = NT / CPR;
     static_assert(BM % RP == 0, "whole passes over a stage");
@@ -260,7 +284,8 @@ __device__ __forceinline__ void tn_tile_dma(unsigned char* lds, const bf16_t* __
       float sum = 0.f;
 #pragma unroll
       for (int g = 0; g < RP; ++g) sum += red[g * C::TN + tid];
-      atomicAdd(dbias + n0 + tid, sum);
+      if constexpr (SLAB) dbias[tid] = sum;
+      else atomicAdd(dbias + n0 + tid, sum);
     }
   }
 #endif
@@ -276,7 +301,7 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(const bf16_t* __restrict__
                                                       float* __restrict__ dbias) {
   __shared__ __attribute__((aligned(16))) unsigned char lds[TN_DMA_LDS];
   const int m_begin = blockIdx.z * rows_per_split;
-  tn_tile_dma<TnSmallD>(lds, A, lda, B, ldb, dW, lddw, M, N, K, blockIdx.x * TN_TN, blockIdx.y * TN_TK, m_begin,
+  tn_tile_dma<TnSmallD, false>(lds, A, lda, B, ldb, dW, lddw, M, N, K, blockIdx.x * TN_TN, blockIdx.y * TN_TK, m_begin,
                         min(M, m_begin + rows_per_split), dbias, blockIdx.y == 0);
 }
 
@@ -317,13 +342,121 @@ __global__ __launch_bounds__(256, SVIT_TN_WPE) void gemm_tn_grouped_kernel(const
   const int tn = tile % g.tiles_n[pi], tk = tile / g.tiles_n[pi];
   const int m_begin = split * g.rows_per_split[pi];
   if (g.big[pi])
-    tn_tile_dma<TnBigD>(lds, (const bf16_t*)p.A, p.lda, (const bf16_t*)p.B, p.ldb, p.dW, p.lddw, p.M, p.N, p.K,
+    tn_tile_dma<TnBigD, false>(lds, (const bf16_t*)p.A, p.lda, (const bf16_t*)p.B, p.ldb, p.dW, p.lddw, p.M, p.N, p.K,
                         tn * TnBig::TN, tk * TnBig::TK, m_begin, min(p.M, m_begin + g.rows_per_split[pi]),
                         p.dbias, tk == 0);
   else
-    tn_tile_dma<TnSmallD>(lds, (const bf16_t*)p.A, p.lda, (const bf16_t*)p.B, p.ldb, p.dW, p.lddw, p.M, p.N, p.K,
+    tn_tile_dma<TnSmallD, false>(lds, (const bf16_t*)p.A, p.lda, (const bf16_t*)p.B, p.ldb, p.dW, p.lddw, p.M, p.N, p.K,
                           tn * TnSmall::TN, tk * TnSmall::TK, m_begin, min(p.M, m_begin + g.rows_per_split[pi]),
                           p.dbias, tk == 0);
+}
+
+// ---------------------------------------------------------------------------------------
+// Slab form (svit_gemm_tn_grouped_slab): the same grid and the same main loop, but no two workgroups
+// ever write one address.  Workgroup (problem, split, tile) -- its LOGICAL id, not the XCD-remapped
+// block index -- stores its fp32 tile into slab number `local` of its problem and, on k-tile 0 of a
+// problem with a bias, its 128 bias partials into the second region; tn_slab_reduce_kernel, launched
+// right behind on the same stream, sums the splits of every output element in index order and adds
+// the sum to dW / dbias with one plain read-modify-write.  One writer per element: the result does
+// not depend on how the workgroups were scheduled.
+struct TnSlabs {
+  long long tile_off[SVIT_TN_GROUP_MAX];   // float offset of the problem's slab 0 (slab = 128 x w floats)
+  long long bias_off[SVIT_TN_GROUP_MAX];   // float offset of its bias partials [split][n tile][128]
+  int red_first[SVIT_TN_GROUP_MAX + 1];    // first block of the reduce grid
+  int w[SVIT_TN_GROUP_MAX];                // slab columns: min(tile width, K rounded up to 32)
+};
+constexpr int TN_RED_THREADS = 128;
+static_assert(TnSmall::TN == 128 && TnBig::TN == 128, "slabs and bias partials are 128 rows");
+
+__global__ __launch_bounds__(256, SVIT_TN_WPE) void gemm_tn_grouped_slab_kernel(const TnGroup g, const TnSlabs sl,
+                                                                               float* __restrict__ ws) {
+  __shared__ __attribute__((aligned(16))) unsigned char lds[TN_DMA_LDS];
+  // (placement as in gemm_tn_grouped_kernel)
+  const int nwg = gridDim.x, lin = blockIdx.x;
+  const int xq = nwg >> 3, xr = nwg & 7, xcd = lin & 7;
+  int pi = 0;
+  const int bid = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + (lin >> 3);
+#pragma unroll
+  for (int i = 1; i < SVIT_TN_GROUP_MAX; ++i)
+    if (i < g.count && bid >= g.first_block[i]) pi = i;
+  const int local = bid - g.first_block[pi];
+  const int tile = local % g.tiles[pi], split = local / g.tiles[pi];
+  const svit_tn_problem& p = g.p[pi];
+  const int tn = tile % g.tiles_n[pi], tk = tile / g.tiles_n[pi];
+  const int m_begin = split * g.rows_per_split[pi];
+  const int w = sl.w[pi];
+  float* slab = ws + sl.tile_off[pi] + (long long)local * (128 * w);
+  float* bslab = p.dbias ? ws + sl.bias_off[pi] + (long long)(split * g.tiles_n[pi] + tn) * 128 : nullptr;
+  if (g.big[pi])
+    tn_tile_dma<TnBigD, true>(lds, (const bf16_t*)p.A, p.lda, (const bf16_t*)p.B, p.ldb, slab, w, p.M, p.N, p.K,
+                              tn * TnBig::TN, tk * TnBig::TK, m_begin, min(p.M, m_begin + g.rows_per_split[pi]),
+                              bslab, tk == 0);
+  else
+    tn_tile_dma<TnSmallD, true>(lds, (const bf16_t*)p.A, p.lda, (const bf16_t*)p.B, p.ldb, slab, w, p.M, p.N, p.K,
+                                tn * TnSmall::TN, tk * TnSmall::TK, m_begin, min(p.M, m_begin + g.rows_per_split[pi]),
+                                bslab, tk == 0);
+}
+
+// thread -> (four adjacent rows, one column) of one problem's dW, consecutive lanes on consecutive
+// columns; behind the K * ceil(N / 4) matrix threads of a problem with a bias, ceil(N / 4) threads
+// take four bias columns each.  Every slab read is one 16-byte load.
+__global__ __launch_bounds__(TN_RED_THREADS) void tn_slab_reduce_kernel(const TnGroup g, const TnSlabs sl,
+                                                                        const float* __restrict__ ws) {
+#pragma clang fp reassociate(off)      // (-ffast-math: the sum below is in split order)
+  int pi = 0;
+  const int blk = blockIdx.x;
+#pragma unroll
+  for (int i = 1; i < SVIT_TN_GROUP_MAX; ++i)
+    if (i < g.count && blk >= sl.red_first[i]) pi = i;
+  const svit_tn_problem& p = g.p[pi];
+  const int N = p.N, K = p.K, rg_n = (N + 3) >> 2;
+  const int tiles = g.tiles[pi], tiles_n = g.tiles_n[pi];
+  const int S = (g.first_block[pi + 1] - g.first_block[pi]) / tiles;
+  const long long e = (long long)(blk - sl.red_first[pi]) * TN_RED_THREADS + threadIdx.x;
+  const long long nmat = (long long)rg_n * K;
+  const float* src;
+  long long stride;       // floats between the same element of consecutive splits
+  if (e < nmat) {
+    const int rg = (int)(e / K), col = (int)(e - (long long)rg * K);
+    const int tk_w = g.big[pi] ? TnBig::TK : TnSmall::TK, w = sl.w[pi];
+    const int tile = (col / tk_w) * tiles_n + rg / 32;
+    stride = (long long)tiles * (128 * w);
+    src = ws + sl.tile_off[pi] + (long long)tile * (128 * w) + ((long long)(rg % 32) * w + col % tk_w) * 4;
+  } else if (p.dbias && e < nmat + rg_n) {
+    const int n = (int)(e - nmat) * 4;
+    stride = (long long)tiles_n * 128;
+    src = ws + sl.bias_off[pi] + (long long)(n / 128) * 128 + n % 128;
+  } else {
+    return;
+  }
+  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+  int s = 0;
+  for (; s + 8 <= S; s += 8) {       // eight loads in flight, added in index order
+    float4 v[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) v[u] = *(const float4*)(src + (s + u) * stride);
+#pragma unroll
+    for (int u = 0; u < 8; ++u) { a0 += v[u].x; a1 += v[u].y; a2 += v[u].z; a3 += v[u].w; }
+  }
+  for (; s < S; ++s) {
+    const float4 v = *(const float4*)(src + s * stride);
+    a0 += v.x; a1 += v.y; a2 += v.z; a3 += v.w;
+  }
+  if (e < nmat) {
+    const int rg = (int)(e / K), col = (int)(e - (long long)rg * K), row = rg * 4;
+    float* d = p.dW + (size_t)row * p.lddw + col;
+    d[0] += a0;
+    if (row + 1 < N) d[p.lddw] += a1;
+    if (row + 2 < N) d[2 * (size_t)p.lddw] += a2;
+    if (row + 3 < N) d[3 * (size_t)p.lddw] += a3;
+  } else {
+    const int n = (int)(e - nmat) * 4;
+    float* d = p.dbias + n;
+    d[0] += a0;
+    if (n + 1 < N) d[1] += a1;
+    if (n + 2 < N) d[2] += a2;
+    if (n + 3 < N) d[3] += a3;
+  }
 }
 
 __global__ void colsum_kernel(const bf16_t* __restrict__ A, int lda, float* __restrict__ out,
@@ -407,7 +540,86 @@ static int tn_check(const svit_tn_problem& p) {
 }
 
 
-static int tn_grouped(const svit_tn_problem* probs, int count, int ordered, void* stream);
+// The ONE split planner: fills g for problems [0, n) (n <= SVIT_TN_GROUP_MAX) and returns the grid size.  A pure
+// function of the shapes and the knob table (the atomic launch, the slab launch and the slab workspace query share it).
+static int tn_plan(const svit_tn_problem* probs, int n, int ordered, TnGroup& g) {
+  g.count = n;
+  long max_steps = 1;
+  const int big_mode = svit_knob(SVIT_K_TN_TILE);
+  const double step_us = svit_knob(SVIT_K_TN_STEP_US_X100) * 0.01, atomic_tbs = svit_knob(SVIT_K_TN_ATOMIC_TBS_X100) * 0.01;
+  constexpr long slots = 512;      // resident 4-wave workgroups the planner counts on
+  int bm[SVIT_TN_GROUP_MAX];
+  double tile_bytes[SVIT_TN_GROUP_MAX];
+  for (int i = 0; i < g.count; ++i) {
+    g.p[i] = probs[i];
+    // 128 x 192 tiles where they are fully used (K a multiple of 192) and measured faster with the
+    // round-3 LDS-DMA body (tools/bench_kernels.py tngroup, profiles/r03_tn_tile_modes.txt): the
+    // M = 3656 groups of blocks 14-15 (-5 / -11 %) and the M = 50696 groups of blocks 2-3 (-16 / -22 %);
+    // not the M = 13064 groups of blocks 4-13 (+10 %: the doubled fp32 tile a workgroup flushes with
+    // atomics outweighs the smaller operand traffic) nor the M = 201224 group of block 0 (+11 %)
+    g.big[i] = big_mode == 1 ? (g.p[i].K % TnBig::TK == 0 && g.p[i].N >= 128 &&
+                                (g.p[i].M <= 4096 || (g.p[i].M >= 32768 && g.p[i].M < 131072)))
+               : big_mode == 3 ? (g.p[i].K % TnBig::TK == 0 && g.p[i].N >= 128)
+                               : (big_mode == 2);
+    const int tn = g.big[i] ? TnBig::TN : TnSmall::TN, tk = g.big[i] ? TnBig::TK : TnSmall::TK;
+    bm[i] = g.big[i] ? TnBigD::BM : TnSmall::BM;
+    tile_bytes[i] = (double)tn * tk * 4.0;
+    g.tiles_n[i] = (g.p[i].N + tn - 1) / tn;
+    g.tiles[i] = g.tiles_n[i] * ((g.p[i].K + tk - 1) / tk);
+    const long st = (g.p[i].M + bm[i] - 1) / bm[i];
+    if (st > max_steps) max_steps = st;
+  }
+  // Every problem is cut into chunks of `steps` steps (64 reduction rows on 128 x 96 tiles, 32 on
+  // 128 x 192: the same 12 MFMAs per wave), so all workgroups run about equally long.  Same
+  // fitted model as svit_gemm_tn: 0.85 us per step with 512 resident workgroups, plus the atomic
+  // flush of one fp32 tile per workgroup at ~0.75 TB/s.
+  double best = 1e30;
+  long best_steps = max_steps;
+  for (long steps = 2; steps <= max_steps; steps += (steps < 32 ? 1 : steps / 16)) {
+    long blocks = 0;
+    double flush = 0.0;
+    for (int i = 0; i < g.count; ++i) {
+      const long st = (g.p[i].M + bm[i] - 1) / bm[i];
+      const long nb = (long)g.tiles[i] * ((st + steps - 1) / steps);
+      blocks += nb;
+      flush += (double)nb * tile_bytes[i];
+    }
+    const double t = (double)((blocks + slots - 1) / slots) * steps * step_us +
+                     flush / (atomic_tbs * 1e6);
+    if (t < best) { best = t; best_steps = steps; }
+  }
+  if (ordered) best_steps = max_steps;
+  int total = 0;
+  for (int i = 0; i < g.count; ++i) {
+    g.rows_per_split[i] = (int)best_steps * bm[i];
+    const int splits = (g.p[i].M + g.rows_per_split[i] - 1) / g.rows_per_split[i];
+    g.first_block[i] = total;
+    total += g.tiles[i] * splits;
+  }
+  for (int i = g.count; i <= SVIT_TN_GROUP_MAX; ++i) g.first_block[i] = total;
+  return total;
+}
+
+static int tn_check_all(const svit_tn_problem* probs, int count) {
+  if (!probs || count <= 0) return SVIT_ERR_ARG;
+  for (int i = 0; i < count; ++i) {
+    const int rc = tn_check(probs[i]);
+    if (rc) return rc;
+  }
+  return SVIT_OK;
+}
+
+static int tn_grouped(const svit_tn_problem* probs, int count, int ordered, void* stream) {
+  const int rc = tn_check_all(probs, count);
+  if (rc) return rc;
+  for (int base = 0; base < count; base += SVIT_TN_GROUP_MAX) {
+    TnGroup g;
+    const int total = tn_plan(probs + base, count - base < SVIT_TN_GROUP_MAX ? count - base : SVIT_TN_GROUP_MAX, ordered, g);
+    hipLaunchKernelGGL(gemm_tn_grouped_kernel, dim3(total), dim3(256), 0, (hipStream_t)stream, g);
+    SVIT_LAUNCH_CHECK();
+  }
+  return SVIT_OK;
+}
 
 extern "C" int svit_gemm_tn_grouped(const svit_tn_problem* probs, int count, void* stream) {
   return tn_grouped(probs, count, 0, stream);
@@ -421,69 +633,60 @@ extern "C" int svit_gemm_tn_grouped_ex(const svit_tn_problem* probs, int count, 
   return tn_grouped(probs, count, ordered, stream);
 }
 
-static int tn_grouped(const svit_tn_problem* probs, int count, int ordered, void* stream) {
-  if (!probs || count <= 0) return SVIT_ERR_ARG;
-  for (int i = 0; i < count; ++i) {
-    const int rc = tn_check(probs[i]);
-    if (rc) return rc;
+// slab regions of a planned group -> floats of workspace (every offset a multiple of 4 floats)
+static int64_t tn_slab_layout(const TnGroup& g, TnSlabs& sl) {
+  long long off = 0;
+  int red = 0;
+  for (int i = 0; i < g.count; ++i) {
+    const int tk = g.big[i] ? TnBig::TK : TnSmall::TK, k32 = (g.p[i].K + 31) / 32 * 32;
+    sl.w[i] = k32 < tk ? k32 : tk;
+    sl.tile_off[i] = off;
+    off += (long long)(g.first_block[i + 1] - g.first_block[i]) * (128 * sl.w[i]);
   }
+  for (int i = 0; i < g.count; ++i) {
+    sl.bias_off[i] = off;
+    const int splits = (g.first_block[i + 1] - g.first_block[i]) / g.tiles[i];
+    if (g.p[i].dbias) off += (long long)splits * g.tiles_n[i] * 128;
+    const long long rg_n = (g.p[i].N + 3) / 4, thr = rg_n * g.p[i].K + (g.p[i].dbias ? rg_n : 0);
+    sl.red_first[i] = red;
+    red += (int)((thr + TN_RED_THREADS - 1) / TN_RED_THREADS);
+  }
+  for (int i = g.count; i < SVIT_TN_GROUP_MAX; ++i) sl.tile_off[i] = sl.bias_off[i] = 0, sl.w[i] = 0;
+  for (int i = g.count; i <= SVIT_TN_GROUP_MAX; ++i) sl.red_first[i] = red;
+  return off;
+}
+
+extern "C" int64_t svit_gemm_tn_grouped_workspace(const svit_tn_problem* probs, int count) {
+  const int rc = tn_check_all(probs, count);
+  if (rc) return rc;
+  int64_t need = 0;
   for (int base = 0; base < count; base += SVIT_TN_GROUP_MAX) {
     TnGroup g;
-    g.count = count - base < SVIT_TN_GROUP_MAX ? count - base : SVIT_TN_GROUP_MAX;
-    long max_steps = 1;
-    const int big_mode = svit_knob(SVIT_K_TN_TILE);
-    const double step_us = svit_knob(SVIT_K_TN_STEP_US_X100) * 0.01, atomic_tbs = svit_knob(SVIT_K_TN_ATOMIC_TBS_X100) * 0.01;
-    constexpr long slots = 512;      // resident 4-wave workgroups the planner counts on
-    int bm[SVIT_TN_GROUP_MAX];
-    double tile_bytes[SVIT_TN_GROUP_MAX];
-    for (int i = 0; i < g.count; ++i) {
-      g.p[i] = probs[base + i];
-      // 128 x 192 tiles where they are fully used (K a multiple of 192) and measured faster with the
-      // round-3 LDS-DMA body (tools/bench_kernels.py tngroup, profiles/r03_tn_tile_modes.txt): the
-      // M = 3656 groups of blocks 14-15 (-5 / -11 %) and the M = 50696 groups of blocks 2-3 (-16 / -22 %);
-      // not the M = 13064 groups of blocks 4-13 (+10 %: the doubled fp32 tile a workgroup flushes with
-      // atomics outweighs the smaller operand traffic) nor the M = 201224 group of block 0 (+11 %)
-      g.big[i] = big_mode == 1 ? (g.p[i].K % TnBig::TK == 0 && g.p[i].N >= 128 &&
-                                  (g.p[i].M <= 4096 || (g.p[i].M >= 32768 && g.p[i].M < 131072)))
-                 : big_mode == 3 ? (g.p[i].K % TnBig::TK == 0 && g.p[i].N >= 128)
-                                 : (big_mode == 2);
-      const int tn = g.big[i] ? TnBig::TN : TnSmall::TN, tk = g.big[i] ? TnBig::TK : TnSmall::TK;
-      bm[i] = g.big[i] ? TnBigD::BM : TnSmall::BM;
-      tile_bytes[i] = (double)tn * tk * 4.0;
-      g.tiles_n[i] = (g.p[i].N + tn - 1) / tn;
-      g.tiles[i] = g.tiles_n[i] * ((g.p[i].K + tk - 1) / tk);
-      const long st = (g.p[i].M + bm[i] - 1) / bm[i];
-      if (st > max_steps) max_steps = st;
-    }
-    // Every problem is cut into chunks of `steps` steps (64 reduction rows on 128 x 96 tiles, 32 on
-    // 128 x 192: the same 12 MFMAs per wave), so all workgroups run about equally long.  Same
-    // fitted model as svit_gemm_tn: 0.85 us per step with 512 resident workgroups, plus the atomic
-    // flush of one fp32 tile per workgroup at ~0.75 TB/s.
-    double best = 1e30;
-    long best_steps = max_steps;
-    for (long steps = 2; steps <= max_steps; steps += (steps < 32 ? 1 : steps / 16)) {
-      long blocks = 0;
-      double flush = 0.0;
-      for (int i = 0; i < g.count; ++i) {
-        const long st = (g.p[i].M + bm[i] - 1) / bm[i];
-        const long nb = (long)g.tiles[i] * ((st + steps - 1) / steps);
-        blocks += nb;
-        flush += (double)nb * tile_bytes[i];
-      }
-      const double t = (double)((blocks + slots - 1) / slots) * steps * step_us +
-                       flush / (atomic_tbs * 1e6);
-      if (t < best) { best = t; best_steps = steps; }
-    }
-    if (ordered) best_steps = max_steps;
-    int total = 0;
-    for (int i = 0; i < g.count; ++i) {
-      g.rows_per_split[i] = (int)best_steps * bm[i];
-      const int splits = (g.p[i].M + g.rows_per_split[i] - 1) / g.rows_per_split[i];
-      g.first_block[i] = total;
-      total += g.tiles[i] * splits;
-    }
-    for (int i = g.count; i <= SVIT_TN_GROUP_MAX; ++i) g.first_block[i] = total;
-    hipLaunchKernelGGL(gemm_tn_grouped_kernel, dim3(total), dim3(256), 0, (hipStream_t)stream, g);
+    TnSlabs sl;
+    tn_plan(probs + base, count - base < SVIT_TN_GROUP_MAX ? count - base : SVIT_TN_GROUP_MAX, 0, g);
+    const int64_t n = tn_slab_layout(g, sl);
+    if (n > need) need = n;
+  }
+  return need;
+}
+
+extern "C" int svit_gemm_tn_grouped_slab(const svit_tn_problem* probs, int count, float* workspace,
+                                         int64_t workspace_floats, void* stream) {
+  const int64_t need = svit_gemm_tn_grouped_workspace(probs, count);
+  if (need < 0) return (int)need;
+  if (!workspace || workspace_floats < need) return SVIT_ERR_ARG;
+  if ((uintptr_t)workspace & 15) return SVIT_ERR_ALIGN;
+  // every group chunk reuses the workspace from offset 0: the chunk's reduce is behind its GEMM and in front of the
+  // next chunk's GEMM on the one stream
+  for (int base = 0; base < count; base += SVIT_TN_GROUP_MAX) {
+    TnGroup g;
+    TnSlabs sl;
+    const int total = tn_plan(probs + base, count - base < SVIT_TN_GROUP_MAX ? count - base : SVIT_TN_GROUP_MAX, 0, g);
+    tn_slab_layout(g, sl);
+    hipLaunchKernelGGL(gemm_tn_grouped_slab_kernel, dim3(total), dim3(256), 0, (hipStream_t)stream, g, sl, workspace);
+    SVIT_LAUNCH_CHECK();
+    hipLaunchKernelGGL(tn_slab_reduce_kernel, dim3(sl.red_first[SVIT_TN_GROUP_MAX]), dim3(TN_RED_THREADS), 0,
+                       (hipStream_t)stream, g, sl, (const float*)workspace);
     SVIT_LAUNCH_CHECK();
   }
   return SVIT_OK;

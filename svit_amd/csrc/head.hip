@@ -154,41 +154,53 @@ __global__ __launch_bounds__(HEAD_NT) void head_bwd_kernel(svit_head_bwd_args g,
   blk -= n1;
   if (blk < n2) {
     if (!g.dboxes && !g.dcontact) return;
-    const int rc = blk / cchunks, c = (blk % cchunks) * HEAD_NT + threadIdx.x;
-    const int n_rows = a.B * (R - 1), i0 = rc * HB_RC, nr = min(HB_RC, n_rows - i0);
-    for (int i = threadIdx.x; i < HB_RC * 10; i += HEAD_NT) {
-      const int ri = i / 10, k = i % 10, row = i0 + ri;
-      float dz = 0.f;
-      if (ri < nr) {
-        const int b = row / (R - 1), r = 1 + row % (R - 1);
-        dz = k < 4 ? head_dz(g, b, r, 1, k) : k < 5 ? head_dz(g, b, r, 2, 0) : head_dz(g, b, r, 3, k - 5);
-      }
-      dzs[i] = dz;
-    }
-    __syncthreads();
-    if (c < a.C) {
-      float acc[10];
+    // g.ordered: ONE block per channel chunk walks every row chunk in order and is the only writer of its
+    // gradient elements (plain +=); otherwise a block per row chunk, meeting the others in fp32 atomics
+    const int c = (blk % cchunks) * HEAD_NT + threadIdx.x;
+    const int n_rows = a.B * (R - 1);
+    const int rc0 = g.ordered ? 0 : blk / cchunks, rc1 = g.ordered ? (n_rows + HB_RC - 1) / HB_RC : rc0 + 1;
+    float acc[10], sb = 0.f;
 #pragma unroll
-      for (int k = 0; k < 10; ++k) acc[k] = 0.f;
+    for (int k = 0; k < 10; ++k) acc[k] = 0.f;
+    for (int rc = rc0; rc < rc1; ++rc) {
+      const int i0 = rc * HB_RC, nr = min(HB_RC, n_rows - i0);
+      if (rc > rc0) __syncthreads();
+      for (int i = threadIdx.x; i < HB_RC * 10; i += HEAD_NT) {
+        const int ri = i / 10, k = i % 10, row = i0 + ri;
+        float dz = 0.f;
+        if (ri < nr) {
+          const int b = row / (R - 1), r = 1 + row % (R - 1);
+          dz = k < 4 ? head_dz(g, b, r, 1, k) : k < 5 ? head_dz(g, b, r, 2, 0) : head_dz(g, b, r, 3, k - 5);
+        }
+        dzs[i] = dz;
+      }
+      __syncthreads();
+      if (c < a.C) {
 #pragma unroll 8
-      for (int ri = 0; ri < nr; ++ri) {
-        const int row = i0 + ri, b = row / (R - 1), r = 1 + row % (R - 1);
-        float xv = a.tokens[((size_t)b * a.N + head_row(a, r)) * a.C + c];
-        if (a.keep) xv *= a.keep[((size_t)b * R + r) * a.C + c];
+        for (int ri = 0; ri < nr; ++ri) {
+          const int row = i0 + ri, b = row / (R - 1), r = 1 + row % (R - 1);
+          float xv = a.tokens[((size_t)b * a.N + head_row(a, r)) * a.C + c];
+          if (a.keep) xv *= a.keep[((size_t)b * R + r) * a.C + c];
 #pragma unroll
-        for (int k = 0; k < 10; ++k) acc[k] += dzs[ri * 10 + k] * xv;
+          for (int k = 0; k < 10; ++k) acc[k] += dzs[ri * 10 + k] * xv;
+        }
       }
+      if (blk % cchunks == 0 && threadIdx.x < 10)
+        for (int ri = 0; ri < nr; ++ri) sb += dzs[ri * 10 + threadIdx.x];
+    }
+    if (c < a.C) {
 #pragma unroll
       for (int k = 0; k < 10; ++k) {
         float* gw = k < 4 ? g.gw_box + (size_t)k * a.C : k < 5 ? g.gw_bce : g.gw_con + (size_t)(k - 5) * a.C;
-        atomicAdd(gw + c, acc[k]);
+        if (g.ordered) gw[c] += acc[k];
+        else atomicAdd(gw + c, acc[k]);
       }
     }
     if (blk % cchunks == 0 && threadIdx.x < 10) {
       const int k = threadIdx.x;
-      float sb = 0.f;
-      for (int ri = 0; ri < nr; ++ri) sb += dzs[ri * 10 + k];
-      atomicAdd(k < 4 ? g.gb_box + k : k < 5 ? g.gb_bce : g.gb_con + (k - 5), sb);
+      float* gb = k < 4 ? g.gb_box + k : k < 5 ? g.gb_bce : g.gb_con + (k - 5);
+      if (g.ordered) *gb += sb;
+      else atomicAdd(gb, sb);
     }
     return;
   }
@@ -299,7 +311,7 @@ extern "C" int svit_head_bwd(const svit_head_bwd_args* g, void* stream) {
   if (a.n_cls > HB_CLS_MAX) return SVIT_ERR_SHAPE;
   const int cchunks = (a.C + HEAD_NT - 1) / HEAD_NT;
   const int n1 = ((a.n_cls + HB_OC - 1) / HB_OC) * cchunks;
-  const int n2 = ((a.B * a.T * a.O + HB_RC - 1) / HB_RC) * cchunks;
+  const int n2 = (g->ordered ? 1 : (a.B * a.T * a.O + HB_RC - 1) / HB_RC) * cchunks;
   const int n3 = cchunks;
   const int rows_per_block = 8, rb = (a.N - 1 + rows_per_block - 1) / rows_per_block;
   hipLaunchKernelGGL(head_bwd_kernel, dim3((unsigned)(n1 + n2 + n3 + a.B * rb)), dim3(HEAD_NT), 0, (hipStream_t)stream,

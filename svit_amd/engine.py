@@ -232,6 +232,11 @@ class Engine:
         # dk/dv query splits, the row splits of the grouped weight-gradient GEMM) runs unsplit, so
         # the whole backward is bit-reproducible run to run (several times slower)
         self.deterministic = False
+        # reproducible training at full speed (cfg.SVIT.REPRODUCIBLE): the weight-gradient GEMMs keep their row splits
+        # but flush into slabs that a second launch sums in split order (ops.gemm_tn_grouped_slab) -- the one reduction
+        # of the default step that meets in fp32 atomics.  Same seed, same gradients bit for bit, run to run, for a
+        # fixed batch shape and library build.  `deterministic` wins if both are set.
+        self.reproducible = False
         self._capture_fork = None   # set by svit_amd/graph.py while it captures: (fn) -> None
         self._capture_join = None
 
@@ -481,8 +486,7 @@ class Engine:
         ops.special_token_grads(dx, f.g("cls_token"), f.g("object_queries"),
                                 f.g("pos_embed_temporal") if Tx > 1 else None, L, Tx, O, Tx > 1)
         dtok = ops.scale_cast(dx, gather=(L, 1))       # patch rows of every clip -> bf16 [B*L, C]
-        ops.gemm_tn(dtok, st["cols"], f.g("patch_embed.proj.weight").view(C, 441),
-                    splits=1 if self.deterministic else 0, dbias=f.g("patch_embed.proj.bias"))
+        self._gemm_tn(dtok, st["cols"], f.g("patch_embed.proj.weight").view(C, 441), f.g("patch_embed.proj.bias"))
         self._flush_tn()
         self._join()
         ready(depth + 1)
@@ -545,7 +549,21 @@ class Engine:
         if not q:
             return
         det = self.deterministic
+        if self.reproducible and not det:
+            # all queued weight-gradient work of a step sits on one stream (the side stream when overlap_wgrad is on):
+            # one slab workspace serves every flush
+            self._fork(lambda: ops.gemm_tn_grouped_slab(q, tag="tn_slab_queue"), q)
+            return
         self._fork(lambda: ops.gemm_tn_grouped(q, ordered=det), q)
+
+    def _gemm_tn(self, a, b, dw, dbias=None):
+        """a stand-alone weight-gradient GEMM on the CURRENT stream (patch embed; interpolated rel-pos tables)"""
+        if self.deterministic:
+            ops.gemm_tn(a, b, dw, splits=1, dbias=dbias)
+        elif self.reproducible:       # a one-problem group; its own workspace: the queued groups may be on the side stream
+            ops.gemm_tn_grouped_slab([(a, b, dw, dbias)], tag="tn_slab_main")
+        else:
+            ops.gemm_tn(a, b, dw, splits=0, dbias=dbias)
 
     def _linear_bwd(self, dy16, x16, wname, bname, need_dx, out=None, accumulate=False,
                     epilogue=hip.EPI_F32, aux=None):
@@ -618,7 +636,7 @@ class Engine:
                 self._tn.append((D[:, o:o + rows], qa2[:, :HD], f.g(n), None))
             else:
                 d = torch.zeros_like(t)
-                ops.gemm_tn(D[:, o:o + rows], qa2[:, :HD], d, splits=1 if self.deterministic else 0)
+                self._gemm_tn(D[:, o:o + rows], qa2[:, :HD], d)
                 f.g(n).add_(m.t() @ d)
         if dq_extra is None:      # wide tables (56x56 / 28x28 stages) or the A/B path: dq = D R as its own GEMM
             # (bf16 epilogue since round 5: the pooled-LN backward adds it to two other bf16 addends -- dq of the attention

@@ -116,7 +116,7 @@ class HeadArgs(C.Structure):
 class HeadBwdArgs(C.Structure):
     _fields_ = [("f", HeadArgs), ("dlogits", vp), ("dboxes", vp), ("dcontact", vp), ("dxobj", vp), ("dtokens", vp),
                 ("gw_proj", vp), ("gb_proj", vp), ("gw_box", vp), ("gb_box", vp), ("gw_bce", vp), ("gb_bce", vp),
-                ("gw_con", vp), ("gb_con", vp)]
+                ("gw_con", vp), ("gb_con", vp), ("ordered", i32)]
 
 
 _SIGS = {
@@ -126,6 +126,8 @@ _SIGS = {
     "svit_gemm_tn": (i32, [vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, vp, vp]),
     "svit_gemm_tn_grouped": (i32, [C.POINTER(TnProblem), i32, vp]),
     "svit_gemm_tn_grouped_ex": (i32, [C.POINTER(TnProblem), i32, i32, vp]),
+    "svit_gemm_tn_grouped_slab": (i32, [C.POINTER(TnProblem), i32, vp, i64, vp]),
+    "svit_gemm_tn_grouped_workspace": (i64, [C.POINTER(TnProblem), i32]),
     "svit_colsum_bf16": (i32, [vp, i32, vp, i32, i32, vp]),
     "svit_cast_f32_bf16": (i32, [vp, vp, i64, vp]),
     "svit_table_interp": (i32, [vp, i32, i32, vp, vp, vp, vp]),

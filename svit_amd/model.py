@@ -101,7 +101,8 @@ class _HeadFn(torch.autograd.Function):
         pairs = model.head.param_pairs()
         with torch.no_grad():
             dtok = ops.head_bwd(tokens, ctx.T, ctx.O, keep, [(w.data, b.data) for w, b in pairs], boxes,
-                                (dlogits, dboxes, dcontact, dxobj), [(w.grad, b.grad) for w, b in pairs])
+                                (dlogits, dboxes, dcontact, dxobj), [(w.grad, b.grad) for w, b in pairs],
+                                ordered=model.engine.reproducible)
         return None, dtok, None, None, None
 
 
@@ -261,6 +262,8 @@ class SViT(nn.Module):
             p.grad = None
         self.flat = flat
         self.engine = Engine(self.plan, flat)
+        # opt-in, not a key of the default tree (like SVIT.CONSISTENCY's reader): bit-reproducible weight gradients
+        self.engine.reproducible = bool(getattr(self.cfg.SVIT, "REPRODUCIBLE", False))
         self._grad_views = None
         self._anchor = torch.zeros((), device=dev, requires_grad=True)
         return self

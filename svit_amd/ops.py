@@ -132,6 +132,78 @@ def gemm_tn_grouped(problems, ordered=False):
         hip.call("svit_gemm_tn_grouped", arr, n, meta=("flop", flop))
 
 
+def _tn_problem_array(problems):
+    n = len(problems)
+    arr = (hip.TnProblem * n)()
+    flop = 0.0
+    for i, (a, b, dw, dbias) in enumerate(problems):
+        _chk_rows(a, b, dw)          # (dw too may be the leading columns of wider rows: lddw = its row stride)
+        _chk_dev(dbias)
+        M, N = a.shape
+        K = dw.shape[1]
+        assert b.shape[0] == M and b.shape[1] >= K and dw.shape[0] == N and dw.dtype == F32
+        t = arr[i]
+        t.A, t.B, t.dW, t.dbias = ptr(a), ptr(b), ptr(dw), ptr(dbias)
+        t.lda, t.ldb, t.lddw, t.M, t.N, t.K = a.stride(0), b.stride(0), dw.stride(0), M, N, K
+        flop += 2.0 * M * N * K
+    return arr, flop
+
+
+_tn_slab_need = {}      # shape set -> floats of slab workspace (the planner is a pure function of the shapes)
+_tn_slab_ws = {}        # (device, tag) -> grow-only workspace
+
+
+def gemm_tn_slab_workspace(arr, n, fresh=False):
+    """floats of workspace svit_gemm_tn_grouped_slab needs for these problems (cached per shape set; fresh: ask again)"""
+    key = tuple((t.M, t.N, t.K, t.dbias is not None) for t in arr)
+    need = None if fresh else _tn_slab_need.get(key)
+    if need is None:
+        need = hip.load().svit_gemm_tn_grouped_workspace(arr, n)
+        if need < 0:
+            hip.check(need, "svit_gemm_tn_grouped_workspace")
+        _tn_slab_need[key] = need
+    return need
+
+
+def _tn_slab_buffer(dev, tag, need):
+    key = (dev.index, tag)
+    ws = _tn_slab_ws.get(key)
+    if ws is None or ws.numel() < need:
+        if ws is not None:
+            torch.cuda.synchronize(dev)      # launches still reading the buffer that is being replaced
+        ws = _tn_slab_ws[key] = torch.empty(max(need, 1), device=dev, dtype=F32)
+    return ws
+
+
+def gemm_tn_grouped_slab(problems, ws=None, tag="tn_slab"):
+    """gemm_tn_grouped without atomics: every row split stores its tile into a slab of `ws` and a second launch sums
+    the slabs in split order -- for fixed shapes the result depends only on the operands (bit-reproducible run to run).
+    ws=None: one grow-only buffer per (device, tag), sized on first use (so a captured step allocates nothing once its
+    warm-up has run).  All slab calls that share a buffer must be on one stream: work on another stream names its own
+    `tag`."""
+    n = len(problems)
+    if n == 0:
+        return
+    arr, flop = _tn_problem_array(problems)
+    if ws is not None:
+        _chk_dev(ws)
+        assert ws.dtype == F32
+        hip.call("svit_gemm_tn_grouped_slab", arr, n, ptr(ws), ws.numel(), meta=("flop", flop))
+        return
+    dev = problems[0][2].device
+    ws = _tn_slab_buffer(dev, tag, gemm_tn_slab_workspace(arr, n))
+    try:
+        hip.call("svit_gemm_tn_grouped_slab", arr, n, ptr(ws), ws.numel(), meta=("flop", flop))
+    except hip.SvitHipError:
+        # refused before any launch.  A cached size goes stale when a tool turns the planner's knobs
+        # (svit_debug_set_tn*): ask again, and only a size that really grew earns a second call
+        need = gemm_tn_slab_workspace(arr, n, fresh=True)
+        if need <= ws.numel():
+            raise
+        ws = _tn_slab_buffer(dev, tag, need)
+        hip.call("svit_gemm_tn_grouped_slab", arr, n, ptr(ws), ws.numel(), meta=("flop", flop))
+
+
 def reduce_defer(on):
     """queue (1) / run (0) the second-stage reduce launches of the backward kernels"""
     hip.call("svit_reduce_defer", int(on))
@@ -635,9 +707,10 @@ def head_fwd(tokens, T, O, keep, head_params):
     return outs
 
 
-def head_bwd(tokens, T, O, keep, head_params, boxes, grads_out, param_grads):
+def head_bwd(tokens, T, O, keep, head_params, boxes, grads_out, param_grads, ordered=False):
     """-> d(tokens) f32 [B,N,C] (zero rows for the patch tokens); the parameter gradients are ADDED into
-    param_grads (same nesting as head_params).  grads_out = (dlogits, dboxes, dcontact, dxobj), None allowed."""
+    param_grads (same nesting as head_params).  grads_out = (dlogits, dboxes, dcontact, dxobj), None allowed.
+    ordered: the box / contact gradients are summed over the object rows in a fixed order (no atomics)."""
     assert tokens.is_contiguous() and tokens.dtype == F32
     go = [None if t is None else t.contiguous() for t in grads_out]
     _chk_dev(tokens, keep, boxes, *[t for t in go if t is not None])
@@ -650,6 +723,7 @@ def head_bwd(tokens, T, O, keep, head_params, boxes, grads_out, param_grads):
     (gwp, gbp), (gwb, gbb), (gwe, gbe), (gwc, gbc) = param_grads
     g.gw_proj, g.gb_proj, g.gw_box, g.gb_box = ptr(gwp), ptr(gbp), ptr(gwb), ptr(gbb)
     g.gw_bce, g.gb_bce, g.gw_con, g.gb_con = ptr(gwe), ptr(gbe), ptr(gwc), ptr(gbc)
+    g.ordered = int(ordered)
     hip.call("svit_head_bwd", C.byref(g))
     return dtok
 
