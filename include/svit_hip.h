@@ -176,6 +176,25 @@ int svit_im2col_patch(const float* video, void* cols, int B, int T, int H, int W
 int svit_im2col_patch_u8(const uint8_t* frames, int64_t frames_bytes, const void* lut,
                          const int32_t* crops, void* cols, int B, int T, int Hs, int Ws, int S,
                          void* stream);
+/* Mixup / CutMix of a batch (cfg.MIXUP; slowfast/datasets/mixup.py, tools/train_net.py:63-71,92-94).  All three
+ * entry points of the feature read ONE 32-byte record `mix` from DEVICE memory, so a captured step holds the same
+ * launches for every draw:
+ *   word [0] int32 mode: 0 none, 1 mixup, 2 CutMix        [1] float lam        [2] float oml = (float)(1.0 - lam), the
+ *   subtraction in double (what torch does with the Python scalar; NOT 1 - (float)lam)      [3..6] int32 yl, yh, xl, xh
+ *   [7] 0.        For CutMix `lam` is the area-corrected value and only the soft target uses it.
+ * svit_mixup_clips: x f32 contiguous [B, planes, H, W] (planes = 3*T of a [B,3,T,H,W] batch), IN PLACE; clip b is paired
+ * with clip B-1-b.  mixup: x[b] = x[b]*lam + x[B-1-b]*oml, products and sum each rounded to nearest (no fma), bit-equal to
+ * torch's mul_/add_ sequence; for odd B the middle clip blends with itself through the same formula.  CutMix: the two
+ * clips are swapped inside [yl,yh) x [xl,xh) of every plane (an empty box is legal).  Mode 0 leaves x bit-unchanged.
+ * float4 accesses when W % 4 == 0 and x is 16-byte aligned, scalar otherwise. */
+int svit_mixup_clips(float* x, const void* mix, int B, int planes, int H, int W, void* stream);
+/* svit_im2col_patch_u8 with the mix applied between the normalisation and the bf16 rounding: lut_f32 f32 [3,256] =
+ * (u/255 - mean[c]) / std[c] unrounded; the partner of clip b is clip B-1-b, read through ITS crop row at the same
+ * (t, y, x) of the crop; values are blended (mode 1) or selected by the box in crop coordinates (mode 2) with the
+ * formulas above and only then rounded to bf16.  Mode 0 gives exactly the bytes of svit_im2col_patch_u8. */
+int svit_im2col_patch_u8_mix(const uint8_t* frames, int64_t frames_bytes, const float* lut_f32,
+                             const int32_t* crops, const void* mix, void* cols, int B, int T, int Hs,
+                             int Ws, int S, void* stream);
 /* cls / object token rows of the block-0 input (video_model_builder.py:326-363). */
 int svit_fill_special_tokens(float* x, const float* cls, const float* objq, const float* pos_t,
                              int B, int N, int L, int Tx, int O, int C, int add_pos, void* stream);
@@ -460,6 +479,19 @@ int svit_haog_loss_bwd(const float* upstream, const float* g_l1, const float* g_
  * backward kernels.  logits f32 [B,C], labels int64 [B] (-100 = ignored row, as torch's default ignore_index; any other
  * label outside [0,C) makes the loss NaN); loss f32 [1] = mean over the counted rows, dlogits f32 [B,C] = d loss / d logits. */
 int svit_ce_loss(const float* logits, const int64_t* labels, int B, int C, float* loss, float* dlogits, void* stream);
+/* Cross entropy against a soft target and its unit gradient in one launch (cfg.MIXUP: the reference hands
+ * nn.CrossEntropyLoss the float [B,C] target of mixup.py::mixup_target).  One workgroup, a wave per row, row losses added
+ * in row order, no atomics.  Exactly one of `target` / `labels` is given:
+ *   dense: target f32 [B,C] (mix must be NULL);
+ *   fused: labels int64 [B]; t[b,c] = v1*lam + v2*oml (each product and the sum rounded to nearest, as torch does) with
+ *          v1 = (c == labels[b]) ? on : off, v2 the same for labels[B-1-b], lam / oml from the record `mix` (see
+ *          svit_mixup_clips; NULL: lam = 1, oml = 0).  on / off are the smoothed one-hot values (off = s/C, on = 1 - s + off,
+ *          computed in double and cast by the caller).  The target is never stored.
+ * loss f32 [1] = (1/B) sum_b sum_c t (logsumexp(x_b) - x_bc); dlogits f32 [B,C] = (softmax(x_b) * sum_c t_bc - t_bc) / B
+ * (what autograd of F.cross_entropy gives for probability targets, also when they do not sum to 1).  No ignore index; a
+ * label outside [0,C) makes the loss NaN. */
+int svit_ce_loss_soft(const float* logits, const float* target, const int64_t* labels, const void* mix, float on,
+                      float off, int B, int C, float* loss, float* dlogits, void* stream);
 /* The step's random draws in one launch (round 6; replaces torch.rand + add + floor + div of DropPath,
  * slowfast/models/common.py:46-59, and the head's nn.Dropout mask): scales f32 [n_blocks, per_block] =
  * floor(keep[b] + U) / keep[b], drop f32 [n_drop] in {0, 1/(1-p_drop)}.  Philox-4x32-10 keyed by state[0], draw number

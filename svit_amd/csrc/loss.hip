@@ -268,6 +268,87 @@ extern "C" int svit_ce_loss(const float* logits, const int64_t* labels, int B, i
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// Cross entropy against a SOFT target (cfg.MIXUP: slowfast/datasets/mixup.py::mixup_target feeds nn.CrossEntropyLoss a float
+// [B, C] target, tools/train_net.py:92-94) and its unit gradient in ONE launch, same structure as ce_loss_kernel.
+//   loss = (1/B) sum_b sum_c t[b,c] (logsumexp(x_b) - x[b,c]);   dlogits = (softmax(x_b) * sum_c t[b,c] - t[b,c]) / B
+// (the sum_c t factor is what autograd of F.cross_entropy gives for targets that do not sum to 1; no ignore index).
+// Dense mode reads t; fused mode builds it in registers from the labels, the labels of the batch reversed and the mix
+// record -- t = v1 * lam + v2 * oml with v = (c == y) ? on : off, rounded as torch rounds it -- and never stores it.
+namespace {
+struct SvitMixRec {                       // the record of csrc/input.hip (include/svit_hip.h)
+  int mode;
+  float lam, oml;
+  int yl, yh, xl, xh, pad;
+};
+__device__ __forceinline__ float soft_target(int c, long y1, long y2, float on, float off, float lam, float oml) {
+  float p = __fmul_rn(c == y1 ? on : off, lam), q = __fmul_rn(c == y2 ? on : off, oml);
+  __asm__("" : "+v"(p));              // (-ffast-math would fuse the products into the add: see mix_blend, csrc/input.hip)
+  __asm__("" : "+v"(q));
+  return __fadd_rn(p, q);
+}
+template <bool DENSE>
+__global__ __launch_bounds__(256) void ce_loss_soft_kernel(const float* __restrict__ x, const float* __restrict__ tgt,
+                                                           const int64_t* __restrict__ lab, const SvitMixRec* __restrict__ mix,
+                                                           float on, float off, int B, int C, float* __restrict__ loss,
+                                                           float* __restrict__ dx) {
+  extern __shared__ float ces_rows[];     // [B] row losses
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const float lam = (!DENSE && mix) ? mix->lam : 1.f, oml = (!DENSE && mix) ? mix->oml : 0.f;
+  const float inv = 1.f / (float)B;
+  for (int r = wave; r < B; r += 4) {
+    const float* xr = x + (size_t)r * C;
+    const float* tr = DENSE ? tgt + (size_t)r * C : nullptr;
+    const long y1 = DENSE ? 0 : lab[r], y2 = DENSE ? 0 : lab[B - 1 - r];
+    const bool bad = !DENSE && (y1 < 0 || y1 >= C || y2 < 0 || y2 >= C);
+    float m = -INFINITY;
+    for (int c = lane; c < C; c += 64) m = fmaxf(m, xr[c]);
+    m = wave_max(m);
+    float s = 0.f;
+    for (int c = lane; c < C; c += 64) s += __expf(xr[c] - m);
+    s = wave_sum(s);
+    const float lse = m + __logf(s);
+    float ts = 0.f, l = 0.f;
+    for (int c = lane; c < C; c += 64) {
+      const float t = DENSE ? tr[c] : soft_target(c, y1, y2, on, off, lam, oml);
+      ts += t;
+      l += t * (lse - xr[c]);
+    }
+    ts = wave_sum(ts);
+    l = wave_sum(l);
+    if (lane == 0) ces_rows[r] = bad ? __builtin_nanf("") : l;
+    const float is = ts * inv / s;
+    for (int c = lane; c < C; c += 64) {
+      const float t = DENSE ? tr[c] : soft_target(c, y1, y2, on, off, lam, oml);
+      dx[(size_t)r * C + c] = __expf(xr[c] - m) * is - t * inv;
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float t = 0.f;
+    for (int r = 0; r < B; ++r) t += ces_rows[r];   // row order: the same bits every run
+    *loss = t * inv;
+  }
+}
+}  // namespace
+
+extern "C" int svit_ce_loss_soft(const float* logits, const float* target, const int64_t* labels, const void* mix, float on,
+                                 float off, int B, int C, float* loss, float* dlogits, void* stream) {
+  if (!logits || !loss || !dlogits) return SVIT_ERR_ARG;
+  if ((target != nullptr) == (labels != nullptr)) return SVIT_ERR_ARG;      // exactly one of dense / fused
+  if (target && mix) return SVIT_ERR_ARG;                                   // (a dense target is already mixed)
+  if (B <= 0 || C <= 0 || B > 8192) return SVIT_ERR_SHAPE;
+  if ((uintptr_t)mix & 3) return SVIT_ERR_ALIGN;
+  if (target)
+    hipLaunchKernelGGL(ce_loss_soft_kernel<true>, dim3(1), dim3(256), (size_t)B * sizeof(float), (hipStream_t)stream, logits,
+                       target, labels, (const SvitMixRec*)mix, on, off, B, C, loss, dlogits);
+  else
+    hipLaunchKernelGGL(ce_loss_soft_kernel<false>, dim3(1), dim3(256), (size_t)B * sizeof(float), (hipStream_t)stream, logits,
+                       target, labels, (const SvitMixRec*)mix, on, off, B, C, loss, dlogits);
+  SVIT_LAUNCH_CHECK();
+  return SVIT_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // The step's random draws in ONE launch (round 6): the stochastic-depth factors of every block, floor(keep_b + U) / keep_b per
 // (block, branch, sample) (slowfast/models/common.py:46-59), and the head's dropout factors, {0, 1 / (1 - p)} per element
 // (nn.Dropout, slowfast/models/head_helper / video_model_builder.py head) -- five stock launches before (rand, add, floor,

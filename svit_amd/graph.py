@@ -27,18 +27,26 @@ import warnings
 
 import torch
 
-from . import hip
+from . import hip, ops
 
 
 class GraphedTrainStep:
-    def __init__(self, model, loss_fun, inputs, labels, warmup=2, frames_pass=False):
+    def __init__(self, model, loss_fun, inputs, labels, warmup=2, frames_pass=False, mixup=None):
         """model: SViT or its DataParallel wrapper (train mode); loss_fun(preds, extra, labels) ->
         scalar; inputs: the reference's `inputs` list ([video f32 [B,3,T,S,S]]); labels: any
         tensor (or tuple/dict of tensors) `loss_fun` takes -- copied into static buffers.
         frames_pass: also run the reference's no-grad single-frame forward of every clip
         (tools/train_net.py:105-110) inside the graph; its outputs reach `loss_fun` as
-        extra["frames_output"] = {"preds", "extra_preds"} (the consistency-loss operand)."""
+        extra["frames_output"] = {"preds", "extra_preds"} (the consistency-loss operand).
+        mixup: a mixup.MixUp (cfg.MIXUP; `mixup.build_mixup(cfg)`) -- the step then OWNS a 32-byte mix record in
+        device memory; the captured body starts with the clip kernel on the static input (or tags a U8Clips, whose
+        im2col mixes) and `loss_fun` receives mixup.MixedLabels over the static labels (int64 [B]) instead of the
+        labels.  Every kernel reads the record at replay time, so one capture serves mixup, CutMix and unmixed
+        steps: `__call__` writes the step's record before the first segment.  The clip is mixed IN PLACE, as the
+        reference mutates its input: a batch handed back in `static_inputs` is mixed where it lies and must be
+        rewritten before the next replay.  The frames pass sees the mixed clip.  None: the same launches as ever."""
         self.frames_pass = frames_pass
+        self.mixup = mixup
         self.wrapper = model
         self.core = model.module if hasattr(model, "module") else model
         if self.core.engine is None:
@@ -50,6 +58,21 @@ class GraphedTrainStep:
                                                            getattr(model, "force_collectives", False)) else None
         self.x = inputs[0].detach().clone().contiguous()
         self.labels = _tree_map(lambda t: t.detach().clone(), labels)
+        self.mix_record = self.loss_labels = None
+        if mixup is not None:
+            from .mixup import NO_MIX
+            if not torch.is_tensor(self.labels) or self.labels.dtype != torch.int64 or self.labels.dim() != 1:
+                raise hip.SvitHipError("GraphedTrainStep(mixup=...) needs int64 [B] labels")
+            if self.x.shape[0] < 2:
+                raise hip.SvitHipError("mixup needs a batch of at least 2 clips")
+            # "no mix" while the body runs for warm-up and capture: those launches leave the static input as it is
+            self.mix_record = torch.from_numpy(NO_MIX.pack()).to(self.x.device)
+            self.loss_labels = mixup.labels(self.labels, self.mix_record)
+            self._mix_slots = torch.empty((16, 8), dtype=torch.int32).pin_memory()
+            self._mix_events, self._mix_next = [None] * 16, 0
+            if not torch.is_tensor(self.x):
+                self.x.lut_f32                # (U8Clips: the fp32 table is built here, outside the capture)
+                self.x.mix = self.mix_record
         self.segments = []          # replay items: ("graph", CUDAGraph) | ("side", fn) | ("join", None) | ("ready", ranks)
         self.loss = self.preds = self.extra = None
         self._keepalive = None
@@ -61,6 +84,11 @@ class GraphedTrainStep:
         eng, flat = core.engine, core.flat
         x = self.x
         Tx = x.shape[2] if x.dim() == 5 else 1
+        labels = self.labels
+        if self.mixup is not None:
+            labels = self.loss_labels
+            if torch.is_tensor(x):
+                ops.mixup_clips(x, self.mix_record)      # in place; a U8Clips is mixed by its im2col instead
         eng.refresh_weights()
         flat.grad.zero_()
         ds = core.sample_drop_scales(x.shape[0], x.device, Tx=Tx)      # (+ the head's dropout factors: one launch)
@@ -87,7 +115,7 @@ class GraphedTrainStep:
                 if frames_out is not None:
                     extra = dict(extra)
                     extra["frames_output"] = frames_out
-                loss = self.loss_fun(preds, extra, self.labels)
+                loss = self.loss_fun(preds, extra, labels)
             dy, = torch.autograd.grad(loss, [yt])
             feat = yt
         else:
@@ -102,7 +130,7 @@ class GraphedTrainStep:
                 if frames_out is not None:
                     extra = dict(extra)
                     extra["frames_output"] = frames_out
-                loss = self.loss_fun(preds, extra, self.labels)
+                loss = self.loss_fun(preds, extra, labels)
             grads = torch.autograd.grad(loss, [feat] + [alias[n] for n, _ in named], allow_unused=True)
             with torch.no_grad():
                 for (n, p), g in zip(named, grads[1:]):
@@ -179,7 +207,9 @@ class GraphedTrainStep:
         self._side = torch.cuda.Stream(device=dev)
 
     # ------------------------------------------------------------------------------------------
-    def __call__(self, inputs, labels):
+    def __call__(self, inputs, labels, mix=None):
+        """mix: this step's mixup.MixRecord (mixup steps only; drawn from np.random when None, as the reference's
+        MixUp call would)."""
         x = inputs[0]
         if x.shape != self.x.shape:
             raise hip.SvitHipError("GraphedTrainStep was captured for input %s, got %s"
@@ -187,6 +217,21 @@ class GraphedTrainStep:
         if x.data_ptr() != self.x.data_ptr():
             self.x.copy_(x, non_blocking=True)
         _tree_copy(self.labels, labels)
+        if self.mixup is not None:
+            rec = self.mixup.draw(self.x.shape) if mix is None else mix
+            # 32 bytes, in stream order before the first segment, without stalling the host: a ring of pinned slots,
+            # each guarded by the event of the copy that last read it
+            i = self._mix_next
+            self._mix_next = (i + 1) % len(self._mix_events)
+            if self._mix_events[i] is not None:
+                self._mix_events[i].synchronize()
+            self._mix_slots[i].copy_(torch.from_numpy(rec.pack()))
+            self.mix_record.copy_(self._mix_slots[i], non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(torch.cuda.current_stream(self.x.device))
+            self._mix_events[i] = ev
+        elif mix is not None:
+            raise hip.SvitHipError("a mix record was passed to a GraphedTrainStep built without mixup")
         main = torch.cuda.current_stream(self.x.device)
         for kind, val in self.segments:
             if kind == "graph":

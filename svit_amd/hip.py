@@ -144,6 +144,8 @@ _SIGS = {
                                  i64, vp]),
     "svit_im2col_patch": (i32, [vp, vp, i32, i32, i32, i32, vp]),
     "svit_im2col_patch_u8": (i32, [vp, i64, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
+    "svit_im2col_patch_u8_mix": (i32, [vp, i64, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
+    "svit_mixup_clips": (i32, [vp, vp, i32, i32, i32, i32, vp]),
     "svit_fill_special_tokens": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
     "svit_special_token_grads": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
     "svit_pool_ln_fwd": (i32, [C.POINTER(PoolArgs), vp]),
@@ -171,6 +173,7 @@ _SIGS = {
     "svit_haog_loss": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp]),
     "svit_haog_loss_bwd": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, vp]),
     "svit_ce_loss": (i32, [vp, vp, i32, i32, vp, vp, vp]),
+    "svit_ce_loss_soft": (i32, [vp, vp, vp, vp, f32, f32, i32, i32, vp, vp, vp]),
     "svit_step_draws": (i32, [vp, vp, i32, i32, vp, i32, C.c_float, vp, vp]),
     "svit_ensemble_update": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
     "svit_topk_correct": (i32, [vp, vp, i32, i32, vp, i32, vp, vp, vp]),

@@ -22,12 +22,21 @@ def normalize_lut(mean, std, device):
     return t.to(torch.bfloat16).contiguous().to(device)
 
 
+def normalize_lut_f32(mean, std, device):
+    """f32 [3,256]: the same table before the bf16 rounding (same operations in the same order) -- what the
+    mixup route blends (`svit_im2col_patch_u8_mix`: normalise, mix in fp32, round once)."""
+    t = torch.arange(256, dtype=torch.float32) / 255.0
+    t = t[None, :] - torch.tensor(list(mean), dtype=torch.float32)[:, None]
+    t = t / torch.tensor(list(std), dtype=torch.float32)[:, None]
+    return t.contiguous().to(device)
+
+
 class U8Clips:
     """B clips cut from V uint8 videos.  Quacks like the fp32 clip tensor where the model and
     GraphedTrainStep look at it (`shape`, `dim()`, `device`, `detach/clone/contiguous/copy_`)."""
 
     def __init__(self, frames, size, crops=None, mean=(0.45, 0.45, 0.45), std=(0.225, 0.225, 0.225),
-                 lut=None):
+                 lut=None, lut_f32=None):
         if frames.dtype != torch.uint8 or frames.dim() != 5 or frames.shape[-1] != 3:
             raise ValueError("frames must be uint8 [V,T,H,W,3], got %s %s" % (frames.dtype, tuple(frames.shape)))
         if not frames.is_cuda:
@@ -51,6 +60,22 @@ class U8Clips:
             raise ValueError("crop table outside the frames")
         self.crops = crops.to(frames.device).contiguous()
         self.lut = normalize_lut(mean, std, frames.device) if lut is None else lut
+        self.mean, self.std = tuple(mean), tuple(std)
+        self._lut_f32 = lut_f32
+        # cfg.MIXUP: the device mix record (svit_amd/mixup.py) -- set by MixUp.mix / GraphedTrainStep, routes
+        # ops.im2col_patch_u8 to svit_im2col_patch_u8_mix; None = the plain kernel
+        self.mix = None
+
+    @property
+    def lut_f32(self):
+        """the fp32 table of the mixup route (built on first use; shared by clones)"""
+        if self._lut_f32 is None:
+            if self.lut is not None and not torch.equal(
+                    self.lut, normalize_lut(self.mean, self.std, self.frames.device)):
+                raise ValueError("U8Clips was given a bf16 table that is not normalize_lut(mean, std): "
+                                 "pass the matching lut_f32 for the mixup route")
+            self._lut_f32 = normalize_lut_f32(self.mean, self.std, self.frames.device)
+        return self._lut_f32
 
     # ---- the parts of the tensor interface the model path touches ---------------------------
     @property
@@ -74,7 +99,8 @@ class U8Clips:
         return self
 
     def clone(self):
-        return U8Clips(self.frames.clone(), self.size, self.crops.clone(), lut=self.lut)
+        return U8Clips(self.frames.clone(), self.size, self.crops.clone(), mean=self.mean, std=self.std,
+                       lut=self.lut, lut_f32=self._lut_f32)
 
     def copy_(self, other, non_blocking=False):
         self.frames.copy_(other.frames, non_blocking=non_blocking)

@@ -97,10 +97,43 @@ class _CrossEntropyHip(torch.autograd.Function):
         return dlogits * d_loss, None
 
 
+class _SoftCrossEntropyHip(torch.autograd.Function):
+    """Cross entropy against a soft target, forward + unit gradient in one launch (svit_ce_loss_soft, include/svit_hip.h):
+    `target` f32 [B,C] (dense), or None with `mixed` = mixup.MixedLabels -- the target of cfg.MIXUP is then built in
+    registers from the labels and the device mix record and never stored."""
+
+    @staticmethod
+    def forward(ctx, logits, target, mixed):
+        from . import ops
+        if mixed is None:
+            loss, dlogits = ops.ce_loss_soft(logits.contiguous(), target=target.contiguous())
+        else:
+            if mixed.num_classes != logits.shape[1]:
+                raise ValueError("MixedLabels built for %d classes, logits have %d" % (mixed.num_classes, logits.shape[1]))
+            loss, dlogits = ops.ce_loss_soft(logits.contiguous(), labels=mixed.labels.contiguous(), mix=mixed.record,
+                                             on=mixed.on, off=mixed.off)
+        ctx.save_for_backward(dlogits)
+        return loss
+
+    @staticmethod
+    def backward(ctx, d_loss):
+        (dlogits,) = ctx.saved_tensors
+        return dlogits * d_loss, None, None
+
+
 def cross_entropy(logits, labels):
-    """F.cross_entropy(logits, labels) (mean, ignore_index -100) -- the fused launch for fp32 logits on the GPU."""
-    if logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 2 and labels.dtype == torch.int64:
+    """F.cross_entropy(logits, labels), reduction "mean" -- one fused launch for fp32 logits on the GPU.  `labels`: int64 [B]
+    (ignore_index -100), a float [B,C] probability target, or mixup.MixedLabels (cfg.MIXUP's target, never materialised)."""
+    from .mixup import MixedLabels
+    on_gpu = logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 2
+    if isinstance(labels, MixedLabels):
+        if on_gpu:
+            return _SoftCrossEntropyHip.apply(logits, None, labels)
+        return F.cross_entropy(logits, labels.dense())
+    if on_gpu and labels.dtype == torch.int64:
         return _CrossEntropyHip.apply(logits, labels)
+    if on_gpu and labels.dtype == torch.float32 and labels.shape == logits.shape:
+        return _SoftCrossEntropyHip.apply(logits, labels, None)
     return F.cross_entropy(logits, labels)
 
 
@@ -149,12 +182,20 @@ class VideoImageLoss(nn.Module):
 
     def forward(self, x, extra_preds, y, metadata):
         ret = {}
+        from .mixup import MixedLabels
+        soft = isinstance(y, MixedLabels) or (torch.is_tensor(y) and y.is_floating_point())
         if self.is_vid():
-            ret["loss_ce"] = cross_entropy(x, y) if self.reduction == "mean" else self.ce_loss(x, y)
+            if self.reduction == "mean":
+                ret["loss_ce"] = cross_entropy(x, y)      # int64 labels | float [B,C] target | MixedLabels (cfg.MIXUP)
+            else:
+                ret["loss_ce"] = self.ce_loss(x, y.dense() if isinstance(y, MixedLabels) else y)
             if self.cfg.TRAIN.FORWARD_VIDEO_FRAMES and "frames_output" in extra_preds:
                 ret.update(self._consistency_loss(extra_preds,
                                                   extra_preds["frames_output"]["extra_preds"]))
         else:
+            if soft:
+                raise NotImplementedError("mixup / soft targets on an image rank: the HAOG losses have no mixed form "
+                                          "(cfg.MIXUP covers the video ranks' cross entropy only)")
             ret.update(self._haog_loss(extra_preds, metadata))
         return ret
 

@@ -347,9 +347,35 @@ def im2col_patch_u8(clips):
     B, S = clips.crops.shape[0], clips.size
     To, Ho, Wo = (T - 1) // 2 + 1, (S - 1) // 4 + 1, (S - 1) // 4 + 1
     cols = torch.empty((B * To * Ho * Wo, 448), device=fr.device, dtype=BF16)
+    mix = getattr(clips, "mix", None)
+    if mix is not None:     # cfg.MIXUP on the uint8 route: blended / swapped between normalisation and bf16 rounding
+        _chk_mix(mix, fr.device)
+        hip.call("svit_im2col_patch_u8_mix", ptr(fr), fr.numel(), ptr(clips.lut_f32), ptr(clips.crops), ptr(mix),
+                 ptr(cols), B, T, Hs, Ws, S)
+        return cols, (To, Ho, Wo)
     hip.call("svit_im2col_patch_u8", ptr(fr), fr.numel(), ptr(clips.lut), ptr(clips.crops),
              ptr(cols), B, T, Hs, Ws, S)
     return cols, (To, Ho, Wo)
+
+
+def _chk_mix(mix, device):
+    """the 32-byte mix record (include/svit_hip.h, svit_mixup_clips): int32 [8] on the device of the data"""
+    _chk_dev(mix)
+    if mix.dtype != torch.int32 or mix.numel() != 8 or mix.device != device:
+        raise hip.SvitHipError("the mix record must be int32 [8] on %s (got %s %s on %s)"
+                               % (device, mix.dtype, tuple(mix.shape), mix.device))
+
+
+def mixup_clips(x, mix):
+    """x f32 contiguous [B, ..., H, W] mixed IN PLACE against the batch reversed, as the device record `mix` says
+    (svit_mixup_clips: mixup blend, CutMix box swap, or nothing)."""
+    _chk_dev(x)
+    _chk_mix(mix, x.device)
+    if x.dtype != F32 or x.dim() < 3:
+        raise hip.SvitHipError("mixup_clips needs an fp32 [B, ..., H, W] tensor, got %s %s" % (x.dtype, tuple(x.shape)))
+    B, H, W = x.shape[0], x.shape[-2], x.shape[-1]
+    hip.call("svit_mixup_clips", ptr(x), ptr(mix), B, x[0].numel() // (H * W), H, W)
+    return x
 
 
 def fill_special_tokens(x, cls, objq, pos_t, L, Tx, O, add_pos):
@@ -761,6 +787,28 @@ def ce_loss(logits, labels):
     loss = torch.empty((), device=logits.device, dtype=F32)
     dlogits = torch.empty_like(logits)
     hip.call("svit_ce_loss", ptr(logits), ptr(labels), logits.shape[0], logits.shape[1], ptr(loss), ptr(dlogits))
+    return loss, dlogits
+
+
+def ce_loss_soft(logits, target=None, labels=None, mix=None, on=1.0, off=0.0):
+    """cross entropy against a soft target and d loss / d logits in one launch (svit_ce_loss_soft).  Either `target` f32 [B,C]
+    (dense) or `labels` int64 [B] (+ the device mix record, + the smoothed one-hot values on / off): the target of
+    mixup.MixUp is then built in registers, t = v(labels) * lam + v(labels reversed) * (1 - lam)."""
+    _chk_dev(logits, target, labels)
+    assert logits.dtype == F32 and logits.dim() == 2
+    B, C_ = logits.shape
+    if (target is None) == (labels is None):
+        raise hip.SvitHipError("ce_loss_soft takes a dense target or labels, not both / neither")
+    if target is not None:
+        assert target.dtype == F32 and target.shape == logits.shape and mix is None
+    else:
+        assert labels.dtype == torch.int64 and labels.numel() == B
+        if mix is not None:
+            _chk_mix(mix, logits.device)
+    loss = torch.empty((), device=logits.device, dtype=F32)
+    dlogits = torch.empty_like(logits)
+    hip.call("svit_ce_loss_soft", ptr(logits), ptr(target), ptr(labels), ptr(mix), float(on), float(off), B, C_,
+             ptr(loss), ptr(dlogits))
     return loss, dlogits
 
 
