@@ -426,6 +426,72 @@ int svit_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, con
                     float max_norm, float lr, float beta1, float beta2, float eps, float wd,
                     int step, float grad_scale, void* stream);
 
+/* Guarded optimiser tail: the same clip + AdamW, but a step whose gradients hold an inf or a NaN is DROPPED on the
+ * device, as GradScaler.step drops it (tools/train_net.py:134-151): weights, moments and AdamW's step counter stay as
+ * they were.  Every scalar of the step lives in a step record in device memory, so the launches below are the same for
+ * every step and can sit inside a captured graph.  The record has two parts in two SEPARATE buffers, so that an upload
+ * never overwrites what the device owns.
+ *
+ * svit_step_host (32 bytes, 8-byte aligned): written by the host before every step, only read by kernels.
+ *   offset  0  float lr[2]            learning rate of [0] the decayed range [0, n_decay), [1] the rest [n_decay, n)
+ *   offset  8  float weight_decay[2]  weight decay of the same two groups
+ *   offset 16  float max_norm         clip_grad_norm_ bound; <= 0: no norm clipping
+ *   offset 20  float clip_value       clip_grad_value_ bound; > 0: g * grad_scale is clamped to +-clip_value element by
+ *                                     element and norm clipping is OFF (the reference's precedence, train_net.py:139-147)
+ *   offset 24  float grad_scale       factor applied to every gradient (1 / loss scale)
+ *   offset 28  float reserved         0
+ * svit_step_dev (48 bytes, 8-byte aligned): written only by kernels (the host zeroes it once, and may set `applied`
+ * when it loads a checkpoint).
+ *   offset  0  int64 applied          steps applied so far = AdamW's step counter
+ *   offset  8  int64 skipped          steps dropped so far
+ *   offset 16  int32 consecutive      steps dropped in a row, 0 after every applied step
+ *   offset 20  int32 apply            this step: 1 applied, 0 dropped
+ *   offset 24  float coef             this step's gradient coefficient (clip coefficient * grad_scale)
+ *   offset 28  float bc1              this step's 1 - beta1^applied
+ *   offset 32  float bc2_sqrt         this step's sqrt(1 - beta2^applied)
+ *   offset 36  float sumsq            sum(g^2) of the last applied step
+ *   offset 40  float grad_norm        sqrt(sumsq) * grad_scale of the last applied step: the last finite gradient norm
+ *   offset 44  float reserved
+ * A dropped step changes `skipped`, `consecutive` and `apply` and nothing else. */
+typedef struct {
+  float lr[2], weight_decay[2];
+  float max_norm, clip_value, grad_scale, reserved;
+} svit_step_host;
+typedef struct {
+  int64_t applied, skipped;
+  int32_t consecutive, apply;
+  float coef, bc1, bc2_sqrt, sumsq, grad_norm, reserved;
+} svit_step_dev;
+
+/* HOST ONLY (no stream, no launch): the bias corrections svit_adamw_step derives from its `step` argument, by the very
+ * same host code: pair k-1 = (1 - powf(beta1, k), sqrtf(1 - powf(beta2, k))) for steps k = 1, 2, ... up to and including
+ * the first step at which both values are exactly 1.0f; past the table both are 1.0f.  *n_entries receives that length
+ * (17321 pairs for betas (0.9, 0.999)).  table (2 floats per pair, room for `capacity` pairs) may be NULL to ask for the
+ * length alone.  SVIT_ERR_ARG: n_entries NULL, a table shorter than the length, or a length above 2^20 (betas that
+ * never reach 1.0f, or not below 1, included).  The device never calls pow: the guard looks the pair up. */
+int svit_adamw_bias_table(float beta1, float beta2, float* table, int64_t capacity, int64_t* n_entries);
+
+/* The guard: svit_sumsq's two-stage deterministic sum of squares (same kernel, same partial layout through `workspace`,
+ * >= 1 float, 1024 for the full grid) whose final one-wave stage also takes the step's decision:
+ *   total = sqrtf(sumsq) * grad_scale;  apply = isfinite(total)
+ *   apply: applied += 1, consecutive = 0, coef = svit_adamw_step's coefficient (grad_scale * min(max_norm / (total + 1e-6),
+ *          1) when max_norm > 0 and clip_value <= 0, grad_scale otherwise), (bc1, bc2_sqrt) = pair `applied` of
+ *          bias_table (1.0f past its `table_entries` pairs), sumsq and grad_norm recorded;
+ *   drop:  skipped += 1, consecutive += 1.
+ * A step of finite gradients whose sum of squares overflows fp32 (a norm above ~1.8e19) counts as non-finite and is
+ * dropped.  The guard runs with norm clipping off too: it is what detects the non-finite step.  Two launches, no
+ * allocation, copy or synchronisation: capturable.  records not 8-byte aligned: SVIT_ERR_ALIGN. */
+int svit_step_guard(const float* g, int64_t n, const svit_step_host* host_rec, svit_step_dev* dev_rec,
+                    const float* bias_table, int64_t table_entries, float* workspace, int64_t workspace_floats,
+                    void* stream);
+/* svit_adamw_step's arithmetic in the same order on p, g, m, v f32 [n] (16-byte aligned, else SVIT_ERR_ALIGN), every
+ * scalar read from the step record the guard left: ONE launch for both weight-decay groups ([0, n_decay) takes lr[0] /
+ * weight_decay[0], [n_decay, n) takes [1]; 0 <= n_decay <= n), 16-byte accesses with a scalar tail for n % 4.  On a
+ * dropped step (apply == 0) every workgroup returns before its first load of p, g, m or v. */
+int svit_adamw_step_guarded(float* p, const float* g, float* m, float* v, int64_t n, int64_t n_decay,
+                            const svit_step_host* host_rec, const svit_step_dev* dev_rec, float beta1, float beta2,
+                            float eps, void* stream);
+
 /* ------------------------------------------------------------------ head (K15) ---------- */
 /* SViT head (slowfast/models/video_model_builder.py:408-551) in one launch each way, fp32: dropout factors
  * applied to the cls / object rows of the final norm's output, class logits from the cls row, box MLP +

@@ -482,6 +482,102 @@ __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
   }
 }
 
+// ---- guarded optimiser tail (include/svit_hip.h: svit_step_host / svit_step_dev) ------------
+// sumsq_final_kernel that also takes the step's decision: no launch of its own for it.  A dropped step touches
+// `skipped`, `consecutive` and `apply` only.
+__global__ void step_guard_final_kernel(const float* __restrict__ partial, int nblocks,
+                                        const svit_step_host* __restrict__ h, svit_step_dev* __restrict__ d,
+                                        const float2* __restrict__ table, int64_t entries) {
+  float s = 0.f;
+  for (int i = threadIdx.x; i < nblocks; i += 64) s += partial[i];
+  s = wave_sum(s);
+  if (threadIdx.x != 0) return;
+  const float max_norm = h->max_norm, grad_scale = h->grad_scale;
+  const float total = sqrtf(s) * grad_scale;
+  // inf / NaN by the exponent bits (the build is -ffast-math: no reliance on what it makes of isfinite)
+  if ((__float_as_uint(total) & 0x7f800000u) != 0x7f800000u) {
+    const int64_t step = d->applied + 1;
+    float coef = grad_scale;
+    // adamw_kernel's coefficient as the build compiles it there: `total + 1e-6f` is ONE fused multiply-add of the square
+    // root and grad_scale (total itself has another use here, which would keep the compiler from contracting it)
+    if (max_norm > 0.f && !(h->clip_value > 0.f))
+      coef *= fminf(max_norm / __builtin_fmaf(sqrtf(s), grad_scale, 1e-6f), 1.0f);
+    float2 bc = make_float2(1.f, 1.f);
+    if (step >= 1 && step <= entries) bc = table[step - 1];
+    d->applied = step;
+    d->consecutive = 0;
+    d->apply = 1;
+    d->coef = coef;
+    d->bc1 = bc.x;
+    d->bc2_sqrt = bc.y;
+    d->sumsq = s;
+    d->grad_norm = total;
+  } else {
+    d->skipped += 1;
+    d->consecutive += 1;
+    d->apply = 0;
+  }
+}
+
+// adamw_kernel's update of one element, the same expressions in the same order.  CLAMP (clip by value instead of by
+// norm) is a template parameter, not a select: with a select in front of it the compiler no longer folds g * coef into
+// the moment updates the way it does in adamw_kernel, and the results differ in the last bit.
+template <bool CLAMP>
+__device__ __forceinline__ void adamw_guarded_update(float& pw, float gr, float& mo, float& va, float coef, float cv,
+                                                     float lr, float wd, float b1, float b2, float eps, float bc1,
+                                                     float bc2_sqrt) {
+  float gi = gr * coef;
+  if (CLAMP) gi = fminf(fmaxf(gi, -cv), cv);
+  float w = pw * (1.f - lr * wd);
+  const float mi = mo * b1 + gi * (1.f - b1);
+  const float vi = va * b2 + gi * gi * (1.f - b2);
+  const float denom = sqrtf(vi) / bc2_sqrt + eps;
+  w -= (lr / bc1) * (mi / denom);
+  pw = w; mo = mi; va = vi;
+}
+
+template <bool CLAMP>
+__device__ __forceinline__ void adamw_guarded_range(float* __restrict__ p, const float* __restrict__ g,
+                                                    float* __restrict__ m, float* __restrict__ v, int64_t n,
+                                                    int64_t n_decay, const svit_step_host* __restrict__ h, float coef,
+                                                    float bc1, float bc2_sqrt, float b1, float b2, float eps) {
+  const float cv = h->clip_value;
+  const float lr0 = h->lr[0], lr1 = h->lr[1], wd0 = h->weight_decay[0], wd1 = h->weight_decay[1];
+  const int64_t n4 = n >> 2;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < n4; q += stride) {
+    const int64_t i = q * 4;
+    float4 P = ((const float4*)p)[q], M = ((const float4*)m)[q], V = ((const float4*)v)[q];
+    const float4 G = ((const float4*)g)[q];
+    const bool d0 = i < n_decay, d1 = i + 1 < n_decay, d2 = i + 2 < n_decay, d3 = i + 3 < n_decay;
+    adamw_guarded_update<CLAMP>(P.x, G.x, M.x, V.x, coef, cv, d0 ? lr0 : lr1, d0 ? wd0 : wd1, b1, b2, eps, bc1, bc2_sqrt);
+    adamw_guarded_update<CLAMP>(P.y, G.y, M.y, V.y, coef, cv, d1 ? lr0 : lr1, d1 ? wd0 : wd1, b1, b2, eps, bc1, bc2_sqrt);
+    adamw_guarded_update<CLAMP>(P.z, G.z, M.z, V.z, coef, cv, d2 ? lr0 : lr1, d2 ? wd0 : wd1, b1, b2, eps, bc1, bc2_sqrt);
+    adamw_guarded_update<CLAMP>(P.w, G.w, M.w, V.w, coef, cv, d3 ? lr0 : lr1, d3 ? wd0 : wd1, b1, b2, eps, bc1, bc2_sqrt);
+    ((float4*)p)[q] = P; ((float4*)m)[q] = M; ((float4*)v)[q] = V;
+  }
+  const int64_t i = n4 * 4 + threadIdx.x;
+  if (blockIdx.x == 0 && i < n) {
+    const bool dec = i < n_decay;
+    float pw = p[i], mo = m[i], va = v[i];
+    adamw_guarded_update<CLAMP>(pw, g[i], mo, va, coef, cv, dec ? lr0 : lr1, dec ? wd0 : wd1, b1, b2, eps, bc1, bc2_sqrt);
+    p[i] = pw; m[i] = mo; v[i] = va;
+  }
+}
+
+// Both weight-decay groups in one launch, 16-byte accesses (28 B per parameter: the tail of the step is HBM-bound), the
+// n % 4 leftovers by the first lanes of workgroup 0.  A dropped step returns before any load of p, g, m, v.
+__global__ __launch_bounds__(256) void adamw_guarded_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                            float* __restrict__ m, float* __restrict__ v, int64_t n,
+                                                            int64_t n_decay, const svit_step_host* __restrict__ h,
+                                                            const svit_step_dev* __restrict__ d, float b1, float b2,
+                                                            float eps) {
+  if (d->apply == 0) return;
+  const float coef = d->coef, bc1 = d->bc1, bc2_sqrt = d->bc2_sqrt;
+  if (h->clip_value > 0.f) adamw_guarded_range<true>(p, g, m, v, n, n_decay, h, coef, bc1, bc2_sqrt, b1, b2, eps);
+  else adamw_guarded_range<false>(p, g, m, v, n, n_decay, h, coef, bc1, bc2_sqrt, b1, b2, eps);
+}
+
 inline unsigned grid_for(int64_t work_items, int block, unsigned cap = 8192) {
   int64_t b = (work_items + block - 1) / block;
   if (b < 1) b = 1;
@@ -803,16 +899,74 @@ extern "C" int svit_sumsq(const float* g, int64_t n, float* sumsq, float* worksp
   return SVIT_OK;
 }
 
+// AdamW's bias corrections of step `step`, on the HOST (glibc's powf): the one place they are computed -- svit_adamw_step
+// passes them as kernel arguments, svit_adamw_bias_table tabulates them for the guarded tail
+// (precise: under the build's -ffast-math the compiler may turn powf(x, (float)int) into a multiplication chain -- whether
+//  it does depends on the surrounding code, and the chain's values are not powf's)
+static inline void adamw_bias_corrections(float beta1, float beta2, int step, float* bc1, float* bc2_sqrt) {
+#pragma float_control(precise, on)
+  *bc1 = 1.f - powf(beta1, (float)step);
+  *bc2_sqrt = sqrtf(1.f - powf(beta2, (float)step));
+}
+
 extern "C" int svit_adamw_step(float* p, const float* g, float* m, float* v, int64_t n,
                                const float* sumsq, float max_norm, float lr, float beta1,
                                float beta2, float eps, float wd, int step, float grad_scale,
                                void* stream) {
   if (!p || !g || !m || !v || n <= 0 || step < 1) return SVIT_ERR_ARG;
-  const float bc1 = 1.f - powf(beta1, (float)step);
-  const float bc2s = sqrtf(1.f - powf(beta2, (float)step));
+  float bc1, bc2s;
+  adamw_bias_corrections(beta1, beta2, step, &bc1, &bc2s);
   hipLaunchKernelGGL(adamw_kernel, dim3(grid_for(n, 256, 4096)), dim3(256), 0, (hipStream_t)stream,
                      p, g, m, v, n, sumsq, max_norm, lr, beta1, beta2, eps, wd, bc1, bc2s,
                      grad_scale);
+  SVIT_LAUNCH_CHECK();
+  return SVIT_OK;
+}
+
+extern "C" int svit_adamw_bias_table(float beta1, float beta2, float* table, int64_t capacity, int64_t* n_entries) {
+  if (!n_entries || (table && capacity < 0)) return SVIT_ERR_ARG;
+  constexpr int64_t kMax = 1ll << 20;
+  for (int64_t k = 1; k <= kMax; ++k) {
+    float bc1, bc2s;
+    adamw_bias_corrections(beta1, beta2, (int)k, &bc1, &bc2s);
+    if (table) {
+      if (k > capacity) return SVIT_ERR_ARG;
+      table[2 * (k - 1)] = bc1;
+      table[2 * (k - 1) + 1] = bc2s;
+    }
+    if (bc1 == 1.0f && bc2s == 1.0f) {
+      *n_entries = k;
+      return SVIT_OK;
+    }
+  }
+  return SVIT_ERR_ARG;
+}
+
+extern "C" int svit_step_guard(const float* g, int64_t n, const svit_step_host* host_rec, svit_step_dev* dev_rec,
+                               const float* bias_table, int64_t table_entries, float* workspace,
+                               int64_t workspace_floats, void* stream) {
+  if (!g || !host_rec || !dev_rec || !workspace || n <= 0 || table_entries < 0 || (table_entries > 0 && !bias_table))
+    return SVIT_ERR_ARG;
+  if (((uintptr_t)host_rec | (uintptr_t)dev_rec | (uintptr_t)bias_table) & 7) return SVIT_ERR_ALIGN;
+  unsigned blocks = grid_for((n + 3) / 4, 256, 1024);      // svit_sumsq's grid: the same partials, bit for bit
+  if ((int64_t)blocks > workspace_floats) blocks = (unsigned)workspace_floats;
+  if (blocks < 1) return SVIT_ERR_ARG;
+  hipLaunchKernelGGL(sumsq_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, g, n, workspace);
+  SVIT_LAUNCH_CHECK();
+  hipLaunchKernelGGL(step_guard_final_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, workspace, (int)blocks,
+                     host_rec, dev_rec, (const float2*)bias_table, table_entries);
+  SVIT_LAUNCH_CHECK();
+  return SVIT_OK;
+}
+
+extern "C" int svit_adamw_step_guarded(float* p, const float* g, float* m, float* v, int64_t n, int64_t n_decay,
+                                       const svit_step_host* host_rec, const svit_step_dev* dev_rec, float beta1,
+                                       float beta2, float eps, void* stream) {
+  if (!p || !g || !m || !v || !host_rec || !dev_rec || n <= 0 || n_decay < 0 || n_decay > n) return SVIT_ERR_ARG;
+  if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) return SVIT_ERR_ALIGN;
+  if (((uintptr_t)host_rec | (uintptr_t)dev_rec) & 7) return SVIT_ERR_ALIGN;
+  hipLaunchKernelGGL(adamw_guarded_kernel, dim3(grid_for(n >> 2, 256, 4096)), dim3(256), 0, (hipStream_t)stream,
+                     p, g, m, v, n, n_decay, host_rec, dev_rec, beta1, beta2, eps);
   SVIT_LAUNCH_CHECK();
   return SVIT_OK;
 }

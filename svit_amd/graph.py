@@ -10,6 +10,13 @@ static for a fixed input shape, so it is captured ONCE into HIP graphs and repla
         loss, preds = step(inputs, labels)      # static tensors, overwritten by every replay
         optimizer.step()                        # eager (lr / bias correction are host scalars)
 
+or, with the guarded optimizer (optim.GuardedClipAdamW keeps every scalar of its step in device memory), the whole step:
+
+    step = GraphedTrainStep(model, loss_fun, inputs, labels, optimizer=optimizer)
+    for inputs, labels in loader:
+        set_lr(optimizer, lr)                   # reaches the replay: uploaded before the first segment
+        loss, preds = step(inputs, labels)      # ends with the optimizer's launches; do NOT call optimizer.step()
+
 What is inside the graph(s): bf16 weight refresh, grad-buffer memset, DropPath / dropout sampling
 (torch's graph-safe Philox state), every backbone kernel, the head, `loss_fun`, the head's
 autograd backward and the whole backbone backward.  Same arithmetic as the eager step
@@ -31,7 +38,7 @@ from . import hip, ops
 
 
 class GraphedTrainStep:
-    def __init__(self, model, loss_fun, inputs, labels, warmup=2, frames_pass=False, mixup=None):
+    def __init__(self, model, loss_fun, inputs, labels, warmup=2, frames_pass=False, mixup=None, optimizer=None):
         """model: SViT or its DataParallel wrapper (train mode); loss_fun(preds, extra, labels) ->
         scalar; inputs: the reference's `inputs` list ([video f32 [B,3,T,S,S]]); labels: any
         tensor (or tuple/dict of tensors) `loss_fun` takes -- copied into static buffers.
@@ -44,7 +51,23 @@ class GraphedTrainStep:
         labels.  Every kernel reads the record at replay time, so one capture serves mixup, CutMix and unmixed
         steps: `__call__` writes the step's record before the first segment.  The clip is mixed IN PLACE, as the
         reference mutates its input: a batch handed back in `static_inputs` is mixed where it lies and must be
-        rewritten before the next replay.  The frames pass sees the mixed clip.  None: the same launches as ever."""
+        rewritten before the next replay.  The frames pass sees the mixed clip.  None: the same launches as ever.
+        optimizer: an optim.GuardedClipAdamW over this model -- the captured body then ENDS with its launches (guard +
+        AdamW, behind the last weight-gradient join; with data parallelism a last segment of its own, replayed after
+        the final bucket's all-reduce has been waited for) and `__call__` uploads its host record before the first
+        segment: the caller no longer calls `optimizer.step()`.  The warm-up runs of the body leave the tail out, so
+        building the step moves no weight.  None: the same segments as ever."""
+        self.optimizer = optimizer
+        if optimizer is not None:
+            from .optim import GuardedClipAdamW
+            if not isinstance(optimizer, GuardedClipAdamW):
+                raise hip.SvitHipError(
+                    "GraphedTrainStep(optimizer=...) takes an optim.GuardedClipAdamW, got %s: only its step reads every "
+                    "scalar (lr, step counter, bias corrections) from device memory; any other optimizer's step holds "
+                    "host scalars a replay would freeze -- call it eagerly after the replay" % type(optimizer).__name__)
+            core = model.module if hasattr(model, "module") else model
+            if optimizer.flat is not core.flat:
+                raise hip.SvitHipError("GraphedTrainStep(optimizer=...): the optimizer was built over another model")
         self.frames_pass = frames_pass
         self.mixup = mixup
         self.wrapper = model
@@ -79,7 +102,7 @@ class GraphedTrainStep:
         self._capture(warmup)
 
     # ------------------------------------------------------------------------------------------
-    def _body(self, boundary):
+    def _body(self, boundary, tail=False):
         core = self.core
         eng, flat = core.engine, core.flat
         x = self.x
@@ -143,6 +166,10 @@ class GraphedTrainStep:
         with torch.no_grad():
             eng.backward(st, dy, on_ready=boundary,
                          ready_ranks=self.dp.launch_ranks() if self.dp is not None else None)
+            if tail and self.optimizer is not None:
+                # every gradient is final here: backward() ends behind its last flush and join, and with data parallelism
+                # the final rank's boundary has just cut the capture, so these launches open a segment of their own
+                self.optimizer.enqueue()
         return (loss.detach(), preds.detach(),
                 {k: v.detach() for k, v in extra.items() if torch.is_tensor(v)}, (st, feat, dy))
 
@@ -197,7 +224,7 @@ class GraphedTrainStep:
                 begin()
                 try:
                     self.loss, self.preds, self.extra, self._keepalive = self._body(
-                        boundary if self.dp is not None else None)
+                        boundary if self.dp is not None else None, tail=True)
                 finally:
                     end()
         finally:
@@ -232,6 +259,8 @@ class GraphedTrainStep:
             self._mix_events[i] = ev
         elif mix is not None:
             raise hip.SvitHipError("a mix record was passed to a GraphedTrainStep built without mixup")
+        if self.optimizer is not None:
+            self.optimizer.upload()
         main = torch.cuda.current_stream(self.x.device)
         for kind, val in self.segments:
             if kind == "graph":

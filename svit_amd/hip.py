@@ -119,6 +119,18 @@ class HeadBwdArgs(C.Structure):
                 ("gw_con", vp), ("gb_con", vp), ("ordered", i32)]
 
 
+class StepHost(C.Structure):
+    """svit_step_host: the part of the guarded optimiser's step record the host uploads before every step"""
+    _fields_ = [("lr", f32 * 2), ("weight_decay", f32 * 2), ("max_norm", f32), ("clip_value", f32),
+                ("grad_scale", f32), ("reserved", f32)]
+
+
+class StepDev(C.Structure):
+    """svit_step_dev: the part only kernels write"""
+    _fields_ = [("applied", i64), ("skipped", i64), ("consecutive", i32), ("apply", i32), ("coef", f32),
+                ("bc1", f32), ("bc2_sqrt", f32), ("sumsq", f32), ("grad_norm", f32), ("reserved", f32)]
+
+
 _SIGS = {
     "svit_version": (i32, []),
     "svit_arch": (C.c_char_p, []),
@@ -168,6 +180,9 @@ _SIGS = {
     "svit_maxpool_bwd_bf16": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "svit_sumsq": (i32, [vp, i64, vp, vp, i64, vp]),
     "svit_adamw_step": (i32, [vp, vp, vp, vp, i64, vp, f32, f32, f32, f32, f32, f32, i32, f32, vp]),
+    "svit_adamw_bias_table": (i32, [f32, f32, vp, i64, C.POINTER(i64)]),       # host only: no stream argument
+    "svit_step_guard": (i32, [vp, i64, vp, vp, vp, i64, vp, i64, vp]),
+    "svit_adamw_step_guarded": (i32, [vp, vp, vp, vp, i64, i64, vp, vp, f32, f32, f32, vp]),
     "svit_head_fwd": (i32, [C.POINTER(HeadArgs), vp]),
     "svit_head_bwd": (i32, [C.POINTER(HeadBwdArgs), vp]),
     "svit_haog_loss": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp]),

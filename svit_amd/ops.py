@@ -706,6 +706,45 @@ def adamw_step(p, g, m, v, sumsq_t, max_norm, lr, beta1, beta2, eps, wd, step, g
              lr, beta1, beta2, eps, wd, step, grad_scale)
 
 
+def adamw_bias_table(beta1, beta2):
+    """(bc1, bc2_sqrt) of AdamW steps 1, 2, ... as svit_adamw_step computes them on the host, up to the first step at
+    which both are 1.0f: float32 numpy [entries, 2] (svit_adamw_bias_table; host only, needs no device)."""
+    import numpy as np
+    cap = 1 << 20
+    buf = np.empty((cap, 2), dtype=np.float32)
+    n = C.c_int64(0)
+    rc = hip.load().svit_adamw_bias_table(beta1, beta2, buf.ctypes.data, cap, C.byref(n))
+    hip.check(rc, "svit_adamw_bias_table (betas %r, %r)" % (beta1, beta2))
+    return buf[:n.value].copy()
+
+
+def _chk_step_records(host_rec, dev_rec, device):
+    """the two parts of the step record (include/svit_hip.h: svit_step_host 32 bytes, svit_step_dev 48 bytes)"""
+    _chk_dev(host_rec, dev_rec)
+    if (host_rec.dtype != F32 or host_rec.numel() != 8 or dev_rec.dtype != torch.int32 or dev_rec.numel() != 12
+            or host_rec.device != device or dev_rec.device != device):
+        raise hip.SvitHipError("the step record is fp32 [8] + int32 [12] on %s" % (device,))
+
+
+def step_guard(g, host_rec, dev_rec, table, workspace):
+    """sum of squares of g + the decision of the step, written to dev_rec (svit_step_guard); table: fp32 [entries, 2]"""
+    _chk_dev(g, table, workspace)
+    _chk_step_records(host_rec, dev_rec, g.device)
+    hip.call("svit_step_guard", ptr(g), g.numel(), ptr(host_rec), ptr(dev_rec), ptr(table), table.shape[0],
+             ptr(workspace), workspace.numel())
+
+
+def adamw_step_guarded(p, g, m, v, n_decay, host_rec, dev_rec, beta1, beta2, eps):
+    """clip + AdamW of both weight-decay groups as the step record says, nothing on a dropped step"""
+    _chk_dev(p, g, m, v)
+    _chk_step_records(host_rec, dev_rec, p.device)
+    n = p.numel()
+    if g.numel() != n or m.numel() != n or v.numel() != n:
+        raise hip.SvitHipError("adamw_step_guarded: p, g, m, v differ in size")
+    hip.call("svit_adamw_step_guarded", ptr(p), ptr(g), ptr(m), ptr(v), n, n_decay, ptr(host_rec), ptr(dev_rec),
+             beta1, beta2, eps)
+
+
 # ---------------------------------------------------------------- head (K15) ----------------
 def _head_args(tokens, T, O, keep, head_params, outs):
     a = hip.HeadArgs()

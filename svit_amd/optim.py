@@ -4,12 +4,17 @@ Replaces `scaler.unscale_ -> clip_grad_norm_(1.0) -> AdamW.step` (tools/train_ne
 slowfast/models/optimizer.py:15-112) by three HBM-bound launches: one sum-of-squares reduction
 over the flat grad buffer and one fused clip+AdamW kernel per weight-decay group.  No host
 synchronisation: the clip coefficient is computed on the device from the reduced norm.
+
+GuardedClipAdamW is the same tail with the other half of `scaler.step`: a step whose gradients hold an inf or a NaN
+is dropped ON THE DEVICE (weights, moments and the step counter stay as they were).  Every scalar of the step lives
+in a step record in device memory, so the tail can end a captured graph (graph.GraphedTrainStep(optimizer=...)).
 """
 import math
 
+import numpy as np
 import torch
 
-from . import ops
+from . import hip, ops
 
 
 def get_lr_at_epoch(cfg, cur_epoch):
@@ -140,10 +145,132 @@ class FusedClipAdamW:
             g["lr"] = src["lr"]
 
 
+def pack_step_host(lr, weight_decay, max_norm, clip_value, grad_scale):
+    """the 32 bytes of svit_step_host (include/svit_hip.h) as float32 [8]; lr / weight_decay: (decayed group, the rest).
+    A clip value switches norm clipping off, the reference's precedence (tools/train_net.py:139-147)."""
+    clip_value = float(clip_value or 0.0)
+    max_norm = 0.0 if clip_value > 0 else float(max_norm or 0.0)
+    return np.array([lr[0], lr[1], weight_decay[0], weight_decay[1], max_norm, clip_value, grad_scale, 0.0],
+                    dtype=np.float32)
+
+
+class GuardedClipAdamW(FusedClipAdamW):
+    """FusedClipAdamW whose step is dropped on the device when a gradient is not finite, as `GradScaler.step` drops
+    it: weights, moments and `step_count` stay as they were, `skipped` counts it.  Two launches of the sum of squares
+    (the second also takes the decision) and ONE AdamW launch over both weight-decay groups, every scalar read from
+    the step record (svit_step_host uploaded by `upload()`, svit_step_dev owned by the kernels).  Nothing here
+    synchronises except the read-outs: `step_count`, `stats()`, `grad_norm()`, `check()`, `state_dict()`.
+
+    clip_grad_value: clip_grad_value_ bound (cfg.SOLVER.CLIP_GRAD_VAL); it replaces norm clipping when set.
+    max_consecutive_skips: `check()` raises once that many steps in a row were dropped -- the deferred form of the
+    reference's check_nan_losses (a NaN loss gives NaN gradients, thus a dropped step).  None: never raises."""
+
+    RING = 16
+
+    def __init__(self, model, lr, weight_decay=1e-4, betas=(0.9, 0.999), eps=1e-8, clip_grad_l2norm=None,
+                 grad_scale=1.0, clip_grad_value=None, max_consecutive_skips=None):
+        super().__init__(model, lr, weight_decay=weight_decay, betas=betas, eps=eps,
+                         clip_grad_l2norm=clip_grad_l2norm, grad_scale=grad_scale)
+        self.clip_value = clip_grad_value
+        self.max_consecutive_skips = max_consecutive_skips
+        dev = self.flat.data.device
+        self._records()
+        self.host_rec = torch.from_numpy(self._pack()).to(dev)
+        # bias corrections of steps 1, 2, ...: tabulated once on the host, by the code the classic step runs per call
+        self.bias_table = torch.from_numpy(ops.adamw_bias_table(betas[0], betas[1])).to(dev)
+        self._ws = torch.zeros(1024, device=dev)
+        self._slots, self._events, self._next = None, [None] * self.RING, 0
+        if dev.type == "cuda":
+            self._warm()
+
+    def _records(self):
+        """svit_step_dev as int32 [12] (created on first use: the base constructor already assigns step_count)"""
+        if "dev_rec" not in self.__dict__:
+            self.dev_rec = torch.zeros(12, dtype=torch.int32, device=self.flat.data.device)
+        return self.dev_rec
+
+    def _warm(self):
+        """one launch of each kernel on four dummy elements, so that a later stream capture meets loaded code; the
+        optimizer's own record and buffers are not touched"""
+        dev = self.flat.data.device
+        z = torch.zeros(4, 4, device=dev)
+        rec = torch.zeros(12, dtype=torch.int32, device=dev)
+        ops.step_guard(z[1], self.host_rec, rec, self.bias_table, self._ws)
+        ops.adamw_step_guarded(z[0], z[1], z[2], z[3], 2, self.host_rec, rec, self.betas[0], self.betas[1], self.eps)
+
+    def _pack(self):
+        g = self.param_groups
+        return pack_step_host((g[0]["lr"], g[1]["lr"]), (g[0]["weight_decay"], g[1]["weight_decay"]),
+                              self.clip, self.clip_value, self.grad_scale)
+
+    # ---- the step: upload() + enqueue(); a GraphedTrainStep holds enqueue() in its graph and calls upload() ------
+    def upload(self):
+        """send this step's lr / weight decay / clip bounds / grad scale, in stream order, without stalling the host:
+        a ring of pinned slots, each guarded by the event of the copy that last read it"""
+        if self._slots is None:
+            self._slots = torch.empty((self.RING, 8), dtype=torch.float32).pin_memory()
+        i = self._next
+        self._next = (i + 1) % self.RING
+        if self._events[i] is not None:
+            self._events[i].synchronize()
+        self._slots[i].copy_(torch.from_numpy(self._pack()))
+        self.host_rec.copy_(self._slots[i], non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(self.host_rec.device))
+        self._events[i] = ev
+
+    def enqueue(self):
+        """the three launches; allocation-free and capturable"""
+        f = self.flat
+        ops.step_guard(f.grad, self.host_rec, self.dev_rec, self.bias_table, self._ws)
+        ops.adamw_step_guarded(f.data, f.grad, self.exp_avg, self.exp_avg_sq, f.n_decay, self.host_rec, self.dev_rec,
+                               self.betas[0], self.betas[1], self.eps)
+
+    @torch.no_grad()
+    def step(self):
+        self.upload()
+        self.enqueue()
+
+    # ---- read-outs (each synchronises) ---------------------------------------------------------------------------
+    @property
+    def step_count(self):
+        """applied steps = AdamW's step counter; dropped steps do not advance it"""
+        return int(self._records().view(torch.int64)[0])
+
+    @step_count.setter
+    def step_count(self, value):
+        self._records().view(torch.int64)[0:1].fill_(int(value))
+
+    def stats(self):
+        r = hip.StepDev.from_buffer_copy(self.dev_rec.cpu().numpy().tobytes())
+        return {"applied": r.applied, "skipped": r.skipped, "consecutive_skipped": r.consecutive,
+                "grad_norm": r.grad_norm, "clip_coef": r.coef}
+
+    def grad_norm(self):
+        """host value of the global grad norm of the last APPLIED step (forces a sync; logging only)"""
+        return self.stats()["grad_norm"]
+
+    def check(self):
+        """call once per LOG_PERIOD: raises when `max_consecutive_skips` or more steps in a row were dropped"""
+        if self.max_consecutive_skips is None:
+            return
+        s = self.stats()
+        if s["consecutive_skipped"] >= self.max_consecutive_skips:
+            raise RuntimeError("the last %d optimizer steps were dropped for non-finite gradients (limit %d; %d applied, "
+                               "%d dropped in all, last finite grad norm %g)"
+                               % (s["consecutive_skipped"], self.max_consecutive_skips, s["applied"], s["skipped"],
+                                  s["grad_norm"]))
+
+
 def construct_optimizer(model, cfg):
-    """slowfast/models/optimizer.py:15-112 for the configuration the SViT recipe uses."""
+    """slowfast/models/optimizer.py:15-112 for the configuration the SViT recipe uses.  SOLVER.CLIP_GRAD_VAL, or the
+    opt-in SVIT.GUARDED_STEP (not a key of the default tree, like SVIT.REPRODUCIBLE), selects the guarded tail."""
     if cfg.SOLVER.OPTIMIZING_METHOD != "adamw" or not cfg.SOLVER.ZERO_WD_1D_PARAM:
         raise NotImplementedError("svit_amd fuses the configs/ssv2.yaml solver (adamw, ZERO_WD_1D_PARAM)")
+    if getattr(cfg.SVIT, "GUARDED_STEP", False) or cfg.SOLVER.CLIP_GRAD_VAL:
+        return GuardedClipAdamW(model, lr=cfg.SOLVER.BASE_LR, weight_decay=cfg.SOLVER.WEIGHT_DECAY,
+                                clip_grad_l2norm=cfg.SOLVER.CLIP_GRAD_L2NORM, clip_grad_value=cfg.SOLVER.CLIP_GRAD_VAL,
+                                max_consecutive_skips=getattr(cfg.SVIT, "MAX_CONSECUTIVE_SKIPS", None))
     return FusedClipAdamW(model, lr=cfg.SOLVER.BASE_LR, weight_decay=cfg.SOLVER.WEIGHT_DECAY,
                           clip_grad_l2norm=cfg.SOLVER.CLIP_GRAD_L2NORM)
 
