@@ -195,6 +195,35 @@ int svit_mixup_clips(float* x, const void* mix, int B, int planes, int H, int W,
 int svit_im2col_patch_u8_mix(const uint8_t* frames, int64_t frames_bytes, const float* lut_f32,
                              const int32_t* crops, const void* mix, void* cols, int B, int T, int Hs,
                              int Ws, int S, void* stream);
+/* Training augmentation on the uint8 route (svit_amd/augment.py): the reference's post-normalisation spatial pipeline of
+ * `spatial_sampling` + `RandomErasing` (slowfast/datasets/utils.py:110-192, transform.py:47-105,154-191,248-285,596-683,
+ * random_erasing.py) applied while the clip is read.  One 64-byte record per output clip, in DEVICE memory (so a captured
+ * step serves every draw):
+ *   struct SvitAug { int32 video, i, j, h, w, out_h, out_w, oy, ox, flip, erase_mode, et, el, eh, ew, seed; }
+ *   video          source video index
+ *   i, j, h, w     source rectangle inside the frame (top, left, height, width)
+ *   out_h, out_w   size the rectangle is resampled to (bilinear, F.interpolate(..., align_corners=False) given size=)
+ *   oy, ox         offset of the S x S window inside that resampled image
+ *   flip           horizontal flip of the window (non-zero = on)
+ *   erase_mode     0 none, 1 const (0), 2 rand (one N(0,1) per clip, channel, frame), 3 pixel (one per element)
+ *   et, el, eh, ew erase box (top, left, height, width) in output coordinates, on every frame
+ *   seed           noise seed: Philox-4x32-10 keyed by it, counter (y*S + x, clip, channel*T + frame), Box-Muller
+ * random-resized crop: out = S, o = 0; short-side jitter + crop (train or test): i = j = 0, (h, w) = (Hs, Ws), out = the
+ * rescaled size, o = the crop offset.  Output pixel (c, t, y, x): xs = flip ? S-1-x : x; per axis scale = float(in) /
+ * float(out), src = max(scale * (dst + 0.5) - 0.5, 0), i0 = min(int(src), in-1), i1 = i0 + (i0 < in-1), l1 = clamp(src - i0,
+ * 0, 1), l0 = 1 - l1; the four taps come from lut_f32 and are combined as l0y*(l0x*a + l1x*b) + l1y*(l0x*c + l1x*d) in fp32.
+ * The kernels clamp every record into the buffer (video into [0, V), h / w into [1, Hs] / [1, Ws], i / j so that the
+ * rectangle lies in the frame, out into [1, 2^24], o into [0, max(out - S, 0)], the box into the window; erase modes
+ * outside 1..3 are 0), so a record rewritten on the device never addresses outside `frames_bytes`.
+ * svit_im2col_patch_u8_aug: the [B*T'*S'*S', 448] bf16 operand of svit_im2col_patch_u8 from those values, rounded ONCE;
+ * `mix` (NULL or the record of svit_mixup_clips) blends / swaps clip b with clip B-1-b -- sampled through ITS record at
+ * the same (t, y, x) -- before the rounding, as svit_im2col_patch_u8_mix does.  With in == out, no flip and no erase the
+ * bytes are those of svit_im2col_patch_u8 (_mix) with the crop table (video, i + oy, j + ox).  S need not fit the frames.
+ * svit_u8_clips_render: the same values unrounded, out f32 [B,3,T,S,S]. */
+int svit_im2col_patch_u8_aug(const uint8_t* frames, int64_t frames_bytes, const float* lut_f32, const void* aug,
+                             const void* mix, void* cols, int B, int T, int Hs, int Ws, int S, void* stream);
+int svit_u8_clips_render(const uint8_t* frames, int64_t frames_bytes, const float* lut_f32, const void* aug,
+                         float* out_f32, int B, int T, int Hs, int Ws, int S, void* stream);
 /* cls / object token rows of the block-0 input (video_model_builder.py:326-363). */
 int svit_fill_special_tokens(float* x, const float* cls, const float* objq, const float* pos_t,
                              int B, int N, int L, int Tx, int O, int C, int add_pos, void* stream);

@@ -1,0 +1,357 @@
+"""Device-side training augmentation for uint8 clips: random-resized crop / scale jitter + crop, flip, random erasing.
+
+The reference's loader normalises the decoded frames and then, per clip and on the host in fp32, runs
+`utils.spatial_sampling` (slowfast/datasets/utils.py:110-192: `random_resized_crop` or `random_short_side_scale_jitter` +
+`random_crop`, `horizontal_flip`; test time: the short-side rescale + `uniform_crop`; datasets/transform.py:47-105,154-191,
+248-348,596-683) and `RandomErasing` (datasets/random_erasing.py, called from ssv2.py:345-426).  Here the frames stay uint8
+`[V,T,Hs,Ws,3]` in device memory, as with `input.U8Clips`; what was drawn for a clip is a 64-byte RECORD (`AugRecord`,
+`struct SvitAug` of include/svit_hip.h) in device memory next to them, and the patch-embedding im2col evaluates the whole
+pipeline per output pixel while it assembles its operand (`svit_im2col_patch_u8_aug`): bilinear taps from the fp32
+normalisation table, one bf16 rounding.  Every kernel reads the records at run time, so one captured `GraphedTrainStep`
+serves every draw -- a step only rewrites B x 64 bytes (and the frames).
+
+    sampler = build_sampler(cfg, "train")                       # cfg.DATA.* and, where the yaml brings it, cfg.AUG.*
+    records = [sampler.draw(Hs, Ws, video=v) for v in range(B)] # host: Python's `random` / `np.random`, reference order
+    clips = AugClips(frames_u8, cfg.DATA.TRAIN_CROP_SIZE, records, cfg.DATA.MEAN, cfg.DATA.STD)
+    model([clips], meta)          # or GraphedTrainStep(model, loss, [clips], labels[, mixup=...])
+    clips.render()                # the same values unrounded, fp32 [B,3,T,S,S]
+
+The draws.  `SpatialSampler.draw` consumes the two global streams exactly as the reference does for the same cfg, so after
+the same `random.seed` / `np.random.seed` it returns the reference's numbers: `_get_param_spatial_crop` (per try
+`random.uniform` for the area, `random.uniform` for the log aspect, one `np.random.uniform` the reference draws for its
+unused `switch_hw`; on success two `random.randint`; after 10 failures the central fallback), or the jitter size from
+`np.random.uniform` (its reciprocal form with INV_UNIFORM_SAMPLE) and the crop offsets from `np.random.randint` (y then x,
+each only where the rescaled side exceeds the crop); then `np.random.uniform` for the flip when DATA.RANDOM_FLIP; then
+`RandomErasing._erase_cube`: `random.random` against RE_PROB, up to 100 tries of two `random.uniform` and, on a fit, two
+`random.randint`.  ONE draw is added that the reference does not make: when a box was found and RE_MODE is `rand` or
+`pixel`, the record's noise seed comes last from `random.getrandbits(31)` (the reference draws the noise itself from
+torch's generator; here it is Philox keyed by that seed -- as random, not the same numbers).  At test time the reference
+still draws the (degenerate) jitter size from `np.random.uniform`, and so does `draw`.
+
+Where the reference itself fails, `draw` raises or does the evident thing: a rescaled frame that is already crop x crop
+makes the reference's `random_crop` return a bare tensor that `spatial_sampling` cannot unpack -- here the offsets are 0
+and nothing is drawn; a rescaled side SHORTER than the crop (a crop of the wrong size there) raises.
+
+Out of scope: RandAugment / colour jitter (uint8 PIL operations on the host, before this pipeline: feed their output as
+`frames`), DATA.TRAIN_JITTER_MOTION_SHIFT, boxes, the image ranks, AUG.RE_COUNT > 1, bicubic resampling, and the frames
+pass of GraphedTrainStep on an `AugClips` (use `render()` and the fp32 route).
+"""
+import collections
+import math
+import random
+
+import numpy as np
+import torch
+
+from . import hip
+from .input import normalize_lut_f32
+
+ERASE_NONE, ERASE_CONST, ERASE_RAND, ERASE_PIXEL = 0, 1, 2, 3
+ERASE_MODES = {"": ERASE_CONST, "const": ERASE_CONST, "rand": ERASE_RAND, "pixel": ERASE_PIXEL}
+FIELDS = "video i j h w out_h out_w oy ox flip erase_mode et el eh ew seed"
+MAX_OUT = 1 << 24           # (AUG_MAX_OUT of csrc/input.hip: resampled sizes stay exact in fp32)
+
+
+class AugRecord(collections.namedtuple("AugRecord", FIELDS)):
+    """One clip's draw, the 16 int32 words of `struct SvitAug` in order (include/svit_hip.h): source video; source
+    rectangle (i, j, h, w); the size (out_h, out_w) it is resampled to; the offset (oy, ox) of the S x S window in that
+    image; flip; erase mode (0 none, 1 const, 2 rand, 3 pixel), erase box (et, el, eh, ew) in output coordinates; seed."""
+    __slots__ = ()
+
+    def pack(self):
+        return np.array(self, dtype=np.int32)
+
+    @classmethod
+    def unpack(cls, words):
+        return cls(*(int(w) for w in np.asarray(words).reshape(16)))
+
+    @classmethod
+    def identity(cls, video, y0, x0, size):
+        """the integer crop (video, y0, x0) of a U8Clips row: in == out, weights exactly 1 and 0"""
+        return cls(video, y0, x0, size, size, size, size, 0, 0, 0, 0, 0, 0, 0, 0, 0)
+
+
+def pack_records(records):
+    """list of AugRecord (or an int [B,16] array / tensor) -> int32 [B,16] tensor on the host"""
+    if torch.is_tensor(records):
+        t = records.to(torch.int32)
+    elif isinstance(records, np.ndarray):
+        t = torch.from_numpy(np.ascontiguousarray(records.astype(np.int32)))
+    else:
+        t = torch.from_numpy(np.stack([AugRecord(*r).pack() for r in records]))
+    if t.dim() != 2 or t.shape[1] != 16:
+        raise ValueError("the record table is int32 [B,16], got %s" % (tuple(t.shape),))
+    return t.contiguous()
+
+
+def unpack_records(table):
+    return [AugRecord.unpack(row) for row in table.detach().cpu().numpy()]
+
+
+def validate_records(table, V, Hs, Ws, S):
+    """ValueError unless every row describes a rectangle inside the frame, a window inside the resampled image and a
+    box inside the window (the device additionally clamps: `clamp_records`)."""
+    t = table.to(torch.int64)
+    f = {n: t[:, k] for k, n in enumerate(FIELDS.split())}
+    checks = (
+        ("video outside [0, %d)" % V, (f["video"] >= 0) & (f["video"] < V)),
+        ("source rectangle outside the %dx%d frame" % (Hs, Ws),
+         (f["h"] >= 1) & (f["w"] >= 1) & (f["i"] >= 0) & (f["j"] >= 0) & (f["i"] + f["h"] <= Hs) & (f["j"] + f["w"] <= Ws)),
+        ("resampled size outside [1, 2^24]",
+         (f["out_h"] >= 1) & (f["out_w"] >= 1) & (f["out_h"] <= MAX_OUT) & (f["out_w"] <= MAX_OUT)),
+        ("%dx%d window outside the resampled image" % (S, S),
+         (f["oy"] >= 0) & (f["ox"] >= 0) & (f["oy"] + S <= f["out_h"]) & (f["ox"] + S <= f["out_w"])),
+        ("erase mode outside 0..3", (f["erase_mode"] >= 0) & (f["erase_mode"] <= 3)),
+        ("erase box outside the window",
+         (f["et"] >= 0) & (f["el"] >= 0) & (f["eh"] >= 0) & (f["ew"] >= 0) & (f["et"] + f["eh"] <= S) & (f["el"] + f["ew"] <= S)),
+    )
+    for what, ok in checks:
+        if not bool(ok.all()):
+            raise ValueError("augmentation record %d: %s" % (int((~ok).nonzero()[0, 0]), what))
+
+
+def clamp_records(table, V, Hs, Ws, S):
+    """What the kernels make of ANY int32 [B,16] table (aug_geom of csrc/input.hip) -- a valid table is unchanged except
+    that flip becomes 0 / 1."""
+    t = np.array(torch.as_tensor(table).detach().cpu().numpy(), dtype=np.int64).reshape(-1, 16)
+    f = {n: t[:, k].copy() for k, n in enumerate(FIELDS.split())}
+    f["video"] = np.clip(f["video"], 0, V - 1)
+    f["h"], f["w"] = np.clip(f["h"], 1, Hs), np.clip(f["w"], 1, Ws)
+    f["i"], f["j"] = np.clip(f["i"], 0, Hs - f["h"]), np.clip(f["j"], 0, Ws - f["w"])
+    f["out_h"], f["out_w"] = np.clip(f["out_h"], 1, MAX_OUT), np.clip(f["out_w"], 1, MAX_OUT)
+    f["oy"] = np.clip(f["oy"], 0, np.maximum(f["out_h"] - S, 0))
+    f["ox"] = np.clip(f["ox"], 0, np.maximum(f["out_w"] - S, 0))
+    f["flip"] = (f["flip"] != 0).astype(np.int64)
+    f["erase_mode"] = np.where((f["erase_mode"] >= 1) & (f["erase_mode"] <= 3), f["erase_mode"], 0)
+    f["et"], f["el"] = np.clip(f["et"], 0, S), np.clip(f["el"], 0, S)
+    f["eh"], f["ew"] = np.clip(f["eh"], 0, S - f["et"]), np.clip(f["ew"], 0, S - f["el"])
+    return torch.from_numpy(np.stack([f[n] for n in FIELDS.split()], axis=1).astype(np.int32))
+
+
+class AugClips:
+    """B augmented clips over V uint8 videos: `frames` u8 [V,T,Hs,Ws,3] on the GPU, `size` = S, `records` a list of
+    AugRecord (or an int32 [B,16] table).  Quacks like `input.U8Clips` where the model and GraphedTrainStep look at it;
+    `mix` (the device mix record of svit_amd/mixup.py) is set by MixUp.mix / GraphedTrainStep."""
+
+    def __init__(self, frames, size, records, mean=(0.45, 0.45, 0.45), std=(0.225, 0.225, 0.225), lut_f32=None):
+        if frames.dtype != torch.uint8 or frames.dim() != 5 or frames.shape[-1] != 3:
+            raise ValueError("frames must be uint8 [V,T,H,W,3], got %s %s" % (frames.dtype, tuple(frames.shape)))
+        if not frames.is_cuda:
+            raise hip.SvitHipError("AugClips lives on the GPU (the host ships uint8, a quarter of the bytes)")
+        self.frames = frames.contiguous()
+        V, T, Hs, Ws, _ = frames.shape
+        self.size = int(size)
+        if self.size < 1:
+            raise ValueError("size must be positive")
+        table = pack_records(records)
+        validate_records(table, V, Hs, Ws, self.size)          # one tiny reduction + sync; the kernels also clamp
+        self.records = table.to(frames.device)
+        self.mean, self.std = tuple(mean), tuple(std)
+        # the fp32 table is built here, outside any capture
+        self.lut_f32 = normalize_lut_f32(mean, std, frames.device) if lut_f32 is None else lut_f32
+        self.mix = None
+
+    # ---- the parts of the tensor interface the model path touches ---------------------------
+    @property
+    def shape(self):
+        return torch.Size((self.records.shape[0], 3, self.frames.shape[1], self.size, self.size))
+
+    @property
+    def device(self):
+        return self.frames.device
+
+    def dim(self):
+        return 5
+
+    def data_ptr(self):
+        return self.frames.data_ptr()
+
+    def detach(self):
+        return self
+
+    def contiguous(self):
+        return self
+
+    def clone(self):
+        return AugClips(self.frames.clone(), self.size, self.records.clone(), mean=self.mean, std=self.std,
+                        lut_f32=self.lut_f32)
+
+    def copy_(self, other, non_blocking=False):
+        self.frames.copy_(other.frames, non_blocking=non_blocking)
+        self.records.copy_(other.records, non_blocking=non_blocking)
+        return self
+
+    def set_records(self, records, validate=True):
+        """rewrite the record table in place (same B); validate=False skips the host check (the kernels clamp)"""
+        table = pack_records(records)
+        if table.shape != self.records.shape:
+            raise ValueError("the record table is int32 %s, got %s" % (tuple(self.records.shape), tuple(table.shape)))
+        if validate:
+            V, _, Hs, Ws, _ = self.frames.shape
+            validate_records(table, V, Hs, Ws, self.size)
+        self.records.copy_(table, non_blocking=True)
+        return self
+
+    def render(self):
+        """fp32 [B,3,T,S,S]: the values the im2col rounds, unrounded (svit_u8_clips_render; no mix)"""
+        from . import ops
+        return ops.u8_clips_render(self)
+
+
+class SpatialSampler:
+    """The reference's random spatial pipeline for one clip as an AugRecord.  mode "train" / "val" / "test" as the
+    reference's dataset (ssv2.py:252-292): AUG applies in "train" only."""
+
+    def __init__(self, crop_size, jitter_scales=(256, 320), scale=None, aspect=None, random_flip=True,
+                 inverse_uniform_sampling=False, re_prob=0.0, re_mode="const", re_count=1, spatial_sampling="random",
+                 min_area=0.02, max_area=1 / 3, min_aspect=0.3):
+        if (scale is None) != (aspect is None):
+            raise ValueError("TRAIN_JITTER_SCALES_RELATIVE and TRAIN_JITTER_ASPECT_RELATIVE come together")
+        if re_count not in (None, 0, 1):
+            raise NotImplementedError("AUG.RE_COUNT > 1 (several erase boxes per clip) is not supported")
+        if str(re_mode).lower() not in ERASE_MODES:
+            raise ValueError("AUG.RE_MODE %r" % (re_mode,))
+        if spatial_sampling not in ("random", "uniform"):
+            raise ValueError(spatial_sampling)
+        self.size = int(crop_size)
+        self.min_scale, self.max_scale = jitter_scales
+        self.scale = None if scale is None else tuple(scale)
+        self.aspect = None if aspect is None else tuple(aspect)
+        self.random_flip = bool(random_flip)
+        self.inverse = bool(inverse_uniform_sampling)
+        self.re_prob = float(re_prob)
+        self.re_mode = ERASE_MODES[str(re_mode).lower()]
+        self.min_area, self.max_area = min_area, max_area
+        self.log_aspect = (math.log(min_aspect), math.log(1 / min_aspect))
+        self.uniform = spatial_sampling == "uniform"
+        # what the last draw() went through (tests pin the rare branches on these)
+        self.trace = {}
+
+    # ---- transform._get_param_spatial_crop ---------------------------------------------------
+    def _resized_crop(self, height, width):
+        scale, ratio = self.scale, self.aspect
+        for n in range(10):
+            target_area = random.uniform(*scale) * (height * width)
+            aspect_ratio = math.exp(random.uniform(math.log(ratio[0]), math.log(ratio[1])))
+            w = int(round(math.sqrt(target_area * aspect_ratio)))
+            h = int(round(math.sqrt(target_area / aspect_ratio)))
+            np.random.uniform()             # the reference's `np.random.uniform() < 0.5 and switch_hw` (switch_hw False)
+            if 0 < w <= width and 0 < h <= height:
+                i = random.randint(0, height - h)
+                j = random.randint(0, width - w)
+                self.trace.update(tries=n + 1, fallback=False)
+                return i, j, h, w
+        in_ratio = float(width) / float(height)
+        if in_ratio < min(ratio):
+            w = width
+            h = int(round(w / min(ratio)))
+        elif in_ratio > max(ratio):
+            h = height
+            w = int(round(h * max(ratio)))
+        else:
+            w, h = width, height
+        self.trace.update(tries=10, fallback=True)
+        return (height - h) // 2, (width - w) // 2, h, w
+
+    # ---- transform.random_short_side_scale_jitter: the rescaled size ------------------------
+    def _jitter(self, height, width, min_size, max_size, inverse):
+        if inverse:
+            size = int(round(1.0 / np.random.uniform(1.0 / max_size, 1.0 / min_size)))
+        else:
+            size = int(round(np.random.uniform(min_size, max_size)))
+        if (width <= height and width == size) or (height <= width and height == size):
+            self.trace.update(jitter_size=size, jitter_identity=True)
+            return height, width
+        new_h = new_w = size
+        if width < height:
+            new_h = int(math.floor((float(height) / width) * size))
+        else:
+            new_w = int(math.floor((float(width) / height) * size))
+        self.trace.update(jitter_size=size, jitter_identity=False)
+        return new_h, new_w
+
+    def _check_covers(self, new_h, new_w):
+        if new_h < self.size or new_w < self.size:
+            raise ValueError("the rescaled frame %dx%d is smaller than the %d crop" % (new_h, new_w, self.size))
+
+    def _erase(self):
+        """RandomErasing._erase_cube on a [T,3,S,S] clip, count 1 -> (top, left, h, w) or None"""
+        if random.random() > self.re_prob:
+            return None
+        area = self.size * self.size
+        for n in range(100):
+            target_area = random.uniform(self.min_area, self.max_area) * area / 1
+            aspect_ratio = math.exp(random.uniform(*self.log_aspect))
+            h = int(round(math.sqrt(target_area * aspect_ratio)))
+            w = int(round(math.sqrt(target_area / aspect_ratio)))
+            if w < self.size and h < self.size:
+                top = random.randint(0, self.size - h)
+                left = random.randint(0, self.size - w)
+                self.trace.update(erase_tries=n + 1)
+                return top, left, h, w
+        self.trace.update(erase_tries=100)
+        return None
+
+    def draw(self, Hs, Ws, video=0, spatial_idx=1):
+        """One clip's record for a Hs x Ws source.  spatial_idx: the test-time crop (0, 1, 2), "uniform" sampling only."""
+        S = self.size
+        self.trace = {}
+        if self.uniform:
+            if spatial_idx not in (0, 1, 2):
+                raise ValueError("spatial_idx must be 0, 1 or 2")
+            new_h, new_w = self._jitter(Hs, Ws, S, S, False)          # (the reference draws the degenerate size too)
+            self._check_covers(new_h, new_w)
+            oy, ox = int(math.ceil((new_h - S) / 2)), int(math.ceil((new_w - S) / 2))
+            if new_h > new_w:
+                oy = 0 if spatial_idx == 0 else new_h - S if spatial_idx == 2 else oy
+            else:
+                ox = 0 if spatial_idx == 0 else new_w - S if spatial_idx == 2 else ox
+            return AugRecord(video, 0, 0, Hs, Ws, new_h, new_w, oy, ox, 0, 0, 0, 0, 0, 0, 0)
+        if self.scale is None:
+            new_h, new_w = self._jitter(Hs, Ws, self.min_scale, self.max_scale, self.inverse)
+            self._check_covers(new_h, new_w)
+            oy = ox = 0
+            if new_h == S and new_w == S:
+                self.trace.update(crop_skipped=True)
+            else:
+                if new_h > S:
+                    oy = int(np.random.randint(0, new_h - S))
+                if new_w > S:
+                    ox = int(np.random.randint(0, new_w - S))
+            geom = (0, 0, Hs, Ws, new_h, new_w, oy, ox)
+        else:
+            geom = self._resized_crop(Hs, Ws) + (S, S, 0, 0)
+        flip = int(np.random.uniform() < 0.5) if self.random_flip else 0
+        mode, box, seed = ERASE_NONE, (0, 0, 0, 0), 0
+        if self.re_prob > 0:
+            found = self._erase()
+            if found is not None:
+                mode, box = self.re_mode, found
+                if mode in (ERASE_RAND, ERASE_PIXEL):
+                    seed = random.getrandbits(31)       # the ONE draw the reference does not make (module docstring)
+        return AugRecord(video, *geom, flip, mode, *box, seed)
+
+
+def build_sampler(cfg, mode="train"):
+    """SpatialSampler from cfg.DATA.* and cfg.AUG.* as the reference's dataset reads them (ssv2.py:95-100,252-292,377-422).
+    AUG is not a key of this build's default tree (the reference's yaml brings it): absent = the reference's defaults,
+    ENABLE False."""
+    if mode not in ("train", "val", "test"):
+        raise ValueError("mode %r" % (mode,))
+    d = cfg.DATA
+    if mode == "test":
+        return SpatialSampler(d.TEST_CROP_SIZE, spatial_sampling="uniform", random_flip=False)
+    a = getattr(cfg, "AUG", None)
+    aug = mode == "train" and a is not None and bool(getattr(a, "ENABLE", False))
+    scale = aspect = None
+    re_prob, re_mode, re_count = 0.0, "const", 1
+    if aug:
+        if getattr(d, "TRAIN_JITTER_MOTION_SHIFT", False):
+            raise NotImplementedError("DATA.TRAIN_JITTER_MOTION_SHIFT is not supported")
+        scl, asp = list(d.TRAIN_JITTER_SCALES_RELATIVE), list(d.TRAIN_JITTER_ASPECT_RELATIVE)
+        scale, aspect = (scl or None), (asp or None)
+        re_prob = float(getattr(a, "RE_PROB", 0.25))
+        re_mode, re_count = getattr(a, "RE_MODE", "pixel"), getattr(a, "RE_COUNT", 1)
+    return SpatialSampler(d.TRAIN_CROP_SIZE, jitter_scales=tuple(d.TRAIN_JITTER_SCALES), scale=scale, aspect=aspect,
+                          random_flip=d.RANDOM_FLIP, inverse_uniform_sampling=d.INV_UNIFORM_SAMPLE, re_prob=re_prob,
+                          re_mode=re_mode, re_count=re_count)

@@ -155,6 +155,25 @@ __device__ __forceinline__ float gelu_erf_grad(float x) {
   return cdf + x * pdf;
 }
 
+// Philox-4x32-10 (Salmon et al., SC'11): counter = (idx, 0, draw), key = seed -> four uniforms in [0, 1) on a 2^-24 grid.
+// Counter-based: a value is a pure function of (seed, draw, idx), whichever thread of whichever kernel asks for it.
+__device__ __forceinline__ void philox_round(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
+  const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
+  const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
+  c[1] = (uint32_t)p1; c[3] = (uint32_t)p0; c[0] = n0; c[2] = n2;
+}
+__device__ __forceinline__ void philox4(uint64_t seed, uint64_t draw, uint32_t idx, float (&u)[4]) {
+  uint32_t c[4] = {idx, 0u, (uint32_t)draw, (uint32_t)(draw >> 32)};
+  uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    philox_round(c, k0, k1);
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) u[i] = (float)(c[i] >> 8) * (1.0f / 16777216.0f);      // [0, 1) on a 2^-24 grid
+}
+
 // Second stage of the two-stage parameter-gradient reductions: every block of the producing
 // kernel stores its partial sums as one row of `partial` [nblocks][n] with plain stores, then
 // this kernel adds the column sums into up to six destination vectors (segments of n).

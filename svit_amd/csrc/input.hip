@@ -271,6 +271,265 @@ __global__ __launch_bounds__(256) void im2col_patch_u8_mix_kernel(
     }
   }
 }
+// ---------------------------------------------------------------------------------------------------------------
+// Training augmentation on the uint8 route (svit_amd/augment.py): the reference's post-normalisation spatial pipeline
+// -- random-resized crop or short-side jitter + crop with bilinear resampling (datasets/transform.py:47-105,154-191,
+// 596-683), horizontal flip (transform.py:248-285) and random erasing of a cube (datasets/random_erasing.py) -- as a
+// pure function of the output coordinate, driven by one 64-byte record per clip in device memory (SvitAug,
+// include/svit_hip.h).  `aug_pixel` below is that function; svit_u8_clips_render writes its fp32 values,
+// svit_im2col_patch_u8_aug rounds them once to bf16 while it assembles the patch-embedding operand.
+struct SvitAug {
+  int video, i, j, h, w, out_h, out_w, oy, ox, flip, erase_mode, et, el, eh, ew, seed;
+};
+
+// a record clamped into the buffer (the host validates at construction, svit_amd/augment.py; a record rewritten on the
+// device can then still never address outside `frames_bytes`) + the two resampling scales
+struct AugGeom {
+  int64_t vbase;                        // byte offset of the source video
+  int i, j, h, w, oy, ox, flip, mode;
+  int et, eb, el, er;                   // erase box [et, eb) x [el, er) in output coordinates
+  float sy, sx;                         // float(in) / float(out), as F.interpolate(size=...) computes it
+  uint32_t seed;
+};
+constexpr int AUG_MAX_OUT = 1 << 24;    // resampled sizes stay exact in fp32
+
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return max(lo, min(v, hi)); }
+
+__device__ __forceinline__ AugGeom aug_geom(const SvitAug* __restrict__ aug, int b, int64_t n_videos, int T, int Hs, int Ws,
+                                            int S) {
+  const SvitAug r = aug[b];
+  AugGeom g;
+  g.vbase = (int64_t)clampi(r.video, 0, (int)n_videos - 1) * T * Hs * Ws * 3;
+  g.h = clampi(r.h, 1, Hs);
+  g.w = clampi(r.w, 1, Ws);
+  g.i = clampi(r.i, 0, Hs - g.h);
+  g.j = clampi(r.j, 0, Ws - g.w);
+  const int out_h = clampi(r.out_h, 1, AUG_MAX_OUT), out_w = clampi(r.out_w, 1, AUG_MAX_OUT);
+  g.oy = clampi(r.oy, 0, max(out_h - S, 0));
+  g.ox = clampi(r.ox, 0, max(out_w - S, 0));
+  g.flip = r.flip != 0;
+  g.mode = (r.erase_mode >= 1 && r.erase_mode <= 3) ? r.erase_mode : 0;
+  g.et = clampi(r.et, 0, S);
+  g.el = clampi(r.el, 0, S);
+  g.eb = g.et + clampi(r.eh, 0, S - g.et);
+  g.er = g.el + clampi(r.ew, 0, S - g.el);
+  // the quotient in double, rounded once: the library is built with -ffast-math, whose fp32 division is a reciprocal
+  // and a multiply -- up to 2 ulp off what the host computes
+  g.sy = (float)((double)g.h / (double)out_h);
+  g.sx = (float)((double)g.w / (double)out_w);
+  g.seed = (uint32_t)r.seed;
+  return g;
+}
+
+// One axis of F.interpolate(mode="bilinear", align_corners=False): destination index -> the two source indices and their
+// weights (ATen area_pixel_compute_source_index + guard_index_and_lambda).  The weights are made opaque so that
+// -ffast-math cannot rewrite the lerps that consume them differently in the two kernels that inline this.
+__device__ __forceinline__ void aug_axis(int dst, int in, float scale, int& i0, int& i1, float& l0, float& l1) {
+  float src = __builtin_fmaf(scale, (float)dst + 0.5f, -0.5f);
+  src = src < 0.f ? 0.f : src;
+  i0 = min((int)src, in - 1);
+  i1 = i0 + (i0 < in - 1 ? 1 : 0);
+  l1 = fminf(fmaxf(src - (float)i0, 0.f), 1.f);
+  l0 = 1.f - l1;
+  __asm__("" : "+v"(l0));
+  __asm__("" : "+v"(l1));
+}
+
+// N(0,1) of the erasing noise: Philox keyed by the record's seed, counter = (idx, clip b, plane c*T + t), Box-Muller on
+// the first two uniforms; v_log / v_sqrt / v_cos (input in revolutions) directly, so every caller gets the same bits.
+// 1 - u is in [2^-24, 1]: |z| <= 5.77.
+__device__ __forceinline__ float aug_noise(uint32_t seed, int b, int plane, uint32_t idx) {
+  float u[4];
+  philox4((uint64_t)seed, ((uint64_t)(uint32_t)b << 32) | (uint32_t)plane, idx, u);
+  const float r = __builtin_amdgcn_sqrtf(-1.3862943611198906f * __builtin_amdgcn_logf(1.f - u[0]));   // sqrt(-2 ln(1 - u0))
+  return r * __builtin_amdgcn_cosf(u[1]);
+}
+
+// taps straight from global memory: pixel (r, col) of the record's rectangle in frame t -> its three bytes
+struct AugGlobalFetch {
+  const uint8_t* __restrict__ frames;
+  int64_t vbase;
+  int Hs, Ws, i, j;
+  __device__ __forceinline__ uint32_t operator()(int t, int r, int col) const {
+    const uint8_t* p = frames + vbase + (((int64_t)t * Hs + (i + r)) * Ws + (j + col)) * 3;
+    return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16);
+  }
+};
+
+// The fp32 value of output pixel (t, y, x) of clip b, all three channels: erased (inside the box, on every frame), or
+// the bilinear resample of the normalised source rectangle.  `tab` f32 [3][256] is the normalisation table.  With
+// in == out the weights are exactly 1 and 0 and the value is the tap itself.
+template <class Fetch>
+__device__ __forceinline__ void aug_pixel(const AugGeom& g, const float* tab, const Fetch& fetch, int b, int t, int y,
+                                          int x, int T, int S, float (&v)[3]) {
+  if (g.mode && y >= g.et && y < g.eb && x >= g.el && x < g.er) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+      v[c] = g.mode == 1 ? 0.f : aug_noise(g.seed, b, c * T + t, g.mode == 3 ? (uint32_t)(y * S + x) : 0xFFFFFFFFu);
+    return;
+  }
+  const int xs = g.flip ? S - 1 - x : x;
+  int r0, r1, c0, c1;
+  float l0y, l1y, l0x, l1x;
+  aug_axis(g.oy + y, g.h, g.sy, r0, r1, l0y, l1y);
+  aug_axis(g.ox + xs, g.w, g.sx, c0, c1, l0x, l1x);
+  const uint32_t pa = fetch(t, r0, c0), pb = fetch(t, r0, c1), pc = fetch(t, r1, c0), pd = fetch(t, r1, c1);
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const float a = tab[c * 256 + ((pa >> (8 * c)) & 255u)], bb = tab[c * 256 + ((pb >> (8 * c)) & 255u)];
+    const float cc = tab[c * 256 + ((pc >> (8 * c)) & 255u)], d = tab[c * 256 + ((pd >> (8 * c)) & 255u)];
+    float p = l1x * bb, q = l1x * d;
+    __asm__("" : "+v"(p));
+    __asm__("" : "+v"(q));
+    const float top = __builtin_fmaf(l0x, a, p), bot = __builtin_fmaf(l0x, cc, q);
+    float s = l1y * bot;
+    __asm__("" : "+v"(s));
+    v[c] = __builtin_fmaf(l0y, top, s);
+  }
+}
+
+__global__ __launch_bounds__(256) void u8_clips_render_kernel(
+    const uint8_t* __restrict__ frames, int64_t frames_bytes, const float* __restrict__ lut,
+    const SvitAug* __restrict__ aug, float* __restrict__ out, int T, int Hs, int Ws, int S) {
+  __shared__ float tab[768];
+  const int b = blockIdx.y / T, t = blockIdx.y % T;
+  const int64_t n_videos = frames_bytes / ((int64_t)T * Hs * Ws * 3);
+  const AugGeom g = aug_geom(aug, b, n_videos, T, Hs, Ws, S);
+  const AugGlobalFetch fetch{frames, g.vbase, Hs, Ws, g.i, g.j};
+  for (int i = threadIdx.x; i < 768; i += 256) tab[i] = lut[i];
+  __syncthreads();
+  const int n = S * S;
+  float* o = out + ((int64_t)b * 3 * T + t) * n;
+  for (int p = blockIdx.x * 256 + threadIdx.x; p < n; p += gridDim.x * 256) {
+    float v[3];
+    aug_pixel(g, tab, fetch, b, t, p / S, p % S, T, S, v);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) o[(int64_t)c * T * n + p] = v[c];
+  }
+}
+
+// svit_im2col_patch_u8 with the fill phase going through aug_pixel.  Same grid, same LDS image and the same store phase.
+// Per chunk the block needs, of each of its three frames, the source rows [r_lo, r_hi] x columns [c_lo, c_hi] that the
+// 7 output rows x COLS output columns resample from; where that rectangle fits AUG_STAGE bytes (img + tab + stage =
+// 51.5 KB, three blocks per CU like the mix kernel) it is staged into LDS with aligned word loads -- every source byte
+// is then fetched from memory once per block instead of once per tap -- otherwise the taps are gathered from global
+// memory.  The mix partner (clip B-1-b through its own record) is always gathered: it is needed on mixing steps only.
+constexpr int AUG_STAGE = 16384;
+
+// taps from the staged rectangle: row (kt, r) starts at the byte its global address has modulo 4, so the staging
+// copies whole words
+struct AugStageFetch {
+  const uint8_t* st;
+  int t0, r_lo, c_lo, nrows, pitch;
+  uint32_t rowbase;                     // (video*T*Hs + i) modulo 2^32: only the address modulo 4 is needed
+  int Hs, Ws, jc;                       // jc = j + c_lo
+  __device__ __forceinline__ uint32_t operator()(int t, int r, int col) const {
+    const uint32_t mis = (((rowbase + (uint32_t)t * Hs + r) * Ws + jc) * 3u) & 3u;
+    const uint8_t* p = st + ((t - t0) * nrows + (r - r_lo)) * pitch + mis + (col - c_lo) * 3;
+    return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16);
+  }
+};
+
+__global__ __launch_bounds__(256) void im2col_patch_u8_aug_kernel(
+    const uint8_t* __restrict__ frames, int64_t frames_bytes, const float* __restrict__ lut,
+    const SvitAug* __restrict__ aug, const SvitMix* __restrict__ mix, bf16_t* __restrict__ cols,
+    int B, int T, int Hs, int Ws, int S, int To, int Ho, int Wo) {
+  __shared__ bf16_t img[63][COLS + 4];  // [(c*3+kt)*7+ky][x - x_start], augmented + mixed + rounded, 0 = padding
+  __shared__ float tab[768];
+  __shared__ uint32_t stage[AUG_STAGE / 4];
+  SvitMix m = {0, 1.f, 0.f, 0, 0, 0, 0, 0};
+  if (mix) m = *mix;
+  const bool mixing = m.mode == 1 || m.mode == 2;
+  const int yo = blockIdx.x % Ho, to = (blockIdx.x / Ho) % To, b = blockIdx.x / (Ho * To);
+  const int pb = B - 1 - b;
+  const int64_t n_videos = frames_bytes / ((int64_t)T * Hs * Ws * 3);
+  const AugGeom g = aug_geom(aug, b, n_videos, T, Hs, Ws, S);
+  const AugGeom g2 = aug_geom(aug, pb, n_videos, T, Hs, Ws, S);
+  const AugGlobalFetch gfetch{frames, g.vbase, Hs, Ws, g.i, g.j};
+  const AugGlobalFetch gfetch2{frames, g2.vbase, Hs, Ws, g2.i, g2.j};
+  for (int i = threadIdx.x; i < 768; i += 256) tab[i] = lut[i];
+  bf16_t* out = cols + (((int64_t)b * To + to) * Ho + yo) * Wo * 448;
+  const int t0 = to * 2 - 1, y0 = yo * 4 - 3;
+  // the source rows of the block's output rows (the same for every chunk)
+  const int ya = max(y0, 0), yb = min(y0 + 7, S);
+  int r_lo, r_hi, tmp;
+  float f0, f1;
+  aug_axis(g.oy + ya, g.h, g.sy, r_lo, tmp, f0, f1);
+  aug_axis(g.oy + yb - 1, g.h, g.sy, tmp, r_hi, f0, f1);
+  const int nrows = r_hi - r_lo + 1;
+  for (int xc0 = 0; xc0 < Wo; xc0 += XO) {
+    const int x_start = xc0 * 4 - 4;
+    const int xa = max(x_start, 0), xb = min(x_start + COLS, S);   // clip columns in the frame
+    // the source columns of this chunk's output columns (xs = S-1-x under the flip: the range is mirrored)
+    int c_lo = 0, c_hi = 0;
+    if (xb > xa) {
+      aug_axis(g.ox + (g.flip ? S - xb : xa), g.w, g.sx, c_lo, tmp, f0, f1);
+      aug_axis(g.ox + (g.flip ? S - 1 - xa : xb - 1), g.w, g.sx, tmp, c_hi, f0, f1);
+    }
+    const int rowbytes = (c_hi - c_lo + 1) * 3, pitch = (rowbytes + 6) & ~3;
+    const bool staged = xb > xa && (int64_t)3 * nrows * pitch <= AUG_STAGE;
+    __syncthreads();                    // table ready / previous chunk's readers done
+    if (staged) {
+      for (int kr = 0; kr < 3 * nrows; ++kr) {
+        const int kt = kr / nrows, r = r_lo + kr - kt * nrows, t = t0 + kt;
+        if (t < 0 || t >= T) continue;                               // uniform over the block
+        const int64_t base = g.vbase + (((int64_t)t * Hs + (g.i + r)) * Ws + (g.j + c_lo)) * 3;
+        const int64_t a0 = base & ~(int64_t)3;                       // aligned 4-byte words
+        const int nwords = (int)((base + rowbytes - a0 + 3) >> 2);   // <= pitch / 4
+        uint32_t* dst = stage + kr * (pitch >> 2);
+        for (int w = threadIdx.x; w < nwords; w += 256) {
+          const int64_t addr = a0 + 4 * (int64_t)w;
+          uint32_t word = 0;
+          if (addr + 4 <= frames_bytes) {
+            word = *(const uint32_t*)(frames + addr);
+          } else {                                                    // last bytes of the buffer
+            for (int k = 0; k < 4; ++k)
+              if (addr + k < frames_bytes) word |= (uint32_t)frames[addr + k] << (8 * k);
+          }
+          dst[w] = word;
+        }
+      }
+      __syncthreads();
+    }
+    const AugStageFetch sfetch{(const uint8_t*)stage, t0, r_lo, c_lo, nrows, pitch,
+                               (uint32_t)(g.vbase / ((int64_t)Ws * 3)) + (uint32_t)g.i, Hs, Ws, g.j + c_lo};
+    // every element of the 63 x COLS image is written here (0 outside the clip): no separate zero pass
+    for (int p = threadIdx.x; p < 21 * COLS; p += 256) {
+      const int line = p / COLS, px = p - line * COLS;
+      const int ky = line % 7, kt = line / 7;
+      const int t = t0 + kt, y = y0 + ky, x = x_start + px;
+      float v[3] = {0.f, 0.f, 0.f};
+      if (t >= 0 && t < T && y >= 0 && y < S && x >= 0 && x < S) {
+        if (staged) aug_pixel(g, tab, sfetch, b, t, y, x, T, S, v);
+        else aug_pixel(g, tab, gfetch, b, t, y, x, T, S, v);
+        if (mixing && (m.mode == 1 || (y >= m.yl && y < m.yh && x >= m.xl && x < m.xh))) {
+          float o[3];
+          aug_pixel(g2, tab, gfetch2, pb, t, y, x, T, S, o);
+#pragma unroll
+          for (int c = 0; c < 3; ++c) v[c] = m.mode == 1 ? mix_blend(v[c], o[c], m.lam, m.oml) : o[c];
+        }
+      }
+#pragma unroll
+      for (int c = 0; c < 3; ++c) img[(c * 3 + kt) * 7 + ky][px] = f32_to_bf16(v[c]);
+    }
+    __syncthreads();
+    const int n_xo = min(XO, Wo - xc0);
+    for (int i = threadIdx.x; i < n_xo * 56; i += 256) {
+      const int xl = i / 56, chunk = i % 56;
+      bf16_t e8[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const int col = chunk * 8 + e;
+        const int kx = col % 7, r = col / 7;
+        e8[e] = col < 441 ? img[r][xl * 4 + 1 + kx] : (bf16_t)0;   // x = xo*4 - 3 + kx
+      }
+      uint4 o;
+      o.x = (uint32_t)e8[0] | ((uint32_t)e8[1] << 16); o.y = (uint32_t)e8[2] | ((uint32_t)e8[3] << 16);
+      o.z = (uint32_t)e8[4] | ((uint32_t)e8[5] << 16); o.w = (uint32_t)e8[6] | ((uint32_t)e8[7] << 16);
+      ((uint4*)out)[(size_t)(xc0 + xl) * 56 + chunk] = o;
+    }
+  }
+}
 }  // namespace
 
 extern "C" int svit_im2col_patch_u8(const uint8_t* frames, int64_t frames_bytes, const void* lut,
@@ -320,6 +579,45 @@ extern "C" int svit_mixup_clips(float* x, const void* mix, int B, int planes, in
   else
     hipLaunchKernelGGL(mixup_clips_kernel<false>, dim3((unsigned)blocks, (unsigned)pairs), dim3(256), 0,
                        (hipStream_t)stream, x, (const SvitMix*)mix, B, (uint32_t)n, (uint32_t)H, (uint32_t)W);
+  SVIT_LAUNCH_CHECK();
+  return SVIT_OK;
+}
+
+static int aug_args_ok(const void* frames, int64_t frames_bytes, const void* lut_f32, const void* aug, const void* out,
+                       int B, int T, int Hs, int Ws, int S) {
+  if (!frames || !lut_f32 || !aug || !out) return SVIT_ERR_ARG;
+  if (B <= 0 || T <= 0 || Hs <= 0 || Ws <= 0 || S <= 0 || S > 16384 || Hs > 32768 || Ws > 32768) return SVIT_ERR_SHAPE;
+  if (frames_bytes < (int64_t)T * Hs * Ws * 3) return SVIT_ERR_SHAPE;                 // at least one whole video
+  if (frames_bytes / ((int64_t)T * Hs * Ws * 3) > 0x7fffffff) return SVIT_ERR_SHAPE;
+  if (((uintptr_t)frames | (uintptr_t)lut_f32 | (uintptr_t)aug | (uintptr_t)out) & 3) return SVIT_ERR_ALIGN;
+  return SVIT_OK;
+}
+
+extern "C" int svit_im2col_patch_u8_aug(const uint8_t* frames, int64_t frames_bytes, const float* lut_f32,
+                                        const void* aug, const void* mix, void* cols, int B, int T, int Hs,
+                                        int Ws, int S, void* stream) {
+  const int rc = aug_args_ok(frames, frames_bytes, lut_f32, aug, cols, B, T, Hs, Ws, S);
+  if (rc != SVIT_OK) return rc;
+  if (((uintptr_t)mix & 3) || ((uintptr_t)cols & 15)) return SVIT_ERR_ALIGN;
+  const int To = (T + 2 - 3) / 2 + 1, Ho = (S + 6 - 7) / 4 + 1, Wo = (S + 6 - 7) / 4 + 1;
+  if ((int64_t)B * To * Ho > 0x7fffffff) return SVIT_ERR_SHAPE;
+  hipLaunchKernelGGL(im2col_patch_u8_aug_kernel, dim3((unsigned)(B * To * Ho)), dim3(256), 0,
+                     (hipStream_t)stream, frames, frames_bytes, lut_f32, (const SvitAug*)aug, (const SvitMix*)mix,
+                     (bf16_t*)cols, B, T, Hs, Ws, S, To, Ho, Wo);
+  SVIT_LAUNCH_CHECK();
+  return SVIT_OK;
+}
+
+extern "C" int svit_u8_clips_render(const uint8_t* frames, int64_t frames_bytes, const float* lut_f32,
+                                    const void* aug, float* out_f32, int B, int T, int Hs, int Ws, int S,
+                                    void* stream) {
+  const int rc = aug_args_ok(frames, frames_bytes, lut_f32, aug, out_f32, B, T, Hs, Ws, S);
+  if (rc != SVIT_OK) return rc;
+  if ((int64_t)B * T > 65535) return SVIT_ERR_SHAPE;
+  int blocks = (S * S + 255) / 256;
+  if (blocks > 1024) blocks = 1024;
+  hipLaunchKernelGGL(u8_clips_render_kernel, dim3((unsigned)blocks, (unsigned)(B * T)), dim3(256), 0,
+                     (hipStream_t)stream, frames, frames_bytes, lut_f32, (const SvitAug*)aug, out_f32, T, Hs, Ws, S);
   SVIT_LAUNCH_CHECK();
   return SVIT_OK;
 }

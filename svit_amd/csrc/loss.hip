@@ -356,22 +356,7 @@ extern "C" int svit_ce_loss_soft(const float* logits, const float* target, const
 // workgroup to finish advances state[1], so a replayed HIP graph draws fresh numbers every replay with no host involvement
 // (state lives in device memory).  Not torch's stream: the masks are as random, not the same numbers.
 namespace {
-__device__ __forceinline__ void philox_round(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-  const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
-  const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
-  c[1] = (uint32_t)p1; c[3] = (uint32_t)p0; c[0] = n0; c[2] = n2;
-}
-__device__ __forceinline__ void philox4(uint64_t seed, uint64_t draw, uint32_t idx, float (&u)[4]) {
-  uint32_t c[4] = {idx, 0u, (uint32_t)draw, (uint32_t)(draw >> 32)};
-  uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    philox_round(c, k0, k1);
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-#pragma unroll
-  for (int i = 0; i < 4; ++i) u[i] = (float)(c[i] >> 8) * (1.0f / 16777216.0f);      // [0, 1) on a 2^-24 grid
-}
+// (philox_round / philox4: common.h -- shared with the erasing noise of csrc/input.hip)
 __global__ __launch_bounds__(256) void step_draws_kernel(unsigned long long* __restrict__ state, const float* __restrict__ keep,
                                                          int n_scale, int per_block, float* __restrict__ scales,
                                                          int n_drop, float p_drop, float* __restrict__ drop) {

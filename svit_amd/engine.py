@@ -13,6 +13,7 @@ import math
 import torch
 
 from . import arch, hip, ops
+from .augment import AugClips
 from .input import U8Clips
 
 HD = arch.HEAD_DIM
@@ -332,11 +333,14 @@ class Engine:
 
     # ------------------------------------------------------------------ forward ----------
     def forward(self, video, drop_scales=None, save=True):
-        """video f32 [B,3,Tx,S,S] (or U8Clips) -> (normed tokens f32 [B,N_last,C_last], saved-state dict)."""
+        """video f32 [B,3,Tx,S,S] (or U8Clips / AugClips) -> (normed tokens f32 [B,N_last,C_last], saved-state dict)."""
         plan, f = self.plan, self.flat
         if isinstance(video, U8Clips):       # decoded uint8 frames + crop table (svit_amd/input.py)
             B, _, Tx = video.shape[:3]
             cols, (To, Ho, Wo) = ops.im2col_patch_u8(video)
+        elif isinstance(video, AugClips):    # the same + one augmentation record per clip (svit_amd/augment.py)
+            B, _, Tx = video.shape[:3]
+            cols, (To, Ho, Wo) = ops.im2col_patch_u8_aug(video)
         else:
             if video.dim() == 4:
                 video = video.unsqueeze(2)

@@ -41,7 +41,9 @@ class GraphedTrainStep:
     def __init__(self, model, loss_fun, inputs, labels, warmup=2, frames_pass=False, mixup=None, optimizer=None):
         """model: SViT or its DataParallel wrapper (train mode); loss_fun(preds, extra, labels) ->
         scalar; inputs: the reference's `inputs` list ([video f32 [B,3,T,S,S]]); labels: any
-        tensor (or tuple/dict of tensors) `loss_fun` takes -- copied into static buffers.
+        tensor (or tuple/dict of tensors) `loss_fun` takes -- copied into static buffers.  The static input may be an
+        input.U8Clips or an augment.AugClips (uint8 frames + crop table / augmentation records, read by the im2col at
+        replay time: `__call__` copies frames and table into the static ones).
         frames_pass: also run the reference's no-grad single-frame forward of every clip
         (tools/train_net.py:105-110) inside the graph; its outputs reach `loss_fun` as
         extra["frames_output"] = {"preds", "extra_preds"} (the consistency-loss operand).
@@ -80,6 +82,9 @@ class GraphedTrainStep:
         self.dp = model if hasattr(model, "_on_ready") and (getattr(model, "world_size", 1) > 1 or
                                                            getattr(model, "force_collectives", False)) else None
         self.x = inputs[0].detach().clone().contiguous()
+        from .augment import AugClips
+        if frames_pass and isinstance(self.x, AugClips):
+            raise hip.SvitHipError("the frames pass does not take an AugClips: feed clips.render() (the fp32 route)")
         self.labels = _tree_map(lambda t: t.detach().clone(), labels)
         self.mix_record = self.loss_labels = None
         if mixup is not None:
@@ -94,7 +99,7 @@ class GraphedTrainStep:
             self._mix_slots = torch.empty((16, 8), dtype=torch.int32).pin_memory()
             self._mix_events, self._mix_next = [None] * 16, 0
             if not torch.is_tensor(self.x):
-                self.x.lut_f32                # (U8Clips: the fp32 table is built here, outside the capture)
+                self.x.lut_f32                # (U8Clips / AugClips: the fp32 table is built here, outside the capture)
                 self.x.mix = self.mix_record
         self.segments = []          # replay items: ("graph", CUDAGraph) | ("side", fn) | ("join", None) | ("ready", ranks)
         self.loss = self.preds = self.extra = None
@@ -111,7 +116,7 @@ class GraphedTrainStep:
         if self.mixup is not None:
             labels = self.loss_labels
             if torch.is_tensor(x):
-                ops.mixup_clips(x, self.mix_record)      # in place; a U8Clips is mixed by its im2col instead
+                ops.mixup_clips(x, self.mix_record)      # in place; a U8Clips / AugClips is mixed by its im2col instead
         eng.refresh_weights()
         flat.grad.zero_()
         ds = core.sample_drop_scales(x.shape[0], x.device, Tx=Tx)      # (+ the head's dropout factors: one launch)

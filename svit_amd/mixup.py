@@ -171,12 +171,13 @@ class MixUp:
 
     def mix(self, x, labels, record=None):
         """The fused route: uploads the record (drawn now unless given), mixes an fp32 clip tensor in place -- or tags a
-        U8Clips, whose im2col then mixes between normalisation and bf16 rounding -- and returns (x, MixedLabels)."""
+        U8Clips / AugClips, whose im2col then mixes between normalisation and bf16 rounding -- and returns (x, MixedLabels)."""
+        from .augment import AugClips
         from .input import U8Clips
         assert x.shape[0] > 1, "Batch size should be greater than 1 for mixup."
         rec = self.draw(x.shape) if record is None else record
         dev_rec = torch.from_numpy(rec.pack()).to(labels.device)
-        if isinstance(x, U8Clips):
+        if isinstance(x, (U8Clips, AugClips)):
             x.lut_f32                         # (built here, outside any capture)
             x.mix = dev_rec.to(x.device)
         else:

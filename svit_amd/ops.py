@@ -358,6 +358,46 @@ def im2col_patch_u8(clips):
     return cols, (To, Ho, Wo)
 
 
+def _chk_aug(clips):
+    """svit_amd.augment.AugClips: the frames, the int32 [B,16] record table and the fp32 table on one device"""
+    fr, rec, lut = clips.frames, clips.records, clips.lut_f32
+    _chk_dev(fr, rec, lut)
+    if rec.dtype != torch.int32 or rec.dim() != 2 or rec.shape[1] != 16 or not rec.is_contiguous() or rec.device != fr.device:
+        raise hip.SvitHipError("the augmentation records must be contiguous int32 [B,16] on %s (got %s %s on %s)"
+                               % (fr.device, rec.dtype, tuple(rec.shape), rec.device))
+    if lut.dtype != F32 or lut.numel() != 768 or lut.device != fr.device:
+        raise hip.SvitHipError("the normalisation table must be f32 [3,256] on %s" % (fr.device,))
+
+
+def im2col_patch_u8_aug(clips):
+    """svit_amd.augment.AugClips -> the same [rows, 448] bf16 operand as im2col_patch: resized crop, flip and erasing per
+    the device records (and the mix of `clips.mix`, when set) between the fp32 normalisation and the one bf16 rounding."""
+    _chk_aug(clips)
+    fr = clips.frames
+    V, T, Hs, Ws, _ = fr.shape
+    B, S = clips.records.shape[0], clips.size
+    To, Ho, Wo = (T - 1) // 2 + 1, (S - 1) // 4 + 1, (S - 1) // 4 + 1
+    cols = torch.empty((B * To * Ho * Wo, 448), device=fr.device, dtype=BF16)
+    mix = getattr(clips, "mix", None)
+    if mix is not None:
+        _chk_mix(mix, fr.device)
+    hip.call("svit_im2col_patch_u8_aug", ptr(fr), fr.numel(), ptr(clips.lut_f32), ptr(clips.records), ptr(mix),
+             ptr(cols), B, T, Hs, Ws, S)
+    return cols, (To, Ho, Wo)
+
+
+def u8_clips_render(clips):
+    """svit_amd.augment.AugClips -> f32 [B,3,T,S,S]: the values im2col_patch_u8_aug rounds, unrounded (no mix)"""
+    _chk_aug(clips)
+    fr = clips.frames
+    V, T, Hs, Ws, _ = fr.shape
+    B, S = clips.records.shape[0], clips.size
+    out = torch.empty((B, 3, T, S, S), device=fr.device, dtype=F32)
+    hip.call("svit_u8_clips_render", ptr(fr), fr.numel(), ptr(clips.lut_f32), ptr(clips.records), ptr(out),
+             B, T, Hs, Ws, S)
+    return out
+
+
 def _chk_mix(mix, device):
     """the 32-byte mix record (include/svit_hip.h, svit_mixup_clips): int32 [8] on the device of the data"""
     _chk_dev(mix)
