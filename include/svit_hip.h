@@ -224,6 +224,36 @@ int svit_im2col_patch_u8_aug(const uint8_t* frames, int64_t frames_bytes, const 
                              const void* mix, void* cols, int B, int T, int Hs, int Ws, int S, void* stream);
 int svit_u8_clips_render(const uint8_t* frames, int64_t frames_bytes, const float* lut_f32, const void* aug,
                          float* out_f32, int B, int T, int Hs, int Ws, int S, void* stream);
+/* RandAugment on the uint8 frames (cfg.AUG.AA_TYPE / INTERPOLATION; svit_amd/randaug.py, csrc/randaug.hip): the reference's
+ * `create_random_augment` (slowfast/datasets/ssv2.py:345-375, rand_augment.py) -- N PIL operations per clip on every frame
+ * at source resolution, before normalisation -- with PIL's bytes.  frames u8 [V,T,Hs,Ws,3]; `records` is the table
+ * SvitRandAugOp [V,N] in DEVICE memory (8-byte aligned), read at run time, so one captured step serves every draw.  The
+ * same operation and arguments apply to every frame of a video; statistics are per frame.
+ *   op            0 NONE, 1 AUTOCONTRAST, 2 EQUALIZE, 3 INVERT, 4 POSTERIZE, 5 SOLARIZE, 6 SOLARIZE_ADD, 7 COLOR, 8 CONTRAST,
+ *                 9 BRIGHTNESS, 10 SHARPNESS, 11 AFFINE; anything else is NONE
+ *   arg_i         bits kept (POSTERIZE; >= 8 is the identity), threshold 0..256 (SOLARIZE), addend (SOLARIZE_ADD, below 128)
+ *   arg_f         the enhancement factor (ops 7-10): out = degenerate + arg_f * (source - degenerate) in fp32, product and
+ *                 sum rounded separately; truncated for 0 <= arg_f <= 1, else clipped to [0, 255] and truncated
+ *   bicubic_mask  AFFINE: bit (t mod 32) set = frame t is resampled bicubically, clear = bilinearly
+ *   m[6]          AFFINE: the output -> input map, xo = m0*(x+.5) + m1*(y+.5) + m2, yo = m3*(x+.5) + m4*(y+.5) + m5 in fp64
+ *                 without contraction; a pixel outside 0 <= xo < Ws, 0 <= yo < Hs (or NaN) is the fill (128,128,128);
+ *                 the filters are ImagingGenericTransform's, every tap index clamped into the frame
+ * svit_randaug_stats: one block per (video, frame); returns at once unless the video's op in `layer` is AUTOCONTRAST,
+ * EQUALIZE or CONTRAST, else builds the frame's 3 x 256 histogram in LDS (integer counts: order-independent) and writes
+ * the 1 KiB slot of that frame in `workspace` (V*T KiB, 4-byte aligned): bytes 0..767 the per-channel table, int32 at
+ * byte 768 the Contrast mean.  svit_randaug_apply: layer `layer` of every video from src to dst (same shape, src != dst),
+ * EVERY byte of dst written (NONE is a copy).  Both are stream-ordered with no host synchronisation; no record can make
+ * either address outside its buffers.  Hs, Ws >= 3. */
+typedef struct SvitRandAugOp {
+  int32_t op, arg_i;
+  float arg_f;
+  uint32_t bicubic_mask;
+  double m[6];
+} SvitRandAugOp;
+int svit_randaug_stats(const uint8_t* frames, const void* records, int layer, void* workspace, int V, int T, int Hs,
+                       int Ws, int N, void* stream);
+int svit_randaug_apply(const uint8_t* src, uint8_t* dst, const void* records, int layer, const void* workspace, int V,
+                       int T, int Hs, int Ws, int N, void* stream);
 /* cls / object token rows of the block-0 input (video_model_builder.py:326-363). */
 int svit_fill_special_tokens(float* x, const float* cls, const float* objq, const float* pos_t,
                              int B, int N, int L, int Tx, int O, int C, int add_pos, void* stream);

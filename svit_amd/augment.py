@@ -32,9 +32,12 @@ Where the reference itself fails, `draw` raises or does the evident thing: a res
 makes the reference's `random_crop` return a bare tensor that `spatial_sampling` cannot unpack -- here the offsets are 0
 and nothing is drawn; a rescaled side SHORTER than the crop (a crop of the wrong size there) raises.
 
-Out of scope: RandAugment / colour jitter (uint8 PIL operations on the host, before this pipeline: feed their output as
-`frames`), DATA.TRAIN_JITTER_MOTION_SHIFT, boxes, the image ranks, AUG.RE_COUNT > 1, bicubic resampling, and the frames
-pass of GraphedTrainStep on an `AugClips` (use `render()` and the fp32 route).
+RandAugment (cfg.AUG.AA_TYPE, the stage BEFORE this pipeline) runs on the device as well: `AugClips(..., randaug=table)`
+with the table of svit_amd/randaug.py keeps the raw frames and runs the chain raw -> `frames` ahead of every read.
+
+Out of scope: colour jitter (AUG.COLOR_JITTER, which the reference's loader never reads), DATA.TRAIN_JITTER_MOTION_SHIFT,
+boxes, the image ranks, AUG.RE_COUNT > 1, bicubic resampling, and the frames pass of GraphedTrainStep on an `AugClips`
+(use `render()` and the fp32 route).
 """
 import collections
 import math
@@ -131,9 +134,14 @@ def clamp_records(table, V, Hs, Ws, S):
 class AugClips:
     """B augmented clips over V uint8 videos: `frames` u8 [V,T,Hs,Ws,3] on the GPU, `size` = S, `records` a list of
     AugRecord (or an int32 [B,16] table).  Quacks like `input.U8Clips` where the model and GraphedTrainStep look at it;
-    `mix` (the device mix record of svit_amd/mixup.py) is set by MixUp.mix / GraphedTrainStep."""
+    `mix` (the device mix record of svit_amd/mixup.py) is set by MixUp.mix / GraphedTrainStep.
+    randaug: the int32 [V,N,16] table of svit_amd/randaug.py (`pack_table`) -- the object then keeps the frames it was
+    given as `raw` (never written), the table in device memory and one scratch buffer, and `frames` becomes the chain's
+    output: ops.im2col_patch_u8_aug / ops.u8_clips_render launch the 2N kernels raw -> frames first, eager and inside a
+    captured step alike.  None: the same launches and bytes as ever."""
 
-    def __init__(self, frames, size, records, mean=(0.45, 0.45, 0.45), std=(0.225, 0.225, 0.225), lut_f32=None):
+    def __init__(self, frames, size, records, mean=(0.45, 0.45, 0.45), std=(0.225, 0.225, 0.225), lut_f32=None,
+                 randaug=None):
         if frames.dtype != torch.uint8 or frames.dim() != 5 or frames.shape[-1] != 3:
             raise ValueError("frames must be uint8 [V,T,H,W,3], got %s %s" % (frames.dtype, tuple(frames.shape)))
         if not frames.is_cuda:
@@ -150,6 +158,27 @@ class AugClips:
         # the fp32 table is built here, outside any capture
         self.lut_f32 = normalize_lut_f32(mean, std, frames.device) if lut_f32 is None else lut_f32
         self.mix = None
+        self.raw = self.ra_table = self.ra_tmp = self.ra_ws = None
+        if randaug is not None:
+            from . import randaug as ra
+            table = self._pack_randaug(randaug)
+            self.raw, self.frames = self.frames, torch.empty_like(self.frames)
+            self.ra_table = table.to(frames.device)
+            self.ra_tmp = torch.empty_like(self.frames) if table.shape[1] > 1 else None
+            self.ra_ws = torch.empty(ra.workspace_bytes(V, T), dtype=torch.uint8, device=frames.device)
+
+    def _pack_randaug(self, table):
+        from . import randaug as ra
+        t = table.to(torch.int32).contiguous() if torch.is_tensor(table) else torch.from_numpy(ra.pack_table(table))
+        if t.dim() != 3 or t.shape[0] != self.frames.shape[0] or t.shape[1] < 1 or t.shape[2] != 16:
+            raise ValueError("the RandAugment table is int32 [%d,N,16], got %s" % (self.frames.shape[0], tuple(t.shape)))
+        return t
+
+    def run_randaug(self):
+        """raw -> frames through the table's N layers (2N launches on the current stream); nothing without a table"""
+        if self.ra_table is not None:
+            from . import randaug as ra
+            ra.apply(self.raw, self.ra_table, self.frames, self.ra_tmp, self.ra_ws)
 
     # ---- the parts of the tensor interface the model path touches ---------------------------
     @property
@@ -164,7 +193,7 @@ class AugClips:
         return 5
 
     def data_ptr(self):
-        return self.frames.data_ptr()
+        return (self.frames if self.raw is None else self.raw).data_ptr()
 
     def detach(self):
         return self
@@ -173,12 +202,31 @@ class AugClips:
         return self
 
     def clone(self):
+        if self.raw is not None:
+            return AugClips(self.raw.clone(), self.size, self.records.clone(), mean=self.mean, std=self.std,
+                            lut_f32=self.lut_f32, randaug=self.ra_table.clone())
         return AugClips(self.frames.clone(), self.size, self.records.clone(), mean=self.mean, std=self.std,
                         lut_f32=self.lut_f32)
 
     def copy_(self, other, non_blocking=False):
-        self.frames.copy_(other.frames, non_blocking=non_blocking)
+        if (self.raw is None) != (other.raw is None) or (self.raw is not None and self.ra_table.shape != other.ra_table.shape):
+            raise ValueError("copy_ between AugClips with and without RandAugment, or with tables of different shapes")
+        if self.raw is not None:
+            self.raw.copy_(other.raw, non_blocking=non_blocking)
+            self.ra_table.copy_(other.ra_table, non_blocking=non_blocking)
+        else:
+            self.frames.copy_(other.frames, non_blocking=non_blocking)
         self.records.copy_(other.records, non_blocking=non_blocking)
+        return self
+
+    def set_randaug(self, table):
+        """rewrite the RandAugment table in place (same [V,N,16]; the kernels clamp whatever it holds)"""
+        if self.raw is None:
+            raise ValueError("this AugClips was built without RandAugment")
+        t = self._pack_randaug(table)
+        if t.shape != self.ra_table.shape:
+            raise ValueError("the RandAugment table is int32 %s, got %s" % (tuple(self.ra_table.shape), tuple(t.shape)))
+        self.ra_table.copy_(t, non_blocking=True)
         return self
 
     def set_records(self, records, validate=True):

@@ -17,7 +17,7 @@ CSRC = os.path.join(HERE, "csrc")
 OUT_DIR = os.path.join(HERE, "lib")
 LIB = os.path.join(OUT_DIR, "libsvit_hip.so")
 SOURCES = ["gemm_nt.hip", "gemm_tn.hip", "norm.hip", "misc.hip", "pool.hip", "attn_fwd.hip", "attn_bwd.hip",
-           "loss.hip", "meter.hip", "input.hip", "head.hip"]
+           "loss.hip", "meter.hip", "input.hip", "head.hip", "randaug.hip"]
 HEADERS = ["common.h", "attn_common.h", "gemm_epilogue.h", os.path.join("..", "..", "include", "svit_hip.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -fno-slp-vectorize: hipcc's SLP pass packs adjacent fp32 multiplies / adds into v_pk_*_f32.  The
@@ -31,7 +31,15 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # such an instruction.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-ffast-math",
          "-fno-finite-math-only", "-fno-slp-vectorize", "-Wno-unused-result"]
+# per-source changes to FLAGS.  randaug.hip must give PIL's bytes: its fp32 / fp64 products and sums are rounded one by
+# one, and under -ffast-math the backend fuses them whatever the source says (csrc/input.hip, mix_blend).
+SOURCE_FLAGS = {"randaug.hip": {"remove": ["-ffast-math"], "add": ["-ffp-contract=off"]}}
 TMP_DIR = os.path.join(OUT_DIR, "tmp")
+
+
+def flags_for(src):
+    change = SOURCE_FLAGS.get(src, {})
+    return [f for f in FLAGS if f not in change.get("remove", ())] + list(change.get("add", ()))
 
 
 _PK = re.compile(r"\s*(v_pk_(?:mul|add|fma)_f32)\s+v\[(\d+):\d+\],\s*(.*)")
@@ -129,7 +137,7 @@ def _compile(src):
     if _newer(obj, deps + [os.path.abspath(__file__)]):
         # -save-temps keeps the device assembly next to a scratch object for check_isa()
         tmp_obj = os.path.join(TMP_DIR, src.replace(".hip", ".o"))
-        cmd = [HIPCC] + FLAGS + ["-save-temps=obj", "-c", os.path.join(CSRC, src), "-o", tmp_obj]
+        cmd = [HIPCC] + flags_for(src) + ["-save-temps=obj", "-c", os.path.join(CSRC, src), "-o", tmp_obj]
         r = subprocess.run(cmd, capture_output=True, text=True, cwd=TMP_DIR)
         if r.returncode != 0:
             raise RuntimeError("hipcc failed for %s:\n%s" % (src, r.stderr))

@@ -160,6 +160,8 @@ _SIGS = {
     "svit_im2col_patch_u8_aug": (i32, [vp, i64, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     "svit_u8_clips_render": (i32, [vp, i64, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     "svit_mixup_clips": (i32, [vp, vp, i32, i32, i32, i32, vp]),
+    "svit_randaug_stats": (i32, [vp, vp, i32, vp, i32, i32, i32, i32, i32, vp]),
+    "svit_randaug_apply": (i32, [vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, vp]),
     "svit_fill_special_tokens": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
     "svit_special_token_grads": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
     "svit_pool_ln_fwd": (i32, [C.POINTER(PoolArgs), vp]),

@@ -373,6 +373,7 @@ def im2col_patch_u8_aug(clips):
     """svit_amd.augment.AugClips -> the same [rows, 448] bf16 operand as im2col_patch: resized crop, flip and erasing per
     the device records (and the mix of `clips.mix`, when set) between the fp32 normalisation and the one bf16 rounding."""
     _chk_aug(clips)
+    clips.run_randaug()         # (cfg.AUG.AA_TYPE: raw -> frames on this stream first; nothing without a table)
     fr = clips.frames
     V, T, Hs, Ws, _ = fr.shape
     B, S = clips.records.shape[0], clips.size
@@ -389,6 +390,7 @@ def im2col_patch_u8_aug(clips):
 def u8_clips_render(clips):
     """svit_amd.augment.AugClips -> f32 [B,3,T,S,S]: the values im2col_patch_u8_aug rounds, unrounded (no mix)"""
     _chk_aug(clips)
+    clips.run_randaug()
     fr = clips.frames
     V, T, Hs, Ws, _ = fr.shape
     B, S = clips.records.shape[0], clips.size
