@@ -219,9 +219,19 @@ int svit_im2col_patch_u8_mix(const uint8_t* frames, int64_t frames_bytes, const 
  * `mix` (NULL or the record of svit_mixup_clips) blends / swaps clip b with clip B-1-b -- sampled through ITS record at
  * the same (t, y, x) -- before the rounding, as svit_im2col_patch_u8_mix does.  With in == out, no flip and no erase the
  * bytes are those of svit_im2col_patch_u8 (_mix) with the crop table (video, i + oy, j + ox).  S need not fit the frames.
- * svit_u8_clips_render: the same values unrounded, out f32 [B,3,T,S,S]. */
+ * svit_u8_clips_render: the same values unrounded, out f32 [B,3,T,S,S].
+ * svit_im2col_patch_u8_aug_frames: the operand of the FRAMES PASS (the no-grad forward of every clip as B*T single
+ * frames, tools/train_net.py:105-110) from the same frames and records: cols bf16 [B*T*S'*S', 448], what
+ * svit_im2col_patch gives for the fp32 tensor [B*T,3,1,S,S] whose frame n = b*T + t is frame t of clip b (T' = 1: the
+ * temporal taps kt = 0 and kt = 2 are padding and zero, kt = 1 holds the frame).  Every pixel is evaluated with the
+ * clip's own (b, t, T), so the erase noise is the clip pass's; with `mix` the partner of frame (b, t) is frame (B-1-b, t)
+ * through that clip's record, mixed before the one rounding.  For T = 1 the bytes are svit_im2col_patch_u8_aug's.  Same
+ * clamping and the same argument checks as svit_im2col_patch_u8_aug (cols 16-byte aligned, B*T*S' below 2^31), all made
+ * before the launch. */
 int svit_im2col_patch_u8_aug(const uint8_t* frames, int64_t frames_bytes, const float* lut_f32, const void* aug,
                              const void* mix, void* cols, int B, int T, int Hs, int Ws, int S, void* stream);
+int svit_im2col_patch_u8_aug_frames(const uint8_t* frames, int64_t frames_bytes, const float* lut_f32, const void* aug,
+                                    const void* mix, void* cols, int B, int T, int Hs, int Ws, int S, void* stream);
 int svit_u8_clips_render(const uint8_t* frames, int64_t frames_bytes, const float* lut_f32, const void* aug,
                          float* out_f32, int B, int T, int Hs, int Ws, int S, void* stream);
 /* RandAugment on the uint8 frames (cfg.AUG.AA_TYPE / INTERPOLATION; svit_amd/randaug.py, csrc/randaug.hip): the reference's

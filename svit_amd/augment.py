@@ -36,8 +36,10 @@ RandAugment (cfg.AUG.AA_TYPE, the stage BEFORE this pipeline) runs on the device
 with the table of svit_amd/randaug.py keeps the raw frames and runs the chain raw -> `frames` ahead of every read.
 
 Out of scope: colour jitter (AUG.COLOR_JITTER, which the reference's loader never reads), DATA.TRAIN_JITTER_MOTION_SHIFT,
-boxes, the image ranks, AUG.RE_COUNT > 1, bicubic resampling, and the frames pass of GraphedTrainStep on an `AugClips`
-(use `render()` and the fp32 route).
+boxes, the image ranks, AUG.RE_COUNT > 1 and bicubic resampling.  The reference's frames pass reads the same frames and
+records: `input.FramesView(clips)` is the B*T frames as single-frame clips (`svit_im2col_patch_u8_aug_frames`; frame
+(b, t) through clip b's record, erase noise and mix partner included) and `GraphedTrainStep(..., frames_pass="u8")` runs
+it inside the replayed step; `frames_pass=True` stays the fp32 route and refuses an `AugClips`.
 """
 import collections
 import math

@@ -277,7 +277,8 @@ __global__ __launch_bounds__(256) void im2col_patch_u8_mix_kernel(
 // 596-683), horizontal flip (transform.py:248-285) and random erasing of a cube (datasets/random_erasing.py) -- as a
 // pure function of the output coordinate, driven by one 64-byte record per clip in device memory (SvitAug,
 // include/svit_hip.h).  `aug_pixel` below is that function; svit_u8_clips_render writes its fp32 values,
-// svit_im2col_patch_u8_aug rounds them once to bf16 while it assembles the patch-embedding operand.
+// svit_im2col_patch_u8_aug rounds them once to bf16 while it assembles the patch-embedding operand, and
+// svit_im2col_patch_u8_aug_frames does the same for the frames pass (every frame as a single-frame clip).
 struct SvitAug {
   int video, i, j, h, w, out_h, out_w, oy, ox, flip, erase_mode, et, el, eh, ew, seed;
 };
@@ -414,7 +415,17 @@ __global__ __launch_bounds__(256) void u8_clips_render_kernel(
 // 51.5 KB, three blocks per CU like the mix kernel) it is staged into LDS with aligned word loads -- every source byte
 // is then fetched from memory once per block instead of once per tap -- otherwise the taps are gathered from global
 // memory.  The mix partner (clip B-1-b through its own record) is always gathered: it is needed on mixing steps only.
+//
+// FRAMES = true is the frames pass (svit_im2col_patch_u8_aug_frames): the operand of the B*T single-frame clips
+// [B*T,3,1,S,S], frame n = b*T + t.  A block is (n, yo); To = 1, so of the 21 (kt, ky) lines only the seven kt = 1
+// lines hold a frame -- frame t of clip b, through aug_pixel with the clip's own (b, t, T), so geometry, erase noise and
+// mix partner (frame t of clip B-1-b) are the clip pass's -- and the other fourteen are the temporal padding: the image
+// is zeroed once and the fill writes the kt = 1 lines only.  One frame's rectangle is staged instead of three, within
+// AUG_STAGE_FRAMES = AUG_STAGE / 3: the rectangle that fits is the one that fits the clip kernel, so a record takes the
+// same path in both passes, and img + tab + stage = 39.8 KB goes four times into a CU's 160 KB instead of three (the
+// block fills a third of the clip kernel's pixels and stores as much: more resident waves behind the stores).
 constexpr int AUG_STAGE = 16384;
+constexpr int AUG_STAGE_FRAMES = 5460;
 
 // taps from the staged rectangle: row (kt, r) starts at the byte its global address has modulo 4, so the staging
 // copies whole words
@@ -430,17 +441,23 @@ struct AugStageFetch {
   }
 };
 
+template <bool FRAMES>
 __global__ __launch_bounds__(256) void im2col_patch_u8_aug_kernel(
     const uint8_t* __restrict__ frames, int64_t frames_bytes, const float* __restrict__ lut,
     const SvitAug* __restrict__ aug, const SvitMix* __restrict__ mix, bf16_t* __restrict__ cols,
     int B, int T, int Hs, int Ws, int S, int To, int Ho, int Wo) {
+  constexpr int KT = FRAMES ? 1 : 3;             // frames a block reads
+  constexpr int LINE0 = FRAMES ? 7 : 0;          // first (kt, ky) line the fill writes, KT * 7 of them
+  constexpr int STAGE = FRAMES ? AUG_STAGE_FRAMES : AUG_STAGE;
   __shared__ bf16_t img[63][COLS + 4];  // [(c*3+kt)*7+ky][x - x_start], augmented + mixed + rounded, 0 = padding
   __shared__ float tab[768];
-  __shared__ uint32_t stage[AUG_STAGE / 4];
+  __shared__ uint32_t stage[STAGE / 4];
   SvitMix m = {0, 1.f, 0.f, 0, 0, 0, 0, 0};
   if (mix) m = *mix;
   const bool mixing = m.mode == 1 || m.mode == 2;
-  const int yo = blockIdx.x % Ho, to = (blockIdx.x / Ho) % To, b = blockIdx.x / (Ho * To);
+  // clip n = b*To + to of the output (FRAMES: To = 1 and n = b*T + t, one single-frame clip per frame)
+  const int yo = blockIdx.x % Ho, n = blockIdx.x / Ho;
+  const int b = FRAMES ? n / T : n / To;
   const int pb = B - 1 - b;
   const int64_t n_videos = frames_bytes / ((int64_t)T * Hs * Ws * 3);
   const AugGeom g = aug_geom(aug, b, n_videos, T, Hs, Ws, S);
@@ -448,8 +465,11 @@ __global__ __launch_bounds__(256) void im2col_patch_u8_aug_kernel(
   const AugGlobalFetch gfetch{frames, g.vbase, Hs, Ws, g.i, g.j};
   const AugGlobalFetch gfetch2{frames, g2.vbase, Hs, Ws, g2.i, g2.j};
   for (int i = threadIdx.x; i < 768; i += 256) tab[i] = lut[i];
-  bf16_t* out = cols + (((int64_t)b * To + to) * Ho + yo) * Wo * 448;
-  const int t0 = to * 2 - 1, y0 = yo * 4 - 3;
+  if (FRAMES)                           // the kt = 0 and kt = 2 lines stay zero: no chunk writes them
+    for (int i = threadIdx.x; i < 63 * (COLS + 4) / 2; i += 256) ((uint32_t*)img)[i] = 0u;
+  bf16_t* out = cols + ((int64_t)n * Ho + yo) * Wo * 448;
+  // tap kt is frame t0 + kt (FRAMES: the one tap kt = 1 is frame n - b*T); the staged frames start at ts
+  const int t0 = FRAMES ? n - b * T - 1 : (n - b * To) * 2 - 1, ts = FRAMES ? t0 + 1 : t0, y0 = yo * 4 - 3;
   // the source rows of the block's output rows (the same for every chunk)
   const int ya = max(y0, 0), yb = min(y0 + 7, S);
   int r_lo, r_hi, tmp;
@@ -467,11 +487,11 @@ __global__ __launch_bounds__(256) void im2col_patch_u8_aug_kernel(
       aug_axis(g.ox + (g.flip ? S - 1 - xa : xb - 1), g.w, g.sx, tmp, c_hi, f0, f1);
     }
     const int rowbytes = (c_hi - c_lo + 1) * 3, pitch = (rowbytes + 6) & ~3;
-    const bool staged = xb > xa && (int64_t)3 * nrows * pitch <= AUG_STAGE;
+    const bool staged = xb > xa && (int64_t)KT * nrows * pitch <= STAGE;
     __syncthreads();                    // table ready / previous chunk's readers done
     if (staged) {
-      for (int kr = 0; kr < 3 * nrows; ++kr) {
-        const int kt = kr / nrows, r = r_lo + kr - kt * nrows, t = t0 + kt;
+      for (int kr = 0; kr < KT * nrows; ++kr) {
+        const int kt = kr / nrows, r = r_lo + kr - kt * nrows, t = ts + kt;
         if (t < 0 || t >= T) continue;                               // uniform over the block
         const int64_t base = g.vbase + (((int64_t)t * Hs + (g.i + r)) * Ws + (g.j + c_lo)) * 3;
         const int64_t a0 = base & ~(int64_t)3;                       // aligned 4-byte words
@@ -491,11 +511,11 @@ __global__ __launch_bounds__(256) void im2col_patch_u8_aug_kernel(
       }
       __syncthreads();
     }
-    const AugStageFetch sfetch{(const uint8_t*)stage, t0, r_lo, c_lo, nrows, pitch,
+    const AugStageFetch sfetch{(const uint8_t*)stage, ts, r_lo, c_lo, nrows, pitch,
                                (uint32_t)(g.vbase / ((int64_t)Ws * 3)) + (uint32_t)g.i, Hs, Ws, g.j + c_lo};
-    // every element of the 63 x COLS image is written here (0 outside the clip): no separate zero pass
-    for (int p = threadIdx.x; p < 21 * COLS; p += 256) {
-      const int line = p / COLS, px = p - line * COLS;
+    // every element of the KT * 7 lines is written here (0 outside the clip): no separate zero pass
+    for (int p = threadIdx.x; p < KT * 7 * COLS; p += 256) {
+      const int line = LINE0 + p / COLS, px = p - (line - LINE0) * COLS;
       const int ky = line % 7, kt = line / 7;
       const int t = t0 + kt, y = y0 + ky, x = x_start + px;
       float v[3] = {0.f, 0.f, 0.f};
@@ -601,9 +621,24 @@ extern "C" int svit_im2col_patch_u8_aug(const uint8_t* frames, int64_t frames_by
   if (((uintptr_t)mix & 3) || ((uintptr_t)cols & 15)) return SVIT_ERR_ALIGN;
   const int To = (T + 2 - 3) / 2 + 1, Ho = (S + 6 - 7) / 4 + 1, Wo = (S + 6 - 7) / 4 + 1;
   if ((int64_t)B * To * Ho > 0x7fffffff) return SVIT_ERR_SHAPE;
-  hipLaunchKernelGGL(im2col_patch_u8_aug_kernel, dim3((unsigned)(B * To * Ho)), dim3(256), 0,
+  hipLaunchKernelGGL(im2col_patch_u8_aug_kernel<false>, dim3((unsigned)(B * To * Ho)), dim3(256), 0,
                      (hipStream_t)stream, frames, frames_bytes, lut_f32, (const SvitAug*)aug, (const SvitMix*)mix,
                      (bf16_t*)cols, B, T, Hs, Ws, S, To, Ho, Wo);
+  SVIT_LAUNCH_CHECK();
+  return SVIT_OK;
+}
+
+extern "C" int svit_im2col_patch_u8_aug_frames(const uint8_t* frames, int64_t frames_bytes, const float* lut_f32,
+                                               const void* aug, const void* mix, void* cols, int B, int T, int Hs,
+                                               int Ws, int S, void* stream) {
+  const int rc = aug_args_ok(frames, frames_bytes, lut_f32, aug, cols, B, T, Hs, Ws, S);
+  if (rc != SVIT_OK) return rc;
+  if (((uintptr_t)mix & 3) || ((uintptr_t)cols & 15)) return SVIT_ERR_ALIGN;
+  const int Ho = (S + 6 - 7) / 4 + 1, Wo = (S + 6 - 7) / 4 + 1;
+  if ((int64_t)B * T * Ho > 0x7fffffff) return SVIT_ERR_SHAPE;
+  hipLaunchKernelGGL(im2col_patch_u8_aug_kernel<true>, dim3((unsigned)(B * T * Ho)), dim3(256), 0,
+                     (hipStream_t)stream, frames, frames_bytes, lut_f32, (const SvitAug*)aug, (const SvitMix*)mix,
+                     (bf16_t*)cols, B, T, Hs, Ws, S, 1, Ho, Wo);
   SVIT_LAUNCH_CHECK();
   return SVIT_OK;
 }

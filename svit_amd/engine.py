@@ -14,7 +14,7 @@ import torch
 
 from . import arch, hip, ops
 from .augment import AugClips
-from .input import U8Clips
+from .input import FramesView, U8Clips
 
 HD = arch.HEAD_DIM
 F32, BF16 = torch.float32, torch.bfloat16
@@ -333,7 +333,7 @@ class Engine:
 
     # ------------------------------------------------------------------ forward ----------
     def forward(self, video, drop_scales=None, save=True):
-        """video f32 [B,3,Tx,S,S] (or U8Clips / AugClips) -> (normed tokens f32 [B,N_last,C_last], saved-state dict)."""
+        """video f32 [B,3,Tx,S,S] (or U8Clips / AugClips / FramesView) -> (normed tokens f32 [B,N_last,C_last], saved-state dict)."""
         plan, f = self.plan, self.flat
         if isinstance(video, U8Clips):       # decoded uint8 frames + crop table (svit_amd/input.py)
             B, _, Tx = video.shape[:3]
@@ -341,6 +341,9 @@ class Engine:
         elif isinstance(video, AugClips):    # the same + one augmentation record per clip (svit_amd/augment.py)
             B, _, Tx = video.shape[:3]
             cols, (To, Ho, Wo) = ops.im2col_patch_u8_aug(video)
+        elif isinstance(video, FramesView):  # the frames of either as single-frame clips (the frames pass)
+            B, _, Tx = video.shape[:3]
+            cols, (To, Ho, Wo) = ops.im2col_patch_u8_aug_frames(video)
         else:
             if video.dim() == 4:
                 video = video.unsqueeze(2)

@@ -46,7 +46,11 @@ class GraphedTrainStep:
         replay time: `__call__` copies frames and table into the static ones).
         frames_pass: also run the reference's no-grad single-frame forward of every clip
         (tools/train_net.py:105-110) inside the graph; its outputs reach `loss_fun` as
-        extra["frames_output"] = {"preds", "extra_preds"} (the consistency-loss operand).
+        extra["frames_output"] = {"preds", "extra_preds"} (the consistency-loss operand).  True: the fp32 route (the
+        static input is the fp32 clip, permuted into B*T frames).  "u8": the static input is a U8Clips or an AugClips
+        and the pass runs on input.FramesView(static input, fresh=True) -- the frames operand is assembled from the
+        same uint8 frames and records (svit_im2col_patch_u8_aug_frames), no fp32 clip exists, the RandAugment chain of
+        an AugClips runs once per step (ahead of the clip forward) and under `mixup` the view sees the step's record.
         mixup: a mixup.MixUp (cfg.MIXUP; `mixup.build_mixup(cfg)`) -- the step then OWNS a 32-byte mix record in
         device memory; the captured body starts with the clip kernel on the static input (or tags a U8Clips, whose
         im2col mixes) and `loss_fun` receives mixup.MixedLabels over the static labels (int64 [B]) instead of the
@@ -83,8 +87,17 @@ class GraphedTrainStep:
                                                            getattr(model, "force_collectives", False)) else None
         self.x = inputs[0].detach().clone().contiguous()
         from .augment import AugClips
-        if frames_pass and isinstance(self.x, AugClips):
-            raise hip.SvitHipError("the frames pass does not take an AugClips: feed clips.render() (the fp32 route)")
+        from .input import U8Clips
+        if isinstance(frames_pass, str):
+            if frames_pass != "u8":
+                raise hip.SvitHipError("frames_pass is False, True or \"u8\", got %r" % (frames_pass,))
+            if not isinstance(self.x, (U8Clips, AugClips)):
+                raise hip.SvitHipError("frames_pass=\"u8\" reads the frames of a U8Clips or an AugClips; for the fp32 "
+                                       "clip tensor pass frames_pass=True")
+            self.x.lut_f32                    # (U8Clips: the fp32 table is built here, outside the capture)
+        elif frames_pass and isinstance(self.x, AugClips):
+            raise hip.SvitHipError("frames_pass=True is the fp32 route and does not take an AugClips: pass "
+                                   "frames_pass=\"u8\" (or feed clips.render())")
         self.labels = _tree_map(lambda t: t.detach().clone(), labels)
         self.mix_record = self.loss_labels = None
         if mixup is not None:
@@ -127,7 +140,11 @@ class GraphedTrainStep:
         frames_out = None
         if self.frames_pass and Tx > 1:
             with torch.no_grad():       # B*T single frames through the same kernels (T' = 1)
-                xf = x.transpose(1, 2).flatten(0, 1).unsqueeze(2)
+                if self.frames_pass == "u8":            # (the clip forward above has run the RandAugment chain)
+                    from .input import FramesView
+                    xf = FramesView(x, fresh=True)
+                else:
+                    xf = x.transpose(1, 2).flatten(0, 1).unsqueeze(2)
                 fy, _ = eng.forward(xf, core.sample_drop_scales(xf.shape[0], x.device), save=False)
                 ffeat = torch.cat((fy[:, :1], fy[:, -core.O:]), dim=1)
                 fp, fe = core.head(ffeat, T=1)

@@ -158,6 +158,7 @@ _SIGS = {
     "svit_im2col_patch_u8": (i32, [vp, i64, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     "svit_im2col_patch_u8_mix": (i32, [vp, i64, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     "svit_im2col_patch_u8_aug": (i32, [vp, i64, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
+    "svit_im2col_patch_u8_aug_frames": (i32, [vp, i64, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     "svit_u8_clips_render": (i32, [vp, i64, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     "svit_mixup_clips": (i32, [vp, vp, i32, i32, i32, i32, vp]),
     "svit_randaug_stats": (i32, [vp, vp, i32, vp, i32, i32, i32, i32, i32, vp]),

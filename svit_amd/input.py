@@ -6,7 +6,8 @@ keeps what the decoder produced -- uint8 `[V,T,Hs,Ws,3]` -- on the device and de
 clip as (source video, y0, x0) + size; normalisation, the T H W C -> C T H W permute and the crop
 (datasets/transform.py:288-348) happen inside the patch-embedding im2col
 (`svit_im2col_patch_u8`).  `model([clips], meta)` accepts it wherever it accepts the fp32 tensor;
-the numbers are bit-identical to feeding the reference-normalised fp32 crop.
+the numbers are bit-identical to feeding the reference-normalised fp32 crop.  `FramesView(clips)` is the
+same clips (or an `augment.AugClips`) as B*T single frames: the input of the reference's frames pass.
 """
 import torch
 
@@ -105,6 +106,61 @@ class U8Clips:
     def copy_(self, other, non_blocking=False):
         self.frames.copy_(other.frames, non_blocking=non_blocking)
         self.crops.copy_(other.crops, non_blocking=non_blocking)
+        return self
+
+
+def identity_records(crops, size):
+    """int32 [B,3] crop table (video, y0, x0) -> the int32 [B,16] augmentation records of the same integer crops
+    (`augment.AugRecord.identity` row by row: rectangle = window = size x size, nothing else), on the table's device:
+    three small launches, so a captured step rebuilds them from the table it finds at replay time."""
+    rec = torch.zeros((crops.shape[0], 16), dtype=torch.int32, device=crops.device)
+    rec[:, 0:3] = crops
+    rec[:, 3:7] = int(size)
+    return rec
+
+
+class FramesView:
+    """The B*T frames of a U8Clips or an augment.AugClips as single-frame clips -- the input of the reference's frames
+    pass (tools/train_net.py:105-110: `inputs[0].transpose(1, 2).flatten(0, 1).unsqueeze(2)`) without the fp32 clip.
+    Nothing is copied: the view reads the clips' `frames`, records (or crop table), `lut_f32` and `mix` when it is
+    used, and `svit_im2col_patch_u8_aug_frames` evaluates frame n = b*T + t with clip b's record (and, under a mix, the
+    partner clip's).  Quacks like the fp32 tensor [B*T,3,1,S,S] where the model path looks.
+    fresh: the caller promises that `clips.frames` already holds this step's RandAugment output (the clip forward of
+    the same step ran the chain), so `ops.im2col_patch_u8_aug_frames` does not run it again."""
+
+    def __init__(self, clips, fresh=False):
+        from .augment import AugClips
+        if not isinstance(clips, (U8Clips, AugClips)):
+            raise TypeError("FramesView takes a U8Clips or an AugClips, got %s" % type(clips).__name__)
+        self.clips = clips
+        self.fresh = bool(fresh)
+
+    frames = property(lambda self: self.clips.frames)
+    lut_f32 = property(lambda self: self.clips.lut_f32)
+    mix = property(lambda self: self.clips.mix)
+    size = property(lambda self: self.clips.size)
+
+    def device_records(self):
+        """the int32 [B,16] records the kernel reads: the AugClips' own table, or the identity records of the crop table"""
+        rec = getattr(self.clips, "records", None)
+        return identity_records(self.clips.crops, self.clips.size) if rec is None else rec
+
+    @property
+    def shape(self):
+        B, _, T, S, _ = self.clips.shape
+        return torch.Size((B * T, 3, 1, S, S))
+
+    @property
+    def device(self):
+        return self.clips.device
+
+    def dim(self):
+        return 5
+
+    def detach(self):
+        return self
+
+    def contiguous(self):
         return self
 
 

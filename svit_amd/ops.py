@@ -360,7 +360,10 @@ def im2col_patch_u8(clips):
 
 def _chk_aug(clips):
     """svit_amd.augment.AugClips: the frames, the int32 [B,16] record table and the fp32 table on one device"""
-    fr, rec, lut = clips.frames, clips.records, clips.lut_f32
+    _chk_aug_parts(clips.frames, clips.records, clips.lut_f32)
+
+
+def _chk_aug_parts(fr, rec, lut):
     _chk_dev(fr, rec, lut)
     if rec.dtype != torch.int32 or rec.dim() != 2 or rec.shape[1] != 16 or not rec.is_contiguous() or rec.device != fr.device:
         raise hip.SvitHipError("the augmentation records must be contiguous int32 [B,16] on %s (got %s %s on %s)"
@@ -385,6 +388,28 @@ def im2col_patch_u8_aug(clips):
     hip.call("svit_im2col_patch_u8_aug", ptr(fr), fr.numel(), ptr(clips.lut_f32), ptr(clips.records), ptr(mix),
              ptr(cols), B, T, Hs, Ws, S)
     return cols, (To, Ho, Wo)
+
+
+def im2col_patch_u8_aug_frames(view):
+    """svit_amd.input.FramesView -> the [B*T*Ho*Wo, 448] bf16 operand of im2col_patch for the B*T frames as single-frame
+    clips [B*T,3,1,S,S] (svit_im2col_patch_u8_aug_frames): frame b*T + t through clip b's record, mixed per `view.mix`.
+    An AugClips with a RandAugment table runs its chain first unless `view.fresh`; a U8Clips goes through the identity
+    records of its crop table."""
+    clips = view.clips
+    if not view.fresh and hasattr(clips, "run_randaug"):
+        clips.run_randaug()
+    fr, rec, lut = view.frames, view.device_records(), view.lut_f32
+    _chk_aug_parts(fr, rec, lut)
+    V, T, Hs, Ws, _ = fr.shape
+    B, S = rec.shape[0], view.size
+    Ho = Wo = (S - 1) // 4 + 1
+    cols = torch.empty((B * T * Ho * Wo, 448), device=fr.device, dtype=BF16)
+    mix = view.mix
+    if mix is not None:
+        _chk_mix(mix, fr.device)
+    hip.call("svit_im2col_patch_u8_aug_frames", ptr(fr), fr.numel(), ptr(lut), ptr(rec), ptr(mix), ptr(cols),
+             B, T, Hs, Ws, S)
+    return cols, (1, Ho, Wo)
 
 
 def u8_clips_render(clips):
