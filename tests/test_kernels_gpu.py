@@ -1,5 +1,8 @@
 """Per-kernel parity: every C-ABI entry point of libsvit_hip.so against fp32 math on the same
-inputs (the CPU oracle's functions where the op is SViT-specific).  Needs a real MI355X."""
+inputs (the CPU oracle's functions where the op is SViT-specific).  Needs a real MI355X.
+The NT GEMM's epilogues are also judged element by element against float64, on every store path and kernel form, in
+tests/test_gemm_parity_gpu.py (bars and mutants: tests/gemm_reference.py); the GEMM tests here keep their whole-tensor
+measure."""
 import math
 
 import numpy as np
