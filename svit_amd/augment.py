@@ -48,8 +48,7 @@ import random
 import numpy as np
 import torch
 
-from . import hip
-from .input import normalize_lut_f32
+from .input import U8Input, normalize_lut_f32
 
 ERASE_NONE, ERASE_CONST, ERASE_RAND, ERASE_PIXEL = 0, 1, 2, 3
 ERASE_MODES = {"": ERASE_CONST, "const": ERASE_CONST, "rand": ERASE_RAND, "pixel": ERASE_PIXEL}
@@ -133,7 +132,7 @@ def clamp_records(table, V, Hs, Ws, S):
     return torch.from_numpy(np.stack([f[n] for n in FIELDS.split()], axis=1).astype(np.int32))
 
 
-class AugClips:
+class AugClips(U8Input):
     """B augmented clips over V uint8 videos: `frames` u8 [V,T,Hs,Ws,3] on the GPU, `size` = S, `records` a list of
     AugRecord (or an int32 [B,16] table).  Quacks like `input.U8Clips` where the model and GraphedTrainStep look at it;
     `mix` (the device mix record of svit_amd/mixup.py) is set by MixUp.mix / GraphedTrainStep.
@@ -142,14 +141,11 @@ class AugClips:
     output: ops.im2col_patch_u8_aug / ops.u8_clips_render launch the 2N kernels raw -> frames first, eager and inside a
     captured step alike.  None: the same launches and bytes as ever."""
 
+    _rows = "records"
+
     def __init__(self, frames, size, records, mean=(0.45, 0.45, 0.45), std=(0.225, 0.225, 0.225), lut_f32=None,
                  randaug=None):
-        if frames.dtype != torch.uint8 or frames.dim() != 5 or frames.shape[-1] != 3:
-            raise ValueError("frames must be uint8 [V,T,H,W,3], got %s %s" % (frames.dtype, tuple(frames.shape)))
-        if not frames.is_cuda:
-            raise hip.SvitHipError("AugClips lives on the GPU (the host ships uint8, a quarter of the bytes)")
-        self.frames = frames.contiguous()
-        V, T, Hs, Ws, _ = frames.shape
+        V, T, Hs, Ws = self._take_frames(frames)
         self.size = int(size)
         if self.size < 1:
             raise ValueError("size must be positive")
@@ -182,26 +178,8 @@ class AugClips:
             from . import randaug as ra
             ra.apply(self.raw, self.ra_table, self.frames, self.ra_tmp, self.ra_ws)
 
-    # ---- the parts of the tensor interface the model path touches ---------------------------
-    @property
-    def shape(self):
-        return torch.Size((self.records.shape[0], 3, self.frames.shape[1], self.size, self.size))
-
-    @property
-    def device(self):
-        return self.frames.device
-
-    def dim(self):
-        return 5
-
     def data_ptr(self):
         return (self.frames if self.raw is None else self.raw).data_ptr()
-
-    def detach(self):
-        return self
-
-    def contiguous(self):
-        return self
 
     def clone(self):
         if self.raw is not None:

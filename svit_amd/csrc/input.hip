@@ -4,18 +4,33 @@
 // slowfast/datasets/utils.py:287-303), permutes T H W C -> C T H W, crops (transform.py:288-348)
 // and ships fp32 clips to the GPU (misc.iter_to_cuda, slowfast/utils/misc.py:374-387): 4 bytes
 // per sample over PCIe and HBM, plus a materialised copy per spatial crop.  Here the clip stays
-// uint8 [V,T,Hs,Ws,3] in HBM; normalisation is a 3 x 256-entry table (built with the reference's
-// own fp32 operation order, so the values are bit-identical), the crop is an (y0, x0) offset per
-// output clip, and both are applied while the im2col rows of Conv3d(3->96, k(3,7,7), s(2,4,4),
-// p(1,3,3)) (stem_helper.py:309-320) are assembled -- same [rows, 448] bf16 operand as
-// svit_im2col_patch, a quarter of the input bytes, no per-crop copy.
+// uint8 [V,T,Hs,Ws,3] in HBM and is normalised (a 3 x 256-entry table built with the reference's
+// own fp32 operation order, so the values are bit-identical), cropped, augmented and mixed while
+// the im2col rows of Conv3d(3->96, k(3,7,7), s(2,4,4), p(1,3,3)) (stem_helper.py:309-320) are
+// assembled -- same [rows, 448] bf16 operand as svit_im2col_patch, a quarter of the input bytes,
+// no per-crop copy.
 //
-// Mixup / CutMix (cfg.MIXUP; slowfast/datasets/mixup.py, tools/train_net.py:63-71,92-94) lives here too.
-// Every kernel of the feature reads ONE 32-byte record from device memory (SvitMix below), so a
-// captured step holds the same launches whatever was drawn for it: `svit_mixup_clips` blends /
-// swaps the fp32 clips of a batch in place against the batch reversed, and
-// `svit_im2col_patch_u8_mix` does the same on the uint8 route between the fp32 normalisation and
-// the bf16 rounding (uint8 frames cannot be blended in place without losing the fp32 arithmetic).
+// The skeleton, shared by the three im2col kernels: a block owns one output row (clip, to, yo) and
+// walks it in chunks of XO output positions.  Per chunk it FILLS the LDS image
+// img[(c*3+kt)*7+ky][x - x_start] -- the 21 (kt, ky) lines x 3 channels x COLS clip columns the
+// chunk's patches read, as bf16, 0 = padding -- and then STORES it (store_chunk): 56 uint4 per
+// output position.  Frame bytes come in aligned words through load_word, which alone knows about
+// the end of the buffer; walk_span hands a contiguous byte span out byte by byte.  What a fill does:
+//   svit_im2col_patch_u8       a line is one byte span of the clip's crop row (CropRow: video,
+//                              y0, x0); each byte goes through the bf16 table.
+//   svit_im2col_patch_u8_mix   Mixup / CutMix (cfg.MIXUP; slowfast/datasets/mixup.py,
+//                              tools/train_net.py:63-71,92-94) between the fp32 normalisation and
+//                              the bf16 rounding: the same span of the partner clip B-1-b is
+//                              dropped into LDS first, then the clip's own span is walked and
+//                              every byte blended with / replaced by the partner's.
+//   svit_im2col_patch_u8_aug[_frames]  every pixel of the lines is aug_pixel (resized crop, flip,
+//                              erasing per the clip's SvitAug record) of the clip, mixed with
+//                              aug_pixel of the partner; the taps come from a staged copy of the
+//                              source rectangle where it fits LDS.
+// Every kernel of the mix feature reads ONE 32-byte record from device memory (SvitMix below), so a
+// captured step holds the same launches whatever was drawn for it; `svit_mixup_clips` blends /
+// swaps the fp32 clips of a batch in place against the batch reversed (uint8 frames cannot be
+// blended in place without losing the fp32 arithmetic).
 #include "common.h"
 #include "../../include/svit_hip.h"
 
@@ -90,21 +105,90 @@ __global__ __launch_bounds__(256) void mixup_clips_kernel(float* __restrict__ x,
 constexpr int XO = 62;                  // output positions per chunk
 constexpr int COLS = XO * 4 + 4;        // clip columns held per chunk: x in [xc0*4 - 4, xc0*4 + 248)
 
+// the aligned word at byte `addr` of the frames; where the buffer ends inside it, the bytes that exist
+__device__ __forceinline__ uint32_t load_word(const uint8_t* __restrict__ frames, int64_t frames_bytes, int64_t addr) {
+  uint32_t word = 0;
+  if (addr + 4 <= frames_bytes) {
+    word = *(const uint32_t*)(frames + addr);
+  } else {                              // last bytes of the buffer
+    for (int k = 0; k < 4; ++k)
+      if (addr + k < frames_bytes) word |= (uint32_t)frames[addr + k] << (8 * k);
+  }
+  return word;
+}
+
+// The block walks the byte span [base, base + nbytes) of the frames in aligned 4-byte words, one word per thread and
+// turn: f(j, byte) for every byte 0 <= j < nbytes of the span, each exactly once over the block.
+template <class F>
+__device__ __forceinline__ void walk_span(const uint8_t* __restrict__ frames, int64_t frames_bytes, int64_t base,
+                                          int nbytes, const F& f) {
+  const int64_t a0 = base & ~(int64_t)3;
+  const int nwords = (int)((base + nbytes - a0 + 3) >> 2);
+  for (int w = threadIdx.x; w < nwords; w += 256) {
+    const int64_t addr = a0 + 4 * (int64_t)w;
+    const uint32_t word = load_word(frames, frames_bytes, addr);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int j = (int)(addr + k - base);
+      if (j < 0 || j >= nbytes) continue;
+      f(j, (word >> (8 * k)) & 255u);
+    }
+  }
+}
+
+__device__ __forceinline__ void zero_image(bf16_t (*img)[COLS + 4]) {
+  for (int i = threadIdx.x; i < 63 * (COLS + 4) / 2; i += 256) ((uint32_t*)img)[i] = 0u;
+}
+
+// the store phase: the image of the chunk that starts at output position xc0 -> 56 uint4 per position of the output
+// row `out` (441 patch elements + 7 zeros; element (r, kx) of position xl is img[r][xl*4 + 1 + kx], x = xo*4 - 3 + kx)
+__device__ __forceinline__ void store_chunk(const bf16_t (*img)[COLS + 4], bf16_t* __restrict__ out, int xc0, int Wo) {
+  const int n_xo = min(XO, Wo - xc0);
+  for (int i = threadIdx.x; i < n_xo * 56; i += 256) {
+    const int xl = i / 56, chunk = i % 56;
+    bf16_t e8[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const int col = chunk * 8 + e;
+      const int kx = col % 7, r = col / 7;
+      e8[e] = col < 441 ? img[r][xl * 4 + 1 + kx] : (bf16_t)0;
+    }
+    uint4 o;
+    o.x = (uint32_t)e8[0] | ((uint32_t)e8[1] << 16); o.y = (uint32_t)e8[2] | ((uint32_t)e8[3] << 16);
+    o.z = (uint32_t)e8[4] | ((uint32_t)e8[5] << 16); o.w = (uint32_t)e8[6] | ((uint32_t)e8[7] << 16);
+    ((uint4*)out)[(size_t)(xc0 + xl) * 56 + chunk] = o;
+  }
+}
+
+// Row b of the crop table (video, y0, x0); a null table is the identity (clip b = video b, no offset).  The host
+// validates the table when it is built (svit_amd/input.py); a table rewritten on the device later is clamped into the
+// frames here, so no entry can address outside them.
+struct CropRow {
+  int v, y0, x0;
+  // byte offset of pixel (t, y, x) of the crop
+  __device__ __forceinline__ int64_t byte_of(int T, int Hs, int Ws, int t, int y, int x) const {
+    return ((((int64_t)v * T + t) * Hs + (y0 + y)) * Ws + (x0 + x)) * 3;
+  }
+};
+
+__device__ __forceinline__ CropRow crop_row(const int32_t* __restrict__ crops, int b, int64_t frames_bytes, int T, int Hs,
+                                            int Ws, int S) {
+  const int64_t n_videos = frames_bytes / ((int64_t)T * Hs * Ws * 3);
+  CropRow r = {crops ? crops[b * 3] : b, crops ? crops[b * 3 + 1] : 0, crops ? crops[b * 3 + 2] : 0};
+  r.v = max(0, min(r.v, (int)n_videos - 1));
+  r.y0 = max(0, min(r.y0, Hs - S));
+  r.x0 = max(0, min(r.x0, Ws - S));
+  return r;
+}
+
 __global__ __launch_bounds__(256) void im2col_patch_u8_kernel(
     const uint8_t* __restrict__ frames, int64_t frames_bytes, const bf16_t* __restrict__ lut,
     const int32_t* __restrict__ crops, bf16_t* __restrict__ cols, int T, int Hs, int Ws, int S,
     int To, int Ho, int Wo) {
-  __shared__ bf16_t img[63][COLS + 4];  // [(c*3+kt)*7+ky][x - x_start], normalised, 0 = padding
+  __shared__ bf16_t img[63][COLS + 4];  // normalised
   __shared__ bf16_t tab[768];
   const int yo = blockIdx.x % Ho, to = (blockIdx.x / Ho) % To, b = blockIdx.x / (Ho * To);
-  // the host validates the crop table when it is built (svit_amd/input.py); a table rewritten
-  // on the device later is clamped into the frames here, so no entry can address outside them
-  int v = crops ? crops[b * 3] : b, y0 = crops ? crops[b * 3 + 1] : 0,
-      x0 = crops ? crops[b * 3 + 2] : 0;
-  const int64_t n_videos = frames_bytes / ((int64_t)T * Hs * Ws * 3);
-  v = max(0, min(v, (int)n_videos - 1));
-  y0 = max(0, min(y0, Hs - S));
-  x0 = max(0, min(x0, Ws - S));
+  const CropRow crop = crop_row(crops, b, frames_bytes, T, Hs, Ws, S);
   for (int i = threadIdx.x; i < 768; i += 256) tab[i] = lut[i];
   bf16_t* out = cols + (((int64_t)b * To + to) * Ho + yo) * Wo * 448;
   for (int xc0 = 0; xc0 < Wo; xc0 += XO) {
@@ -112,7 +196,7 @@ __global__ __launch_bounds__(256) void im2col_patch_u8_kernel(
     __syncthreads();                    // table ready / previous chunk's readers done
     // zero the image (padding), then drop the in-frame bytes of each (kt, ky) line: the three
     // channels of a pixel are adjacent bytes, so a line is one contiguous span of COLS*3 bytes
-    for (int i = threadIdx.x; i < 63 * (COLS + 4) / 2; i += 256) ((uint32_t*)img)[i] = 0u;
+    zero_image(img);
     __syncthreads();
     for (int line = 0; line < 21; ++line) {
       const int ky = line % 7, kt = line / 7;
@@ -120,71 +204,32 @@ __global__ __launch_bounds__(256) void im2col_patch_u8_kernel(
       if (t < 0 || t >= T || y < 0 || y >= S) continue;          // uniform over the block
       const int xa = max(x_start, 0), xb = min(x_start + COLS, S);   // clip columns in the frame
       if (xb <= xa) continue;
-      const int64_t base = ((((int64_t)v * T + t) * Hs + (y0 + y)) * Ws + (x0 + xa)) * 3;
-      const int nbytes = (xb - xa) * 3;
-      const int64_t a0 = base & ~(int64_t)3;                       // aligned 4-byte words
-      const int nwords = (int)((base + nbytes - a0 + 3) >> 2);
-      for (int w = threadIdx.x; w < nwords; w += 256) {
-        const int64_t addr = a0 + 4 * (int64_t)w;
-        uint32_t word = 0;
-        if (addr + 4 <= frames_bytes) {
-          word = *(const uint32_t*)(frames + addr);
-        } else {                                                    // last bytes of the buffer
-          for (int k = 0; k < 4; ++k)
-            if (addr + k < frames_bytes) word |= (uint32_t)frames[addr + k] << (8 * k);
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const int j = (int)(addr + k - base);                    // byte index inside the span
-          if (j < 0 || j >= nbytes) continue;
-          const int px = j / 3, c = j - px * 3;
-          img[(c * 3 + kt) * 7 + ky][xa - x_start + px] = tab[c * 256 + ((word >> (8 * k)) & 255u)];
-        }
-      }
+      walk_span(frames, frames_bytes, crop.byte_of(T, Hs, Ws, t, y, xa), (xb - xa) * 3, [&](int j, uint32_t byte) {
+        const int px = j / 3, c = j - px * 3;
+        img[(c * 3 + kt) * 7 + ky][xa - x_start + px] = tab[c * 256 + byte];
+      });
     }
     __syncthreads();
-    const int n_xo = min(XO, Wo - xc0);
-    for (int i = threadIdx.x; i < n_xo * 56; i += 256) {
-      const int xl = i / 56, chunk = i % 56;
-      bf16_t e8[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const int col = chunk * 8 + e;
-        const int kx = col % 7, r = col / 7;
-        e8[e] = col < 441 ? img[r][xl * 4 + 1 + kx] : (bf16_t)0;   // x = xo*4 - 3 + kx
-      }
-      uint4 o;
-      o.x = (uint32_t)e8[0] | ((uint32_t)e8[1] << 16); o.y = (uint32_t)e8[2] | ((uint32_t)e8[3] << 16);
-      o.z = (uint32_t)e8[4] | ((uint32_t)e8[5] << 16); o.w = (uint32_t)e8[6] | ((uint32_t)e8[7] << 16);
-      ((uint4*)out)[(size_t)(xc0 + xl) * 56 + chunk] = o;
-    }
+    store_chunk(img, out, xc0, Wo);
   }
 }
-// svit_im2col_patch_u8 with the mix between the normalisation and the bf16 rounding.  The partner
-// of clip b is clip B-1-b, read through ITS crop row at the same (t, y, x) of the crop; its byte
-// span has its own alignment (other x0, other base & 3), so phase A drops the partner's raw bytes
-// of all 21 lines into LDS indexed by the byte position inside the span -- which is the same for
-// both clips -- and phase B walks the clip's own words as the plain kernel does.
+
+// The partner of clip b is clip B-1-b, read through ITS crop row at the same (t, y, x) of the crop; its byte span has
+// its own alignment (other x0, other base & 3), so phase A drops the partner's raw bytes of all 21 lines into LDS
+// indexed by the byte position inside the span -- which is the same for both clips -- and phase B walks the clip's own
+// words as the plain kernel does.
 __global__ __launch_bounds__(256) void im2col_patch_u8_mix_kernel(
     const uint8_t* __restrict__ frames, int64_t frames_bytes, const float* __restrict__ lut,
     const int32_t* __restrict__ crops, const SvitMix* __restrict__ mix, bf16_t* __restrict__ cols,
     int B, int T, int Hs, int Ws, int S, int To, int Ho, int Wo) {
-  __shared__ bf16_t img[63][COLS + 4];  // [(c*3+kt)*7+ky][x - x_start], mixed + rounded, 0 = padding
+  __shared__ bf16_t img[63][COLS + 4];  // mixed + rounded
   __shared__ float tab[768];
   __shared__ uint8_t pbytes[21][COLS * 3];   // the partner's bytes of every (kt, ky) line
   const SvitMix m = *mix;
   const bool mixing = m.mode == 1 || m.mode == 2;
   const int yo = blockIdx.x % Ho, to = (blockIdx.x / Ho) % To, b = blockIdx.x / (Ho * To);
-  const int pb = B - 1 - b;
-  const int64_t n_videos = frames_bytes / ((int64_t)T * Hs * Ws * 3);
-  int v = crops ? crops[b * 3] : b, y0 = crops ? crops[b * 3 + 1] : 0, x0 = crops ? crops[b * 3 + 2] : 0;
-  int v2 = crops ? crops[pb * 3] : pb, y02 = crops ? crops[pb * 3 + 1] : 0, x02 = crops ? crops[pb * 3 + 2] : 0;
-  v = max(0, min(v, (int)n_videos - 1));
-  y0 = max(0, min(y0, Hs - S));
-  x0 = max(0, min(x0, Ws - S));
-  v2 = max(0, min(v2, (int)n_videos - 1));
-  y02 = max(0, min(y02, Hs - S));
-  x02 = max(0, min(x02, Ws - S));
+  const CropRow crop = crop_row(crops, b, frames_bytes, T, Hs, Ws, S);
+  const CropRow crop2 = crop_row(crops, B - 1 - b, frames_bytes, T, Hs, Ws, S);
   for (int i = threadIdx.x; i < 768; i += 256) tab[i] = lut[i];
   bf16_t* out = cols + (((int64_t)b * To + to) * Ho + yo) * Wo * 448;
   for (int xc0 = 0; xc0 < Wo; xc0 += XO) {
@@ -192,30 +237,14 @@ __global__ __launch_bounds__(256) void im2col_patch_u8_mix_kernel(
     const int xa = max(x_start, 0), xb = min(x_start + COLS, S);   // clip columns in the frame
     const int nbytes = (xb - xa) * 3;
     __syncthreads();                    // table ready / previous chunk's readers done
-    for (int i = threadIdx.x; i < 63 * (COLS + 4) / 2; i += 256) ((uint32_t*)img)[i] = 0u;
+    zero_image(img);
     if (mixing && xb > xa) {
       for (int line = 0; line < 21; ++line) {
         const int ky = line % 7, kt = line / 7;
         const int t = to * 2 - 1 + kt, y = yo * 4 - 3 + ky;
         if (t < 0 || t >= T || y < 0 || y >= S) continue;          // uniform over the block
-        const int64_t base = ((((int64_t)v2 * T + t) * Hs + (y02 + y)) * Ws + (x02 + xa)) * 3;
-        const int64_t a0 = base & ~(int64_t)3;
-        const int nwords = (int)((base + nbytes - a0 + 3) >> 2);
-        for (int w = threadIdx.x; w < nwords; w += 256) {
-          const int64_t addr = a0 + 4 * (int64_t)w;
-          uint32_t word = 0;
-          if (addr + 4 <= frames_bytes) {
-            word = *(const uint32_t*)(frames + addr);
-          } else {
-            for (int k = 0; k < 4; ++k)
-              if (addr + k < frames_bytes) word |= (uint32_t)frames[addr + k] << (8 * k);
-          }
-#pragma unroll
-          for (int k = 0; k < 4; ++k) {
-            const int j = (int)(addr + k - base);
-            if (j >= 0 && j < nbytes) pbytes[line][j] = (uint8_t)((word >> (8 * k)) & 255u);
-          }
-        }
+        walk_span(frames, frames_bytes, crop2.byte_of(T, Hs, Ws, t, y, xa), nbytes,
+                  [&](int j, uint32_t byte) { pbytes[line][j] = (uint8_t)byte; });
       }
     }
     __syncthreads();
@@ -224,53 +253,24 @@ __global__ __launch_bounds__(256) void im2col_patch_u8_mix_kernel(
       const int t = to * 2 - 1 + kt, y = yo * 4 - 3 + ky;
       if (t < 0 || t >= T || y < 0 || y >= S) continue;          // uniform over the block
       if (xb <= xa) continue;
-      const int64_t base = ((((int64_t)v * T + t) * Hs + (y0 + y)) * Ws + (x0 + xa)) * 3;
-      const int64_t a0 = base & ~(int64_t)3;                       // aligned 4-byte words
-      const int nwords = (int)((base + nbytes - a0 + 3) >> 2);
       const bool y_in = y >= m.yl && y < m.yh;
-      for (int w = threadIdx.x; w < nwords; w += 256) {
-        const int64_t addr = a0 + 4 * (int64_t)w;
-        uint32_t word = 0;
-        if (addr + 4 <= frames_bytes) {
-          word = *(const uint32_t*)(frames + addr);
-        } else {                                                    // last bytes of the buffer
-          for (int k = 0; k < 4; ++k)
-            if (addr + k < frames_bytes) word |= (uint32_t)frames[addr + k] << (8 * k);
+      walk_span(frames, frames_bytes, crop.byte_of(T, Hs, Ws, t, y, xa), nbytes, [&](int j, uint32_t byte) {
+        const int px = j / 3, c = j - px * 3;
+        float val = tab[c * 256 + byte];
+        if (mixing) {
+          const float other = tab[c * 256 + pbytes[line][j]];
+          const int x = xa + px;
+          if (m.mode == 1) val = mix_blend(val, other, m.lam, m.oml);
+          else if (y_in && x >= m.xl && x < m.xh) val = other;
         }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const int j = (int)(addr + k - base);                    // byte index inside the span
-          if (j < 0 || j >= nbytes) continue;
-          const int px = j / 3, c = j - px * 3;
-          float val = tab[c * 256 + ((word >> (8 * k)) & 255u)];
-          if (mixing) {
-            const float other = tab[c * 256 + pbytes[line][j]];
-            const int x = xa + px;
-            if (m.mode == 1) val = mix_blend(val, other, m.lam, m.oml);
-            else if (y_in && x >= m.xl && x < m.xh) val = other;
-          }
-          img[(c * 3 + kt) * 7 + ky][xa - x_start + px] = f32_to_bf16(val);
-        }
-      }
+        img[(c * 3 + kt) * 7 + ky][xa - x_start + px] = f32_to_bf16(val);
+      });
     }
     __syncthreads();
-    const int n_xo = min(XO, Wo - xc0);
-    for (int i = threadIdx.x; i < n_xo * 56; i += 256) {
-      const int xl = i / 56, chunk = i % 56;
-      bf16_t e8[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const int col = chunk * 8 + e;
-        const int kx = col % 7, r = col / 7;
-        e8[e] = col < 441 ? img[r][xl * 4 + 1 + kx] : (bf16_t)0;   // x = xo*4 - 3 + kx
-      }
-      uint4 o;
-      o.x = (uint32_t)e8[0] | ((uint32_t)e8[1] << 16); o.y = (uint32_t)e8[2] | ((uint32_t)e8[3] << 16);
-      o.z = (uint32_t)e8[4] | ((uint32_t)e8[5] << 16); o.w = (uint32_t)e8[6] | ((uint32_t)e8[7] << 16);
-      ((uint4*)out)[(size_t)(xc0 + xl) * 56 + chunk] = o;
-    }
+    store_chunk(img, out, xc0, Wo);
   }
 }
+
 // ---------------------------------------------------------------------------------------------------------------
 // Training augmentation on the uint8 route (svit_amd/augment.py): the reference's post-normalisation spatial pipeline
 // -- random-resized crop or short-side jitter + crop with bilinear resampling (datasets/transform.py:47-105,154-191,
@@ -449,7 +449,7 @@ __global__ __launch_bounds__(256) void im2col_patch_u8_aug_kernel(
   constexpr int KT = FRAMES ? 1 : 3;             // frames a block reads
   constexpr int LINE0 = FRAMES ? 7 : 0;          // first (kt, ky) line the fill writes, KT * 7 of them
   constexpr int STAGE = FRAMES ? AUG_STAGE_FRAMES : AUG_STAGE;
-  __shared__ bf16_t img[63][COLS + 4];  // [(c*3+kt)*7+ky][x - x_start], augmented + mixed + rounded, 0 = padding
+  __shared__ bf16_t img[63][COLS + 4];  // augmented + mixed + rounded
   __shared__ float tab[768];
   __shared__ uint32_t stage[STAGE / 4];
   SvitMix m = {0, 1.f, 0.f, 0, 0, 0, 0, 0};
@@ -465,8 +465,7 @@ __global__ __launch_bounds__(256) void im2col_patch_u8_aug_kernel(
   const AugGlobalFetch gfetch{frames, g.vbase, Hs, Ws, g.i, g.j};
   const AugGlobalFetch gfetch2{frames, g2.vbase, Hs, Ws, g2.i, g2.j};
   for (int i = threadIdx.x; i < 768; i += 256) tab[i] = lut[i];
-  if (FRAMES)                           // the kt = 0 and kt = 2 lines stay zero: no chunk writes them
-    for (int i = threadIdx.x; i < 63 * (COLS + 4) / 2; i += 256) ((uint32_t*)img)[i] = 0u;
+  if (FRAMES) zero_image(img);          // the kt = 0 and kt = 2 lines stay zero: no chunk writes them
   bf16_t* out = cols + ((int64_t)n * Ho + yo) * Wo * 448;
   // tap kt is frame t0 + kt (FRAMES: the one tap kt = 1 is frame n - b*T); the staged frames start at ts
   const int t0 = FRAMES ? n - b * T - 1 : (n - b * To) * 2 - 1, ts = FRAMES ? t0 + 1 : t0, y0 = yo * 4 - 3;
@@ -497,17 +496,7 @@ __global__ __launch_bounds__(256) void im2col_patch_u8_aug_kernel(
         const int64_t a0 = base & ~(int64_t)3;                       // aligned 4-byte words
         const int nwords = (int)((base + rowbytes - a0 + 3) >> 2);   // <= pitch / 4
         uint32_t* dst = stage + kr * (pitch >> 2);
-        for (int w = threadIdx.x; w < nwords; w += 256) {
-          const int64_t addr = a0 + 4 * (int64_t)w;
-          uint32_t word = 0;
-          if (addr + 4 <= frames_bytes) {
-            word = *(const uint32_t*)(frames + addr);
-          } else {                                                    // last bytes of the buffer
-            for (int k = 0; k < 4; ++k)
-              if (addr + k < frames_bytes) word |= (uint32_t)frames[addr + k] << (8 * k);
-          }
-          dst[w] = word;
-        }
+        for (int w = threadIdx.x; w < nwords; w += 256) dst[w] = load_word(frames, frames_bytes, a0 + 4 * (int64_t)w);
       }
       __syncthreads();
     }
@@ -533,24 +522,16 @@ __global__ __launch_bounds__(256) void im2col_patch_u8_aug_kernel(
       for (int c = 0; c < 3; ++c) img[(c * 3 + kt) * 7 + ky][px] = f32_to_bf16(v[c]);
     }
     __syncthreads();
-    const int n_xo = min(XO, Wo - xc0);
-    for (int i = threadIdx.x; i < n_xo * 56; i += 256) {
-      const int xl = i / 56, chunk = i % 56;
-      bf16_t e8[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const int col = chunk * 8 + e;
-        const int kx = col % 7, r = col / 7;
-        e8[e] = col < 441 ? img[r][xl * 4 + 1 + kx] : (bf16_t)0;   // x = xo*4 - 3 + kx
-      }
-      uint4 o;
-      o.x = (uint32_t)e8[0] | ((uint32_t)e8[1] << 16); o.y = (uint32_t)e8[2] | ((uint32_t)e8[3] << 16);
-      o.z = (uint32_t)e8[4] | ((uint32_t)e8[5] << 16); o.w = (uint32_t)e8[6] | ((uint32_t)e8[7] << 16);
-      ((uint4*)out)[(size_t)(xc0 + xl) * 56 + chunk] = o;
-    }
+    store_chunk(img, out, xc0, Wo);
   }
 }
 }  // namespace
+
+// the output grid of the patch embedding Conv3d(k(3,7,7), s(2,4,4), p(1,3,3)) over T frames of S x S
+struct PatchGrid {
+  int To, Ho, Wo;
+};
+static PatchGrid patch_grid(int T, int S) { return {(T + 2 - 3) / 2 + 1, (S + 6 - 7) / 4 + 1, (S + 6 - 7) / 4 + 1}; }
 
 extern "C" int svit_im2col_patch_u8(const uint8_t* frames, int64_t frames_bytes, const void* lut,
                                     const int32_t* crops, void* cols, int B, int T, int Hs,
@@ -558,10 +539,10 @@ extern "C" int svit_im2col_patch_u8(const uint8_t* frames, int64_t frames_bytes,
   if (!frames || !lut || !cols) return SVIT_ERR_ARG;
   if (B <= 0 || T <= 0 || Hs <= 0 || Ws <= 0 || S <= 0 || S > Hs || S > Ws) return SVIT_ERR_SHAPE;
   if ((uintptr_t)frames & 3) return SVIT_ERR_ALIGN;
-  const int To = (T + 2 - 3) / 2 + 1, Ho = (S + 6 - 7) / 4 + 1, Wo = (S + 6 - 7) / 4 + 1;
-  hipLaunchKernelGGL(im2col_patch_u8_kernel, dim3((unsigned)(B * To * Ho)), dim3(256), 0,
+  const PatchGrid g = patch_grid(T, S);
+  hipLaunchKernelGGL(im2col_patch_u8_kernel, dim3((unsigned)(B * g.To * g.Ho)), dim3(256), 0,
                      (hipStream_t)stream, frames, frames_bytes, (const bf16_t*)lut, crops,
-                     (bf16_t*)cols, T, Hs, Ws, S, To, Ho, Wo);
+                     (bf16_t*)cols, T, Hs, Ws, S, g.To, g.Ho, g.Wo);
   SVIT_LAUNCH_CHECK();
   return SVIT_OK;
 }
@@ -573,10 +554,10 @@ extern "C" int svit_im2col_patch_u8_mix(const uint8_t* frames, int64_t frames_by
   if (B <= 0 || T <= 0 || Hs <= 0 || Ws <= 0 || S <= 0 || S > Hs || S > Ws) return SVIT_ERR_SHAPE;
   if (frames_bytes < (int64_t)T * Hs * Ws * 3) return SVIT_ERR_SHAPE;
   if (((uintptr_t)frames | (uintptr_t)mix | (uintptr_t)lut_f32) & 3) return SVIT_ERR_ALIGN;
-  const int To = (T + 2 - 3) / 2 + 1, Ho = (S + 6 - 7) / 4 + 1, Wo = (S + 6 - 7) / 4 + 1;
-  hipLaunchKernelGGL(im2col_patch_u8_mix_kernel, dim3((unsigned)(B * To * Ho)), dim3(256), 0,
+  const PatchGrid g = patch_grid(T, S);
+  hipLaunchKernelGGL(im2col_patch_u8_mix_kernel, dim3((unsigned)(B * g.To * g.Ho)), dim3(256), 0,
                      (hipStream_t)stream, frames, frames_bytes, lut_f32, crops, (const SvitMix*)mix,
-                     (bf16_t*)cols, B, T, Hs, Ws, S, To, Ho, Wo);
+                     (bf16_t*)cols, B, T, Hs, Ws, S, g.To, g.Ho, g.Wo);
   SVIT_LAUNCH_CHECK();
   return SVIT_OK;
 }
@@ -613,34 +594,33 @@ static int aug_args_ok(const void* frames, int64_t frames_bytes, const void* lut
   return SVIT_OK;
 }
 
-extern "C" int svit_im2col_patch_u8_aug(const uint8_t* frames, int64_t frames_bytes, const float* lut_f32,
-                                        const void* aug, const void* mix, void* cols, int B, int T, int Hs,
-                                        int Ws, int S, void* stream) {
+// both passes of the augmented im2col: FRAMES = the B*T frames as single-frame clips (To = 1)
+template <bool FRAMES>
+static int launch_im2col_aug(const uint8_t* frames, int64_t frames_bytes, const float* lut_f32, const void* aug,
+                             const void* mix, void* cols, int B, int T, int Hs, int Ws, int S, void* stream) {
   const int rc = aug_args_ok(frames, frames_bytes, lut_f32, aug, cols, B, T, Hs, Ws, S);
   if (rc != SVIT_OK) return rc;
   if (((uintptr_t)mix & 3) || ((uintptr_t)cols & 15)) return SVIT_ERR_ALIGN;
-  const int To = (T + 2 - 3) / 2 + 1, Ho = (S + 6 - 7) / 4 + 1, Wo = (S + 6 - 7) / 4 + 1;
-  if ((int64_t)B * To * Ho > 0x7fffffff) return SVIT_ERR_SHAPE;
-  hipLaunchKernelGGL(im2col_patch_u8_aug_kernel<false>, dim3((unsigned)(B * To * Ho)), dim3(256), 0,
+  const PatchGrid g = patch_grid(FRAMES ? 1 : T, S);
+  const int64_t blocks = (int64_t)B * (FRAMES ? T : g.To) * g.Ho;
+  if (blocks > 0x7fffffff) return SVIT_ERR_SHAPE;
+  hipLaunchKernelGGL(im2col_patch_u8_aug_kernel<FRAMES>, dim3((unsigned)blocks), dim3(256), 0,
                      (hipStream_t)stream, frames, frames_bytes, lut_f32, (const SvitAug*)aug, (const SvitMix*)mix,
-                     (bf16_t*)cols, B, T, Hs, Ws, S, To, Ho, Wo);
+                     (bf16_t*)cols, B, T, Hs, Ws, S, g.To, g.Ho, g.Wo);
   SVIT_LAUNCH_CHECK();
   return SVIT_OK;
+}
+
+extern "C" int svit_im2col_patch_u8_aug(const uint8_t* frames, int64_t frames_bytes, const float* lut_f32,
+                                        const void* aug, const void* mix, void* cols, int B, int T, int Hs,
+                                        int Ws, int S, void* stream) {
+  return launch_im2col_aug<false>(frames, frames_bytes, lut_f32, aug, mix, cols, B, T, Hs, Ws, S, stream);
 }
 
 extern "C" int svit_im2col_patch_u8_aug_frames(const uint8_t* frames, int64_t frames_bytes, const float* lut_f32,
                                                const void* aug, const void* mix, void* cols, int B, int T, int Hs,
                                                int Ws, int S, void* stream) {
-  const int rc = aug_args_ok(frames, frames_bytes, lut_f32, aug, cols, B, T, Hs, Ws, S);
-  if (rc != SVIT_OK) return rc;
-  if (((uintptr_t)mix & 3) || ((uintptr_t)cols & 15)) return SVIT_ERR_ALIGN;
-  const int Ho = (S + 6 - 7) / 4 + 1, Wo = (S + 6 - 7) / 4 + 1;
-  if ((int64_t)B * T * Ho > 0x7fffffff) return SVIT_ERR_SHAPE;
-  hipLaunchKernelGGL(im2col_patch_u8_aug_kernel<true>, dim3((unsigned)(B * T * Ho)), dim3(256), 0,
-                     (hipStream_t)stream, frames, frames_bytes, lut_f32, (const SvitAug*)aug, (const SvitMix*)mix,
-                     (bf16_t*)cols, B, T, Hs, Ws, S, 1, Ho, Wo);
-  SVIT_LAUNCH_CHECK();
-  return SVIT_OK;
+  return launch_im2col_aug<true>(frames, frames_bytes, lut_f32, aug, mix, cols, B, T, Hs, Ws, S, stream);
 }
 
 extern "C" int svit_u8_clips_render(const uint8_t* frames, int64_t frames_bytes, const float* lut_f32,

@@ -336,20 +336,17 @@ class Engine:
         """video f32 [B,3,Tx,S,S] (or U8Clips / AugClips / FramesView) -> (normed tokens f32 [B,N_last,C_last], saved-state dict)."""
         plan, f = self.plan, self.flat
         if isinstance(video, U8Clips):       # decoded uint8 frames + crop table (svit_amd/input.py)
-            B, _, Tx = video.shape[:3]
             cols, (To, Ho, Wo) = ops.im2col_patch_u8(video)
         elif isinstance(video, AugClips):    # the same + one augmentation record per clip (svit_amd/augment.py)
-            B, _, Tx = video.shape[:3]
             cols, (To, Ho, Wo) = ops.im2col_patch_u8_aug(video)
         elif isinstance(video, FramesView):  # the frames of either as single-frame clips (the frames pass)
-            B, _, Tx = video.shape[:3]
             cols, (To, Ho, Wo) = ops.im2col_patch_u8_aug_frames(video)
         else:
             if video.dim() == 4:
                 video = video.unsqueeze(2)
             video = video.contiguous().to(F32)
-            B, _, Tx = video.shape[:3]
             cols, (To, Ho, Wo) = ops.im2col_patch(video)
+        B, _, Tx = video.shape[:3]
         T = plan.num_frames // plan.patch_stride[0] if Tx > 1 else Tx  # from cfg, builder:322
         if To != T:
             raise hip.SvitHipError("clip has %d frames but cfg.DATA.NUM_FRAMES=%d" % (Tx, plan.num_frames))

@@ -14,36 +14,60 @@ import torch
 from . import hip
 
 
-def normalize_lut(mean, std, device):
-    """bf16 [3,256]: tensor_normalize (datasets/utils.py:287-303) of every uint8 value, with the
-    reference's fp32 operation order, then the bf16 rounding the patch-embed operand gets."""
-    t = torch.arange(256, dtype=torch.float32) / 255.0
-    t = t[None, :] - torch.tensor(list(mean), dtype=torch.float32)[:, None]
-    t = t / torch.tensor(list(std), dtype=torch.float32)[:, None]
-    return t.to(torch.bfloat16).contiguous().to(device)
-
-
 def normalize_lut_f32(mean, std, device):
-    """f32 [3,256]: the same table before the bf16 rounding (same operations in the same order) -- what the
-    mixup route blends (`svit_im2col_patch_u8_mix`: normalise, mix in fp32, round once)."""
+    """f32 [3,256]: tensor_normalize (datasets/utils.py:287-303) of every uint8 value, with the reference's fp32
+    operation order -- what the mixup route blends (`svit_im2col_patch_u8_mix`: normalise, mix in fp32, round once)."""
     t = torch.arange(256, dtype=torch.float32) / 255.0
     t = t[None, :] - torch.tensor(list(mean), dtype=torch.float32)[:, None]
     t = t / torch.tensor(list(std), dtype=torch.float32)[:, None]
     return t.contiguous().to(device)
 
 
-class U8Clips:
-    """B clips cut from V uint8 videos.  Quacks like the fp32 clip tensor where the model and
-    GraphedTrainStep look at it (`shape`, `dim()`, `device`, `detach/clone/contiguous/copy_`)."""
+def normalize_lut(mean, std, device):
+    """bf16 [3,256]: the same table after the bf16 rounding the patch-embed operand gets."""
+    return normalize_lut_f32(mean, std, "cpu").to(torch.bfloat16).to(device)
 
-    def __init__(self, frames, size, crops=None, mean=(0.45, 0.45, 0.45), std=(0.225, 0.225, 0.225),
-                 lut=None, lut_f32=None):
+
+class U8Input:
+    """uint8 frames [V,T,Hs,Ws,3] on the GPU + a table with one row per clip (`_rows` names it), standing in for the
+    fp32 clip tensor [B,3,T,S,S]: the parts of the tensor interface the model path and GraphedTrainStep touch."""
+    _rows = None
+
+    def _take_frames(self, frames):
         if frames.dtype != torch.uint8 or frames.dim() != 5 or frames.shape[-1] != 3:
             raise ValueError("frames must be uint8 [V,T,H,W,3], got %s %s" % (frames.dtype, tuple(frames.shape)))
         if not frames.is_cuda:
-            raise hip.SvitHipError("U8Clips lives on the GPU (the host ships uint8, a quarter of the bytes)")
+            raise hip.SvitHipError("%s lives on the GPU (the host ships uint8, a quarter of the bytes)"
+                                   % type(self).__name__)
         self.frames = frames.contiguous()
-        V, T, Hs, Ws, _ = frames.shape
+        return frames.shape[:4]
+
+    @property
+    def shape(self):
+        return torch.Size((getattr(self, self._rows).shape[0], 3, self.frames.shape[1], self.size, self.size))
+
+    @property
+    def device(self):
+        return self.frames.device
+
+    def dim(self):
+        return 5
+
+    def detach(self):
+        return self
+
+    def contiguous(self):
+        return self
+
+
+class U8Clips(U8Input):
+    """B clips cut from V uint8 videos.  Quacks like the fp32 clip tensor where the model and
+    GraphedTrainStep look at it (`shape`, `dim()`, `device`, `detach/clone/contiguous/copy_`)."""
+    _rows = "crops"
+
+    def __init__(self, frames, size, crops=None, mean=(0.45, 0.45, 0.45), std=(0.225, 0.225, 0.225),
+                 lut=None, lut_f32=None):
+        V, T, Hs, Ws = self._take_frames(frames)
         self.size = int(size)
         if self.size > Hs or self.size > Ws:
             raise ValueError("crop %d larger than the frames %dx%d" % (self.size, Hs, Ws))
@@ -78,26 +102,8 @@ class U8Clips:
             self._lut_f32 = normalize_lut_f32(self.mean, self.std, self.frames.device)
         return self._lut_f32
 
-    # ---- the parts of the tensor interface the model path touches ---------------------------
-    @property
-    def shape(self):
-        return torch.Size((self.crops.shape[0], 3, self.frames.shape[1], self.size, self.size))
-
-    @property
-    def device(self):
-        return self.frames.device
-
-    def dim(self):
-        return 5
-
     def data_ptr(self):
         return self.frames.data_ptr()
-
-    def detach(self):
-        return self
-
-    def contiguous(self):
-        return self
 
     def clone(self):
         return U8Clips(self.frames.clone(), self.size, self.crops.clone(), mean=self.mean, std=self.std,
@@ -119,7 +125,7 @@ def identity_records(crops, size):
     return rec
 
 
-class FramesView:
+class FramesView(U8Input):
     """The B*T frames of a U8Clips or an augment.AugClips as single-frame clips -- the input of the reference's frames
     pass (tools/train_net.py:105-110: `inputs[0].transpose(1, 2).flatten(0, 1).unsqueeze(2)`) without the fp32 clip.
     Nothing is copied: the view reads the clips' `frames`, records (or crop table), `lut_f32` and `mix` when it is
@@ -149,19 +155,6 @@ class FramesView:
     def shape(self):
         B, _, T, S, _ = self.clips.shape
         return torch.Size((B * T, 3, 1, S, S))
-
-    @property
-    def device(self):
-        return self.clips.device
-
-    def dim(self):
-        return 5
-
-    def detach(self):
-        return self
-
-    def contiguous(self):
-        return self
 
 
 def spatial_crops_u8(frames, size, num_crops=3, **kw):

@@ -339,31 +339,33 @@ def im2col_patch(video):
     return cols, (To, Ho, Wo)
 
 
-def im2col_patch_u8(clips):
-    """svit_amd.input.U8Clips -> the same [rows, 448] bf16 operand as im2col_patch."""
-    fr = clips.frames
+def _im2col_u8(name, fr, lut, table, S, mix=(), frames_pass=False):
+    """One launch of a uint8 im2col kernel: frames u8 [V,T,Hs,Ws,3], its normalisation table, the per-clip table (crop
+    rows or augmentation records) and, for the kernels that take one, the mix record (`mix` = (record or None,)).
+    -> (cols bf16 [rows, 448], (To, Ho, Wo)); frames_pass: the B*T frames as single-frame clips."""
     _chk_dev(fr)
     V, T, Hs, Ws, _ = fr.shape
-    B, S = clips.crops.shape[0], clips.size
-    To, Ho, Wo = (T - 1) // 2 + 1, (S - 1) // 4 + 1, (S - 1) // 4 + 1
-    cols = torch.empty((B * To * Ho * Wo, 448), device=fr.device, dtype=BF16)
-    mix = getattr(clips, "mix", None)
-    if mix is not None:     # cfg.MIXUP on the uint8 route: blended / swapped between normalisation and bf16 rounding
-        _chk_mix(mix, fr.device)
-        hip.call("svit_im2col_patch_u8_mix", ptr(fr), fr.numel(), ptr(clips.lut_f32), ptr(clips.crops), ptr(mix),
-                 ptr(cols), B, T, Hs, Ws, S)
-        return cols, (To, Ho, Wo)
-    hip.call("svit_im2col_patch_u8", ptr(fr), fr.numel(), ptr(clips.lut), ptr(clips.crops),
-             ptr(cols), B, T, Hs, Ws, S)
+    B = table.shape[0]
+    n, To = (B * T, 1) if frames_pass else (B, (T - 1) // 2 + 1)
+    Ho = Wo = (S - 1) // 4 + 1
+    cols = torch.empty((n * To * Ho * Wo, 448), device=fr.device, dtype=BF16)
+    for m in mix:
+        if m is not None:
+            _chk_mix(m, fr.device)
+    hip.call(name, ptr(fr), fr.numel(), ptr(lut), ptr(table), *[ptr(m) for m in mix], ptr(cols), B, T, Hs, Ws, S)
     return cols, (To, Ho, Wo)
 
 
-def _chk_aug(clips):
-    """svit_amd.augment.AugClips: the frames, the int32 [B,16] record table and the fp32 table on one device"""
-    _chk_aug_parts(clips.frames, clips.records, clips.lut_f32)
+def im2col_patch_u8(clips):
+    """svit_amd.input.U8Clips -> the same [rows, 448] bf16 operand as im2col_patch."""
+    mix = getattr(clips, "mix", None)
+    if mix is not None:     # cfg.MIXUP on the uint8 route: blended / swapped between normalisation and bf16 rounding
+        return _im2col_u8("svit_im2col_patch_u8_mix", clips.frames, clips.lut_f32, clips.crops, clips.size, (mix,))
+    return _im2col_u8("svit_im2col_patch_u8", clips.frames, clips.lut, clips.crops, clips.size)
 
 
-def _chk_aug_parts(fr, rec, lut):
+def _chk_aug(fr, rec, lut):
+    """the frames, the int32 [B,16] record table and the fp32 table of an augment.AugClips on one device"""
     _chk_dev(fr, rec, lut)
     if rec.dtype != torch.int32 or rec.dim() != 2 or rec.shape[1] != 16 or not rec.is_contiguous() or rec.device != fr.device:
         raise hip.SvitHipError("the augmentation records must be contiguous int32 [B,16] on %s (got %s %s on %s)"
@@ -375,19 +377,10 @@ def _chk_aug_parts(fr, rec, lut):
 def im2col_patch_u8_aug(clips):
     """svit_amd.augment.AugClips -> the same [rows, 448] bf16 operand as im2col_patch: resized crop, flip and erasing per
     the device records (and the mix of `clips.mix`, when set) between the fp32 normalisation and the one bf16 rounding."""
-    _chk_aug(clips)
+    _chk_aug(clips.frames, clips.records, clips.lut_f32)
     clips.run_randaug()         # (cfg.AUG.AA_TYPE: raw -> frames on this stream first; nothing without a table)
-    fr = clips.frames
-    V, T, Hs, Ws, _ = fr.shape
-    B, S = clips.records.shape[0], clips.size
-    To, Ho, Wo = (T - 1) // 2 + 1, (S - 1) // 4 + 1, (S - 1) // 4 + 1
-    cols = torch.empty((B * To * Ho * Wo, 448), device=fr.device, dtype=BF16)
-    mix = getattr(clips, "mix", None)
-    if mix is not None:
-        _chk_mix(mix, fr.device)
-    hip.call("svit_im2col_patch_u8_aug", ptr(fr), fr.numel(), ptr(clips.lut_f32), ptr(clips.records), ptr(mix),
-             ptr(cols), B, T, Hs, Ws, S)
-    return cols, (To, Ho, Wo)
+    return _im2col_u8("svit_im2col_patch_u8_aug", clips.frames, clips.lut_f32, clips.records, clips.size,
+                      (getattr(clips, "mix", None),))
 
 
 def im2col_patch_u8_aug_frames(view):
@@ -399,22 +392,13 @@ def im2col_patch_u8_aug_frames(view):
     if not view.fresh and hasattr(clips, "run_randaug"):
         clips.run_randaug()
     fr, rec, lut = view.frames, view.device_records(), view.lut_f32
-    _chk_aug_parts(fr, rec, lut)
-    V, T, Hs, Ws, _ = fr.shape
-    B, S = rec.shape[0], view.size
-    Ho = Wo = (S - 1) // 4 + 1
-    cols = torch.empty((B * T * Ho * Wo, 448), device=fr.device, dtype=BF16)
-    mix = view.mix
-    if mix is not None:
-        _chk_mix(mix, fr.device)
-    hip.call("svit_im2col_patch_u8_aug_frames", ptr(fr), fr.numel(), ptr(lut), ptr(rec), ptr(mix), ptr(cols),
-             B, T, Hs, Ws, S)
-    return cols, (1, Ho, Wo)
+    _chk_aug(fr, rec, lut)
+    return _im2col_u8("svit_im2col_patch_u8_aug_frames", fr, lut, rec, view.size, (view.mix,), frames_pass=True)
 
 
 def u8_clips_render(clips):
     """svit_amd.augment.AugClips -> f32 [B,3,T,S,S]: the values im2col_patch_u8_aug rounds, unrounded (no mix)"""
-    _chk_aug(clips)
+    _chk_aug(clips.frames, clips.records, clips.lut_f32)
     clips.run_randaug()
     fr = clips.frames
     V, T, Hs, Ws, _ = fr.shape

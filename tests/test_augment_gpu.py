@@ -253,6 +253,7 @@ def _mix(mode, lam, box=(0, 0, 0, 0)):
     ((3, 4, 40, 56, 3), 32, [(0, 3, 5), (2, 8, 24), (1, 0, 7)]),                   # odd B
     ((3, 4, 40, 56, 3), 32, [(0, 3, 5), (1, 0, 21), (2, 6, 0), (1, 6, 18)]),
     ((1, 2, 300, 300, 3), 256, [(0, 0, 0), (0, 44, 43)]),                          # two chunks per row
+    ((1, 3, 41, 59, 3), 37, [(0, 4, 22), (0, 1, 0)]),       # 21771 bytes = 3 mod 4, clip 0 ends on the last byte
 ])
 def test_identity_geometry_is_bit_equal_to_the_plain_u8_kernels(ops, shape, S, table):
     from svit_amd.augment import AugClips

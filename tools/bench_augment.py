@@ -151,7 +151,7 @@ def main():
            "steps": args.steps, "warmup": args.warmup, "rounds": args.rounds, "ms_per_step": ms,
            "ms_per_step_best": {a: min(v) for a, v in ms.items() if v},
            "spread_ms": {a: round(max(v) - min(v), 3) for a, v in ms.items() if v}, "loss": loss,
-           "n_graphs": {a: graphed[a].n_graphs for a in arms}, "kernel_us": kernels,
+           "n_graphs": {a: graphed[a].n_graphs for a in graphed}, "kernel_us": kernels,
            "records": {"aug": [list(r) for r in records(0.0)]}}
     if ms.get("plain"):
         base = min(ms["plain"])
