@@ -681,6 +681,18 @@ int svit_debug_set_pool(int key, int val);
  * plan, a workspace smaller than the plan's partial rows, key 1 = 0: SVIT_ERR_SHAPE in the product library, the two streaming
  * launches in a -DSVIT_DIAG_POOL_STREAMING build), -1 = no call yet. */
 int svit_debug_pool_bwd_path(void);
+/* What the host would decide for a pooling geometry -- the forward's chooser and the chunk search themselves, asked with plain
+ * integers.  Launches nothing and needs no device.  save_mask: bit i = tensor i saves pre / mean / rstd; sel: selector tables
+ * are given; relq_lpad: svit_pool_args.relq_lpad where q's rel-pos columns are wanted, else 0.  Fills out (n_out >= 24) and
+ * returns the number of values written, or an error code.
+ * kind 0, the forward (svit_pool_ln_fwd_qkv[_sel]): path (0 frame, 1 MFMA slab, 2 VALU slab, 3 staged, 4 streaming / tiled);
+ *   who writes q's rel-pos columns (0 nobody, 1 pool_slab_ln_kernel, 2 the trailing svit_gemm_nt with SVIT_EPI_RELQ); the
+ *   number of pooling launches; per launch the kernel (0 pool_frame_fwd, 1 pool_mfma_fwd, 2 pool_slab_fwd, 3 pool_slab_ln,
+ *   4 pool_fwd_staged, 5 pool_ln_fwd3), grid x, y, z, block size, dynamic LDS bytes.
+ * kind 1 / 2, the chunk plan of the staged forward / of svit_pool_conv_bwd_qkv: ok (0 = no plan), n_per[3], r_per[3],
+ *   t_chunks[3], y_chunks[3], order[3], first_item[4], LDS bytes, max_chunks. */
+int svit_debug_pool_plan(int kind, int B, int heads, int T, int H, int W, int n_obj, int sq, int sk, int sv, int save_mask,
+                         int sel, int relq_lpad, int32_t* out, int n_out);
 /* attention: key 0 = dkv kernel form (0 heuristic, 1 four waves, 2 eight waves with query halves), key 3 = the
  * forward's T' = 1 tile for Nk <= 64 (1 on (default), 0 the generic kernel). */
 int svit_attn_debug_set(int key, int val);

@@ -9,8 +9,8 @@
 #include <mutex>
 #include <vector>
 #include <cmath>
-#include <cstdlib>
-#include <atomic>
+#include <cstddef>
+#include <cstring>
 #include "common.h"
 #include "../../include/svit_hip.h"
 
@@ -2119,38 +2119,67 @@ static int check_pool_dims(int B, int heads, int T, int H, int W, int n_obj, int
   return SVIT_OK;
 }
 
-extern "C" int svit_pool_ln_fwd(const svit_pool_args* a, void* stream) {
-  if (!a || !a->qkv || !a->conv_w || !a->gamma || !a->beta || !a->out || !a->pre || !a->mean || !a->rstd)
-    return SVIT_ERR_ARG;
-  int rc = check_pool_dims(a->B, a->heads, a->T, a->H, a->W, a->n_obj, a->stride_hw);
-  if (rc) return rc;
-  if (a->which < 0 || a->which > 2 || a->ld_out < HD || a->ld_out % 8 != 0) return SVIT_ERR_ARG;
-  const int Ho = (a->H - 1) / a->stride_hw + 1, Wo = (a->W - 1) / a->stride_hw + 1;
-  if (a->mode == 1) {
-    const int extra = a->ld_out - HD;
-    if (extra % 32 != 0 || extra < Ho + Wo + a->T) return SVIT_ERR_SHAPE;
-  }
-  const int Nout = 1 + a->T * Ho * Wo + a->n_obj;
-  hipLaunchKernelGGL(pool_ln_fwd_kernel, dim3(persistent_x((Nout + 63) / 64, a->B * a->heads),
-                                              a->B * a->heads), dim3(256), 0, (hipStream_t)stream, *a);
-  SVIT_LAUNCH_CHECK();
-  return SVIT_OK;
+// pooled plane and token count of one tensor: Nout = 1 (cls) + T * Ho * Wo + n_obj
+struct PoolOut { int Ho, Wo, Nout; };
+static PoolOut pool_out(int T, int H, int W, int n_obj, int s) {
+  const int Ho = (H - 1) / s + 1, Wo = (W - 1) / s + 1;
+  return {Ho, Wo, 1 + T * Ho * Wo + n_obj};
 }
+static PoolOut pool_out(const svit_pool_args& a) { return pool_out(a.T, a.H, a.W, a.n_obj, a.stride_hw); }
 
 static int check_pool_fwd(const svit_pool_args* a) {
   if (!a->qkv || !a->conv_w || !a->gamma || !a->beta || !a->out) return SVIT_ERR_ARG;
   if ((a->pre == nullptr) != (a->mean == nullptr) || (a->mean == nullptr) != (a->rstd == nullptr))
     return SVIT_ERR_ARG;     // the saved-for-backward trio is all-or-nothing
-  int rc = check_pool_dims(a->B, a->heads, a->T, a->H, a->W, a->n_obj, a->stride_hw);
-  if (rc) return rc;
+  if (int rc = check_pool_dims(a->B, a->heads, a->T, a->H, a->W, a->n_obj, a->stride_hw)) return rc;
   if (a->which < 0 || a->which > 2 || a->ld_out < HD || a->ld_out % 8 != 0) return SVIT_ERR_ARG;
-  const int Ho = (a->H - 1) / a->stride_hw + 1, Wo = (a->W - 1) / a->stride_hw + 1;
   if (a->mode == 1) {
+    const PoolOut o = pool_out(*a);
     const int extra = a->ld_out - HD;
-    if (extra % 32 != 0 || extra < Ho + Wo + a->T) return SVIT_ERR_SHAPE;
+    if (extra % 32 != 0 || extra < o.Ho + o.Wo + a->T) return SVIT_ERR_SHAPE;
   }
   return SVIT_OK;
 }
+
+extern "C" int svit_pool_ln_fwd(const svit_pool_args* a, void* stream) {
+  if (!a || !a->pre || !a->mean || !a->rstd) return SVIT_ERR_ARG;      // (the single-tensor kernel always saves the trio)
+  if (int rc = check_pool_fwd(a)) return rc;
+  hipLaunchKernelGGL(pool_ln_fwd_kernel, dim3(persistent_x((pool_out(*a).Nout + 63) / 64, a->B * a->heads),
+                                              a->B * a->heads), dim3(256), 0, (hipStream_t)stream, *a);
+  SVIT_LAUNCH_CHECK();
+  return SVIT_OK;
+}
+
+// What the host decides from, for a q / k / v pooling call: plain integers, filled from the argument blocks (pool_geom) or by
+// the plan query (svit_debug_pool_plan).  T / H / W / n_obj are per tensor because the forward entry points have never
+// refused tensors that differ in them; every caller passes one volume three times.
+struct PoolGeom {
+  int B, heads, T[3], H[3], W[3], n_obj[3], s[3];
+  int pre[3];        // the tensor saves pre / mean / rstd
+  int sel;           // selector tables were given
+  int relq_lpad;     // q's rel-pos columns are wanted: rows of the concatenated tables (svit_pool_args.relq_lpad), else 0
+};
+static PoolGeom pool_geom(int B, int heads, int T, int H, int W, int n_obj, int sq, int sk, int sv) {
+  PoolGeom g = {};
+  g.B = B; g.heads = heads;
+  for (int i = 0; i < 3; ++i) { g.T[i] = T; g.H[i] = H; g.W[i] = W; g.n_obj[i] = n_obj; g.s[i] = i == 0 ? sq : i == 1 ? sk : sv; }
+  return g;
+}
+static PoolGeom pool_geom(const svit_pool_args* a3, bool sel) {
+  PoolGeom g = {};
+  g.B = a3[0].B; g.heads = a3[0].heads;
+  for (int i = 0; i < 3; ++i) {
+    g.T[i] = a3[i].T; g.H[i] = a3[i].H; g.W[i] = a3[i].W; g.n_obj[i] = a3[i].n_obj; g.s[i] = a3[i].stride_hw;
+    g.pre[i] = a3[i].pre != nullptr;
+  }
+  g.sel = sel;
+  g.relq_lpad = a3[0].relq_R ? a3[0].relq_lpad : 0;
+  return g;
+}
+static PoolGeom pool_geom(const svit_pool_dgrad_args* d3) {
+  return pool_geom(d3[0].B, d3[0].heads, d3[0].T, d3[0].H, d3[0].W, d3[0].n_obj, d3[0].stride_hw, d3[1].stride_hw, d3[2].stride_hw);
+}
+static PoolOut pool_out(const PoolGeom& g, int i) { return pool_out(g.T[i], g.H[i], g.W[i], g.n_obj[i], g.s[i]); }
 
 // plan of the LDS-tiled stride-1 stencil for one tensor (see pool_tiled_body)
 static PoolTilePlan plan_tiled(int T, int H, int W, int n_obj, int bh) {
@@ -2180,93 +2209,78 @@ static size_t tiled_lds_bytes(int W) {
 // SVIT_K_POOL_FWD of the knob table (common.h): 0 = streaming kernels, 1 = VALU slab conv, 2 = MFMA conv where it is ahead,
 // 3 = MFMA conv wherever its geometry holds.  Whole planes only: the y-chunked planner for 28x28 planes (rounds 3-4)
 // measured level with the streaming kernel inside the step (profiles/r04_in_step_sweeps.txt) and was removed in round 5.
-static SlabPlan plan_slab(const svit_pool_args& a) {
+static SlabPlan plan_slab(const PoolGeom& g, int i) {
   SlabPlan pl = {0, 0, 0, 0, 0};
-  const int s = a.stride_hw;
+  const int s = g.s[i], T = g.T[i], H = g.H[i], W = g.W[i];
   // measured (tools/pool_one.py under rocprofv3, profiles/r03_pool_slab.txt): ahead of the streaming
   // kernel on the 14x14 and 7x7 planes (12 of 16 blocks), behind it on 28x28 and behind the tiled
   // stencil on 56x56 -- the conv phase is VALU-bound (27 v_dot2 per output channel) and a slab
   // workgroup serialises fill -> conv -> store with one 16-wave workgroup per CU (106 SGPRs)
-  if (!svit_knob(SVIT_K_POOL_FWD) || s > 2 || !a.pre || a.H * a.W > 196) return pl;
-  const int Ho = (a.H - 1) / s + 1;
+  if (!svit_knob(SVIT_K_POOL_FWD) || s > 2 || !g.pre[i] || H * W > 196) return pl;
+  const PoolOut o = pool_out(g, i);
   double best = 1e30;
-  for (int tc = 1; tc <= a.T; ++tc)
-    for (int yc = Ho; yc <= Ho; ++yc) {     // whole planes: the planes this path is used on (<= 14x14) fit
-      const int pin = std::min(a.T, tc + 2), rin = std::min(a.H, s * (yc - 1) + 3);
-      if ((long)pin * rin * a.W > SLAB_MAXTOK) continue;
-      const double cost = ((double)pin / tc) * ((double)rin / (s * yc)) - 1e-6 * tc * yc;
-      if (cost < best) { best = cost; pl.TC = tc; pl.YC = yc; }
-    }
+  const int yc = o.Ho;                          // whole planes: the planes this path is used on (<= 14x14) fit
+  for (int tc = 1; tc <= T; ++tc) {
+    const int pin = std::min(T, tc + 2), rin = std::min(H, s * (yc - 1) + 3);
+    if ((long)pin * rin * W > SLAB_MAXTOK) continue;
+    const double cost = ((double)pin / tc) * ((double)rin / (s * yc)) - 1e-6 * tc * yc;
+    if (cost < best) { best = cost; pl.TC = tc; pl.YC = yc; }
+  }
   if (pl.TC == 0) return pl;
-  pl.ny = (Ho + pl.YC - 1) / pl.YC;
+  pl.ny = (o.Ho + pl.YC - 1) / pl.YC;
   // at most one 64-token unit per wave (the conv phase of a workgroup is then ONE pass of ~750 VALU
   // instructions per wave), then cut in t until the tensor alone gives the chip >= 128 workgroups
-  const int Wo = (a.W - 1) / s + 1;
-  while (pl.TC > 1 && (long)pl.TC * pl.YC * Wo > SLAB_NT) pl.TC = (pl.TC + 1) / 2;
-  while (pl.TC > 1 && (long)((a.T + pl.TC - 1) / pl.TC) * pl.ny * a.B * a.heads * 4 < 128) pl.TC = (pl.TC + 1) / 2;
-  pl.nt = (a.T + pl.TC - 1) / pl.TC;
+  while (pl.TC > 1 && (long)pl.TC * pl.YC * o.Wo > SLAB_NT) pl.TC = (pl.TC + 1) / 2;
+  while (pl.TC > 1 && (long)((T + pl.TC - 1) / pl.TC) * pl.ny * g.B * g.heads * 4 < 128) pl.TC = (pl.TC + 1) / 2;
+  pl.nt = (T + pl.TC - 1) / pl.TC;
   pl.on = 1;
   return pl;
 }
 
-// (chunking of one tensor; memo key of a plan: batch*heads, T, H, W, the three strides, kind)
 // The LDS-staged kernels address a clip of qkv / dqkv through a buffer descriptor: num_records = the clip's bytes as an int,
 // per-lane 32-bit byte offsets, 0x7ffffff0 as the "past the end" sentinel.  A clip that large takes the 64-bit streaming paths.
 static bool pool_clip_span_ok(int T, int H, int W, int n_obj, int heads) {
   const size_t span = (size_t)(1 + (size_t)T * H * W + n_obj) * 3 * heads * HD * 2;
   return span < 0x7ffffff0u;
 }
-
+// ---- chunk plans of the two LDS-staged kernels (pool_fwd_staged_kernel, pool_bwd_fused_kernel) ----
+// Both cut every tensor into chunks of n planes x r rows: an item (one per batch*head, tensor, channel group, t-chunk, y-chunk)
+// stages the (n + 2)-plane image of its chunk in LDS.  One search picks (n, r) for q and one pair for k and v together (same
+// stride in every block of the model) so that the items are about equally long and fill the chip's slots.  Estimate of the
+// launch = the longest item if everything is resident at once, else the average load of a slot plus half an item.  What
+// differs between the kernels comes in as a model: the row extent and stride class per tensor, lds_of(i, n, r), item_us(i, n, r),
+// cost(i, plan, t_chunks, y_chunks, &sum, &longest) and admit(q's plan, kv's plan).
 struct PfTensorPlan { int n, r; };
-struct PfPlanKey { int v[8]; bool operator==(const PfPlanKey& o) const { for (int i = 0; i < 8; ++i) if (v[i] != o.v[i]) return false; return true; } };
-// Planner of the staged conv forward (pool_fwd_staged_kernel): output planes (n) and output rows (R) per chunk and tensor so
-// that (n + 2) planes of the R-row image fit LDS at three workgroups per CU and the items fill the chip about evenly.
-// Item time: staging 3 us + 0.08 us per 1-KiB piece and wave, 0.27 us per 16-output step (27 reads + 54 dot2), ~1 us of tail.
-// Memoised per geometry like the backward's plan.  false: some tensor's smallest image does not fit.
-struct PsPlanEntry { PfPlanKey key; bool ok; PoolFwdStaged plan; size_t lds; };
-static std::mutex g_ps_plan_mu;
-static std::vector<PsPlanEntry> g_ps_plans;
-#ifndef SVIT_PS_LDS_KB      // LDS budget of a staged-forward workgroup / resident workgroups the planner counts on.  Swept in
-#define SVIT_PS_LDS_KB 79   // diagnostic builds (profiles/r05_pool_fwd_staged.txt): 256 threads x 52 KB x 3 per CU 255 us over blocks 0-3,
-#define SVIT_PS_SLOTS 512   // 256 x 79 KB x 2: 238, 512 x 79 KB x 2: 232 (default), 1024 x 156 KB x 1: 287
-#endif
-static bool plan_fwd_staged(const svit_pool_args* a3, PoolFwdStaged* g, size_t* lds_out) {
-  constexpr size_t LDS_MAX = SVIT_PS_LDS_KB * 1024;
-  constexpr double SLOTS = SVIT_PS_SLOTS;
-  const int T = a3[0].T, BH = a3[0].B * a3[0].heads;
-  if (!pool_clip_span_ok(T, a3[0].H, a3[0].W, a3[0].n_obj, a3[0].heads)) return false;
-  const PfPlanKey key = {{BH, T, a3[0].H, a3[0].W, a3[0].stride_hw, a3[1].stride_hw, a3[2].stride_hw, 1}};
-  {
-    std::lock_guard<std::mutex> lk(g_ps_plan_mu);
-    for (const auto& e : g_ps_plans)
-      if (e.key == key) { *g = e.plan; *lds_out = e.lds; return e.ok; }
-  }
-  int se[3], Ho[3], Wo[3];
+struct PoolChunkPlan {
+  int ok;
+  int n_per[3], r_per[3];        // planes / rows per chunk, per tensor
+  int t_chunks[3], y_chunks[3];  // chunks along t / y
+  int order[3], first_item[4];   // tensors in launch order (longest items first: the dispatcher fills the second slot of every
+                                 //  CU with the shorter ones) / item ranges of order[0..2]
+  int lds, max_chunks;           // dynamic LDS bytes of the launch / max over the tensors of t_chunks * y_chunks
+};
+template <class K> static void chunk_plan_into(const PoolChunkPlan& p, K* k) {
   for (int i = 0; i < 3; ++i) {
-    const int s = a3[i].stride_hw;
-    se[i] = s >= 3 ? 3 : s;
-    Ho[i] = (a3[i].H - 1) / s + 1;
-    Wo[i] = (a3[i].W - 1) / s + 1;
+    k->n_per[i] = p.n_per[i]; k->r_per[i] = p.r_per[i]; k->t_chunks[i] = p.t_chunks[i]; k->y_chunks[i] = p.y_chunks[i];
+    k->order[i] = p.order[i];
   }
-  auto lds_of = [&](int i, int n, int r) { return ((size_t)(n + 2) * ps_plane_bytes(se[i], r, a3[i].W, Wo[i]) + 1023) / 1024 * 1024; };
-  auto item_us = [&](int i, int n, int r) {
-    return 3.0 + 0.08 * (double)(lds_of(i, n, r) / 1024) / 4.0 + std::ceil((double)n * r * Wo[i] / PS_SLOTS) * 0.27 + 1.0;
-  };
+  for (int j = 0; j < 4; ++j) k->first_item[j] = p.first_item[j];
+}
+
+template <class M> static PoolChunkPlan pool_chunk_search(const M& m, int T, int BH, size_t lds_max, size_t lds_min, double slots) {
+  PoolChunkPlan p = {};
+  // candidate (n, r) per tensor: every n, r = ceil(extent / k)
   auto candidates = [&](int i, std::vector<PfTensorPlan>* out) {
     for (int n = 1; n <= T; ++n) {
       int last_r = -1;
-      for (int k = 1; k <= Ho[i]; ++k) {
-        const int r = (Ho[i] + k - 1) / k;
+      for (int k = 1; k <= m.ext[i]; ++k) {
+        const int r = (m.ext[i] + k - 1) / k;
         if (r == last_r) continue;
         last_r = r;
-        if (lds_of(i, n, r) <= LDS_MAX) out->push_back({n, r});
+        if (m.lds_of(i, n, r) <= lds_max) out->push_back({n, r});
       }
     }
   };
-  PsPlanEntry e;
-  e.key = key;
-  e.lds = 0;
-  e.ok = false;
   std::vector<PfTensorPlan> cq, c1, c2, ckv;
   candidates(0, &cq);
   candidates(1, &c1);
@@ -2274,125 +2288,242 @@ static bool plan_fwd_staged(const svit_pool_args* a3, PoolFwdStaged* g, size_t* 
   for (const auto& x : c1)
     for (const auto& y : c2)
       if (x.n == y.n && x.r == y.r) ckv.push_back(x);
-  if (se[1] != se[2] || Ho[1] != Ho[2]) ckv = c1.size() < c2.size() ? c1 : c2;
-  if (!cq.empty() && !ckv.empty()) {
-    double best = 1e300;
-    PfTensorPlan bq = cq[0], bkv = ckv[0];
-    for (const auto& pq : cq)
-      for (const auto& pkv : ckv) {
-        const PfTensorPlan pl[3] = {pq, pkv, pkv};
-        double items = 0, sum = 0, longest = 0;
-        bool fits = true;
-        for (int i = 0; i < 3; ++i) {
-          if (lds_of(i, pl[i].n, pl[i].r) > LDS_MAX) { fits = false; break; }
-          const int tc = (T + pl[i].n - 1) / pl[i].n, yc = (Ho[i] + pl[i].r - 1) / pl[i].r;
-          items += 3.0 * BH * tc * yc;
-          sum += 3.0 * BH * tc * yc * item_us(i, pl[i].n, pl[i].r);
-          longest = std::max(longest, item_us(i, pl[i].n, pl[i].r));
-        }
-        if (!fits) continue;
-        const double est = items <= SLOTS ? std::max(longest, sum / SLOTS) : sum / SLOTS + 0.5 * longest;
-        if (est < best) { best = est; bq = pq; bkv = pkv; }
+  if (m.cls[1] != m.cls[2] || m.ext[1] != m.ext[2]) ckv = c1.size() < c2.size() ? c1 : c2;      // (not the model's case: take the tighter list)
+  if (cq.empty() || ckv.empty()) return p;
+  double best = 1e300;
+  PfTensorPlan bq = cq[0], bkv = ckv[0];
+  for (const auto& pq : cq)
+    for (const auto& pkv : ckv) {
+      const PfTensorPlan pl[3] = {pq, pkv, pkv};
+      double items = 0, sum = 0, longest = 0;
+      bool fits = true;
+      for (int i = 0; i < 3 && fits; ++i) {
+        if (m.lds_of(i, pl[i].n, pl[i].r) > lds_max) { fits = false; break; }
+        const int tc = (T + pl[i].n - 1) / pl[i].n, yc = (m.ext[i] + pl[i].r - 1) / pl[i].r;
+        items += 3.0 * BH * tc * yc;
+        m.cost(i, pl[i], tc, yc, &sum, &longest);
       }
-    if (best < 1e300) {
-      const PfTensorPlan pl[3] = {bq, bkv, bkv};
-      double len[3];
-      size_t lds = 0;
-      for (int i = 0; i < 3; ++i) {
-        e.plan.n_per[i] = pl[i].n;
-        e.plan.r_per[i] = pl[i].r;
-        e.plan.t_chunks[i] = (T + pl[i].n - 1) / pl[i].n;
-        e.plan.y_chunks[i] = (Ho[i] + pl[i].r - 1) / pl[i].r;
-        lds = std::max(lds, lds_of(i, pl[i].n, pl[i].r));
-        len[i] = item_us(i, pl[i].n, pl[i].r);
-      }
-      int ord[3] = {0, 1, 2};
-      std::sort(ord, ord + 3, [&](int x, int y) { return len[x] > len[y] || (len[x] == len[y] && x < y); });
-      int first = 0;
-      for (int j = 0; j < 3; ++j) {
-        e.plan.order[j] = ord[j];
-        e.plan.first_item[j] = first;
-        first += 3 * BH * e.plan.t_chunks[ord[j]] * e.plan.y_chunks[ord[j]];
-      }
-      e.plan.first_item[3] = first;
-      e.lds = lds;
-      e.ok = true;
+      if (!fits || !m.admit(pq, pkv)) continue;
+      const double est = items <= slots ? std::max(longest, sum / slots) : sum / slots + 0.5 * longest;
+      if (est < best) { best = est; bq = pq; bkv = pkv; }
     }
+  if (best >= 1e300) return p;
+  const PfTensorPlan pl[3] = {bq, bkv, bkv};
+  size_t lds = lds_min;
+  double len[3];
+  p.max_chunks = 1;
+  for (int i = 0; i < 3; ++i) {
+    p.n_per[i] = pl[i].n;
+    p.r_per[i] = pl[i].r;
+    p.t_chunks[i] = (T + pl[i].n - 1) / pl[i].n;
+    p.y_chunks[i] = (m.ext[i] + pl[i].r - 1) / pl[i].r;
+    p.max_chunks = std::max(p.max_chunks, p.t_chunks[i] * p.y_chunks[i]);
+    lds = std::max(lds, m.lds_of(i, pl[i].n, pl[i].r));
+    len[i] = m.item_us(i, pl[i].n, pl[i].r);
   }
+  int ord[3] = {0, 1, 2};
+  std::sort(ord, ord + 3, [&](int x, int y) { return len[x] > len[y] || (len[x] == len[y] && x < y); });
+  int first = 0;
+  for (int j = 0; j < 3; ++j) {
+    p.order[j] = ord[j];
+    p.first_item[j] = first;
+    first += 3 * BH * p.t_chunks[ord[j]] * p.y_chunks[ord[j]];
+  }
+  p.first_item[3] = first;
+  p.lds = (int)lds;
+  p.ok = 1;
+  return p;
+}
+
+// Staged conv forward: output planes (n) and output rows (r) per chunk so that (n + 2) planes of the r-row image fit LDS.
+// Item time: staging 3 us + 0.08 us per 1-KiB piece and wave, 0.27 us per 16-output step (27 reads + 54 dot2), ~1 us of tail.
+#ifndef SVIT_PS_LDS_KB      // LDS budget of a staged-forward workgroup / resident workgroups the planner counts on.  Swept in
+#define SVIT_PS_LDS_KB 79   // diagnostic builds (profiles/r05_pool_fwd_staged.txt): 256 threads x 52 KB x 3 per CU 255 us over blocks 0-3,
+#define SVIT_PS_SLOTS 512   // 256 x 79 KB x 2: 238, 512 x 79 KB x 2: 232 (default), 1024 x 156 KB x 1: 287
+#endif
+struct PsChunkModel {
+  int BH, W, cls[3], ext[3], Wo[3];      // cls: stride class (1, 2, 3 = any stride >= 3); ext: output rows
+  size_t lds_of(int i, int n, int r) const { return ((size_t)(n + 2) * ps_plane_bytes(cls[i], r, W, Wo[i]) + 1023) / 1024 * 1024; }
+  double item_us(int i, int n, int r) const {
+    return 3.0 + 0.08 * (double)(lds_of(i, n, r) / 1024) / 4.0 + std::ceil((double)n * r * Wo[i] / PS_SLOTS) * 0.27 + 1.0;
+  }
+  void cost(int i, PfTensorPlan p, int tc, int yc, double* sum, double* longest) const {
+    *sum += 3.0 * BH * tc * yc * item_us(i, p.n, p.r);
+    *longest = std::max(*longest, item_us(i, p.n, p.r));
+  }
+  bool admit(PfTensorPlan, PfTensorPlan) const { return true; }
+};
+static PoolChunkPlan search_fwd_staged(const PoolGeom& g) {
+  PsChunkModel m = {g.B * g.heads, g.W[0]};
+  for (int i = 0; i < 3; ++i) {
+    const PoolOut o = pool_out(g.T[0], g.H[0], g.W[0], g.n_obj[0], g.s[i]);
+    m.cls[i] = pf_class(g.s[i]);
+    m.ext[i] = o.Ho;
+    m.Wo[i] = o.Wo;
+  }
+  return pool_chunk_search(m, g.T[0], m.BH, SVIT_PS_LDS_KB * 1024, 0, SVIT_PS_SLOTS);
+}
+
+// Fused conv backward: input planes (n) and unit rows (r) per chunk, two workgroups per CU.  Item time, from the in-kernel
+// stamps of round 5 (profiles/r05_pool_bwd_stamps.txt, MI355X): staging 3 us + 0.08 us per 1-KiB piece and wave, then
+// ceil(planes x units / 16 thread slots) steps of 0.47 us (stride 1: one token per unit), 0.96 us (stride 2: four tokens -- four
+// loads and four stores -- per unit) or ~2 us (stride >= 3: nine), 2.5 us of tail (+ 1.5 us for the cls / object rows of chunk 0).
+// The last chunk along t and along y is ragged and costed as such.  No plan where not even one unit row of three planes fits;
+// a candidate past 4096 partial rows per tensor (batch*heads x chunks) is not admitted.
+struct PfChunkModel {
+  int T, BH, cls[3], ext[3], UC[3], Wo[3];           // ext / UC: rows / columns of units of a plane
+  double step_us[3];
+  size_t lds_of(int i, int n, int r) const { return ((size_t)(n + 2) * pf_plane_bytes(pf_image_rows(cls[i], r), Wo[i]) + 1023) / 1024 * 1024; }
+  double item_us(int i, int n, int r, bool first = false) const {
+    return 3.0 + 0.08 * (double)(lds_of(i, n, r) / 1024) / 4.0 + std::ceil((double)n * r * UC[i] / PF_SLOTS) * step_us[i] + 2.5 +
+           (first ? 1.5 : 0.0);
+  }
+  void cost(int i, PfTensorPlan p, int tc, int yc, double* sum, double* longest) const {
+    const int nl = T - (tc - 1) * p.n, rl = ext[i] - (yc - 1) * p.r;
+    *sum += 3.0 * BH * ((tc - 1) * (yc - 1) * item_us(i, p.n, p.r, false) + (tc - 1) * item_us(i, p.n, rl, false) +
+                        (yc - 1) * item_us(i, nl, p.r, false) + item_us(i, nl, rl, false) + 1.5);
+    *longest = std::max(*longest, item_us(i, p.n, p.r, tc * yc == 1));
+  }
+  bool admit(PfTensorPlan pq, PfTensorPlan pkv) const {
+    return (long)BH * std::max((T + pq.n - 1) / pq.n * ((ext[0] + pq.r - 1) / pq.r),
+                               (T + pkv.n - 1) / pkv.n * ((ext[1] + pkv.r - 1) / pkv.r)) <= 4096;
+  }
+};
+static PoolChunkPlan search_bwd_fused(const PoolGeom& g) {
+  constexpr size_t LDS_MAX = 79 * 1024;       // two workgroups per CU (the image is staged in whole 1-KiB pieces)
+  PfChunkModel m = {g.T[0], g.B * g.heads};
+  for (int i = 0; i < 3; ++i) {
+    const PoolOut o = pool_out(g.T[0], g.H[0], g.W[0], g.n_obj[0], g.s[i]);
+    m.Wo[i] = o.Wo;
+    m.cls[i] = pf_class(g.s[i]);
+    m.ext[i] = pf_unit_rows(m.cls[i], g.H[0], o.Ho);
+    m.UC[i] = m.cls[i] == 1 ? g.W[0] : m.cls[i] == 2 ? (g.W[0] + 1) / 2 : o.Wo;
+    m.step_us[i] = m.cls[i] == 1 ? 0.47 : m.cls[i] == 2 ? 0.96 : 2.0;
+    if (3 * (size_t)pf_plane_bytes(pf_image_rows(m.cls[i], 1), o.Wo) + 1023 > LDS_MAX) return PoolChunkPlan{};
+  }
+  return pool_chunk_search(m, m.T, m.BH, LDS_MAX, 4 * 16 * 54 * sizeof(float), 512.0);
+}
+
+// A search costs ~1 ms of host time and its result is a pure function of the key -- batch*heads, T, H, W, the three strides,
+// kind -- so it is memoised (a training step has at most 16 distinct geometries per kind; the table is append-only,
+// mutex-guarded, and holds no device state).  false: no plan (a clip past the descriptor span, an image that does not fit).
+enum { POOL_PLAN_BWD = 0, POOL_PLAN_STAGED = 1 };
+struct PfPlanKey { int v[8]; bool operator==(const PfPlanKey& o) const { for (int i = 0; i < 8; ++i) if (v[i] != o.v[i]) return false; return true; } };
+struct PfPlanEntry { PfPlanKey key; PoolChunkPlan plan; };
+static std::mutex g_pf_plan_mu;
+static std::vector<PfPlanEntry> g_pf_plans;
+static bool pool_chunk_plan(const PoolGeom& g, int kind, PoolChunkPlan* out) {
+  *out = {};
+  if (!pool_clip_span_ok(g.T[0], g.H[0], g.W[0], g.n_obj[0], g.heads)) return false;
+  const PfPlanKey key = {{g.B * g.heads, g.T[0], g.H[0], g.W[0], g.s[0], g.s[1], g.s[2], kind}};
   {
-    std::lock_guard<std::mutex> lk(g_ps_plan_mu);
-    if (g_ps_plans.size() < 256) g_ps_plans.push_back(e);
+    std::lock_guard<std::mutex> lk(g_pf_plan_mu);
+    for (const auto& e : g_pf_plans)
+      if (e.key == key) { *out = e.plan; return out->ok; }
   }
-  *g = e.plan; *lds_out = e.lds;
-  return e.ok;
+  *out = kind == POOL_PLAN_STAGED ? search_fwd_staged(g) : search_bwd_fused(g);
+  std::lock_guard<std::mutex> lk(g_pf_plan_mu);
+  if (g_pf_plans.size() < 256) g_pf_plans.push_back({key, *out});
+  return out->ok;
 }
 
-static int pool_ln_fwd_qkv_kernels(const svit_pool_args* a3, const uint32_t* const* sel3, void* stream, int* q_on_slab);
-
-// rel-pos columns of the q tensor (svit_pool_args.relq_*): the slab LayerNorm kernel writes them itself; on any
-// other path the product + gather runs as its own launch (svit_gemm_nt, SVIT_EPI_RELQ) right behind the pooling
-static int pool_ln_fwd_qkv_impl(const svit_pool_args* a3, const uint32_t* const* sel3, void* stream) {
-  if (!a3) return SVIT_ERR_ARG;
-  const svit_pool_args& q = a3[0];
-  if (q.relq_R) {
-    if (!q.relq_map || q.relq_lpad <= 0 || q.relq_lpad % 96 != 0 || q.which != 0 || q.mode != 0 ||
-        (q.ld_out != 128 && q.ld_out != 160) || (((uintptr_t)q.relq_R | (uintptr_t)q.relq_map) & 15))
-      return SVIT_ERR_ARG;
-  }
-  int q_on_slab = 0;
-  if (int rc = pool_ln_fwd_qkv_kernels(a3, sel3, stream, &q_on_slab)) return rc;
-  if (q.relq_R && !q_on_slab) {
-    const int s = q.stride_hw, Nout = 1 + q.T * ((q.H - 1) / s + 1) * ((q.W - 1) / s + 1) + q.n_obj;
-    svit_gemm_args g = {};
-    g.A = q.out; g.lda = q.ld_out;
-    g.W = q.relq_R; g.ldw = HD;
-    g.M = q.B * q.heads * Nout; g.N = (q.relq_lpad + 95) / 96 * 96; g.K = HD;
-    g.epilogue = SVIT_EPI_RELQ;
-    g.relq_map = q.relq_map; g.relq_out = q.out; g.relq_ld = q.ld_out;
-    g.relq_extra = q.ld_out - HD; g.relq_rows = Nout; g.relq_scale = q.relq_scale;
-    return svit_gemm_nt(&g, stream);
-  }
-  return SVIT_OK;
+// ---- forward of q, k, v: geometry -> choice -> launches ----
+enum { POOL_PATH_FRAME = 0, POOL_PATH_MFMA, POOL_PATH_SLAB, POOL_PATH_STAGED, POOL_PATH_STREAM };     // PoolFwdChoice.path
+enum { POOL_RELQ_NOBODY = 0, POOL_RELQ_SLAB_LN, POOL_RELQ_GEMM };                                       // PoolFwdChoice.relq
+enum { POOL_KERNEL_FRAME = 0, POOL_KERNEL_MFMA, POOL_KERNEL_SLAB, POOL_KERNEL_SLAB_LN, POOL_KERNEL_STAGED, POOL_KERNEL_FWD3 };
+struct PoolLaunch { int kernel; unsigned gx, gy, gz, block, lds; };
+// the kernel structs hold what the chooser decides (plans, skip flags); their pointers are the launch functions' to fill
+struct PoolFwdChoice {
+  int path;
+  int relq;                  // who writes q's rel-pos columns: nobody, pool_slab_ln_kernel, the trailing SVIT_EPI_RELQ GEMM
+  int n_launch;
+  PoolLaunch launch[3];
+  PoolFrame3 frame;
+  int frame_img_bytes;
+  PoolSlab3 slab;            // plan[i].on: pool_slab_ln_kernel normalises tensor i (slab and staged paths)
+  PoolFwdStaged staged;
+  PoolFwd3 fwd3;             // skip[i] = slab.plan[i].on
+};
+static void add_launch(PoolFwdChoice* c, int kernel, dim3 grid, unsigned block, size_t lds) {
+  c->launch[c->n_launch++] = {kernel, grid.x, grid.y, grid.z, block, (unsigned)lds};
 }
 
-static int pool_ln_fwd_qkv_kernels(const svit_pool_args* a3, const uint32_t* const* sel3, void* stream, int* q_on_slab) {
-  if (!a3) return SVIT_ERR_ARG;
-  PoolFwd3 g;
+// pool_frame_fwd_kernel: bands of R output rows whose image fits FR_IMG_MAX; false where one row does not fit
+static bool choose_frame(const PoolGeom& g, PoolFwdChoice* c) {
+  PoolFrame3& fg = c->frame;
+  size_t img = 0;
+  double cost[3], cost_sum = 0.0;
+  for (int i = 0; i < 3; ++i) {
+    const int se = pf_class(g.s[i]);
+    const PoolOut o = pool_out(g, i);
+    int R = o.Ho;
+    while (R > 1 && fr_image_bytes(se, R, g.W[i], o.Wo) > FR_IMG_MAX) --R;
+    if (fr_image_bytes(se, R, g.W[i], o.Wo) > FR_IMG_MAX) return false;
+    const int chunks = (o.Ho + R - 1) / R;
+    R = (o.Ho + chunks - 1) / chunks;
+    fg.r_per[i] = R;
+    fg.y_chunks[i] = chunks;
+    fg.n_items[i] = g.B * g.heads * chunks;
+    const size_t ib = fr_image_bytes(se, R, g.W[i], o.Wo);
+    img = std::max(img, ib);
+    // item time (tools/pool_frame_stamps.py): ~0.03 us per 1-KiB piece to issue, ~0.7 us at the barrier, ~1 us per 64-token pass
+    const int passes = (R * o.Wo + 1 + g.n_obj[i] + 63) / 64;
+    cost[i] = fg.n_items[i] * (0.7 + 0.03 * (double)(ib >> 10) + 1.0 * passes);
+    cost_sum += cost[i];
+  }
+  // workgroups per tensor in proportion to its work (one persistent workgroup per CU; each reads ONE tensor's weights)
+  int wgs[3], total_wgs = 256;
+  for (int i = 0; i < 3; ++i) wgs[i] = std::max(1, std::min(fg.n_items[i], (int)(total_wgs * cost[i] / cost_sum + 0.5)));
+  while (wgs[0] + wgs[1] + wgs[2] > total_wgs) {
+    int big = 0;
+    for (int i = 1; i < 3; ++i) if (wgs[i] > wgs[big]) big = i;
+    --wgs[big];
+  }
+  for (int i = 0; i < 3; ++i) fg.wg_first[i + 1] = fg.wg_first[i] + wgs[i];
+  c->frame_img_bytes = (int)((img + 1023) / 1024 * 1024);
+  add_launch(c, POOL_KERNEL_FRAME, dim3((unsigned)fg.wg_first[3]), FR_NT, FR_HEAD + 2 * (size_t)c->frame_img_bytes);
+  return true;
+}
+
+// pool_slab_ln_kernel over the tensors with slab.plan[i].on
+#ifndef SVIT_SLAB_LN_WANT
+#define SVIT_SLAB_LN_WANT 2048      // (in-step A/B of round 4: 1024 -> 2048 is -0.02..-0.04 ms)
+#endif
+static void add_slab_ln(const PoolGeom& g, PoolFwdChoice* c) {
+  int blocks = 1;
+  for (int i = 0; i < 3; ++i)
+    if (c->slab.plan[i].on) blocks = std::max(blocks, (int)persistent_x((pool_out(g, i).Nout + 63) / 64, g.B * g.heads * 3, SVIT_SLAB_LN_WANT));
+  const size_t lds = c->relq == POOL_RELQ_SLAB_LN ? (size_t)64 * SLN_QROW + (size_t)64 * g.relq_lpad * 2 : 0;
+  add_launch(c, POOL_KERNEL_SLAB_LN, dim3(blocks, g.B * g.heads, 3), 256, lds);
+}
+
+// pool_ln_fwd3_kernel over the other tensors: streaming, or the LDS-tiled stencil at stride 1 where tables were given
+static void add_fwd3(const PoolGeom& g, PoolFwdChoice* c) {
   unsigned gx = 1;
   size_t lds = 0;
-  PoolSlab3 sg;
-  unsigned sgx = 0;
-  size_t slds = 0;
-  int n_slab = 0, ln_blocks = 1;
   for (int i = 0; i < 3; ++i) {
-    const int rc = check_pool_fwd(&a3[i]);
-    if (rc) return rc;
-    if (a3[i].B != a3[0].B || a3[i].heads != a3[0].heads) return SVIT_ERR_SHAPE;
-    sg.p[i] = a3[i];
-    sg.sel[i] = sel3 ? sel3[i] : nullptr;
-    sg.plan[i] = sel3 ? plan_slab(a3[i]) : SlabPlan{0, 0, 0, 0, 0};
-    g.skip[i] = sg.plan[i].on;
-    if (i == 0) {
-      const bool fuse = a3[0].relq_lpad <= 288;       // (the product tile of 64 tokens must fit LDS)
-      if (!fuse) sg.p[0].relq_R = nullptr;
-      *q_on_slab = sg.plan[0].on && fuse;
+    if ((c->fwd3.skip[i] = c->slab.plan[i].on)) continue;
+    unsigned x = persistent_x((pool_out(g, i).Nout + 63) / 64, g.B * g.heads * 3);
+    if (g.s[i] == 1 && g.sel) {
+      c->fwd3.plan[i] = plan_tiled(g.T[i], g.H[i], g.W[i], g.n_obj[i], g.B * g.heads);
+      x = (unsigned)(c->fwd3.plan[i].n_wgs + c->fwd3.plan[i].n_special);
+      lds = std::max(lds, tiled_lds_bytes(g.W[i]));
     }
-    if (sg.plan[i].on) {
-      const SlabPlan& pl = sg.plan[i];
-      const int s = a3[i].stride_hw;
-      const int pin = std::min(a3[i].T, pl.TC + 2), rin = std::min(a3[i].H, s * (pl.YC - 1) + 3);
-      const size_t need = ((size_t)pin * rin * a3[i].W * 48 + 1023) / 1024 * 1024 + 64 + 96;
-      if (need > slds) slds = need;
-      if ((unsigned)(pl.nt * pl.ny) > sgx) sgx = pl.nt * pl.ny;
-      const int nout = 1 + a3[i].T * ((a3[i].H - 1) / s + 1) * ((a3[i].W - 1) / s + 1) + a3[i].n_obj;
-#ifndef SVIT_SLAB_LN_WANT
-#define SVIT_SLAB_LN_WANT 2048
-#endif
-      constexpr long ln_want = SVIT_SLAB_LN_WANT;    // (in-step A/B of round 4: 1024 -> 2048 is -0.02..-0.04 ms)
-      ln_blocks = std::max(ln_blocks, (int)persistent_x((nout + 63) / 64, a3[0].B * a3[0].heads * 3, ln_want));
-      ++n_slab;
-    }
+    gx = std::max(gx, x);
   }
+  add_launch(c, POOL_KERNEL_FWD3, dim3(gx, g.B * g.heads, 3), 256, lds);
+}
+
+// Reads nothing but the geometry and the knobs.  Precedence: frame; slab, with pool_ln_fwd3_kernel for the tensors that are
+// not on the slab; staged; pool_ln_fwd3_kernel.  q's rel-pos columns: pool_slab_ln_kernel writes them where it normalises q and
+// the product tile of 64 tokens fits LDS (relq_lpad <= 288), else svit_gemm_nt with SVIT_EPI_RELQ right behind the pooling.
+static PoolFwdChoice pool_fwd_choose(const PoolGeom& g) {
+  PoolFwdChoice c = {};
+  const int BH = g.B * g.heads;
+  const int relq_gemm = g.relq_lpad ? POOL_RELQ_GEMM : POOL_RELQ_NOBODY;
+  const int relq_ln = g.relq_lpad && g.relq_lpad <= 288 ? POOL_RELQ_SLAB_LN : relq_gemm;
+  c.path = POOL_PATH_STREAM;
+  c.relq = relq_gemm;
   // round 5: one-plane volumes (frames pass, image ranks): conv + LayerNorm in one launch from an LDS-staged plane;
   // svit_debug_set_pool(3, 0) keeps the paths below (A/B)
   // (round 6: default 2 = every T = 1 pass, training steps of the image ranks included.  Round 5 kept those on the streaming
@@ -2402,139 +2533,165 @@ static int pool_ln_fwd_qkv_kernels(const svit_pool_args* a3, const uint32_t* con
   //  0.9789 on that tensor (profiles/r06_yardstick.txt): both orders sit well inside what a correct bf16 implementation
   //  produces, and the test now measures against the yardstick.  1 = no-grad passes only, 0 = never.)
   const int fr_mode = svit_knob(SVIT_K_POOL_FRAME);
-  if (a3[0].T == 1 && a3[1].T == 1 && a3[2].T == 1 && (fr_mode == 2 || (fr_mode == 1 && !a3[0].pre && !a3[1].pre && !a3[2].pre)) &&
-      pool_clip_span_ok(1, a3[0].H, a3[0].W, a3[0].n_obj, a3[0].heads)) {
-    PoolFrame3 fg;
-    size_t img = 0;
-    bool ok = true;
-    double cost[3], cost_sum = 0.0;
-    for (int i = 0; i < 3 && ok; ++i) {
-      const int s = a3[i].stride_hw, se = s < 3 ? s : 3;
-      const int Ho = (a3[i].H - 1) / s + 1, Wo = (a3[i].W - 1) / s + 1;
-      int R = Ho;
-      while (R > 1 && fr_image_bytes(se, R, a3[i].W, Wo) > FR_IMG_MAX) --R;
-      if (fr_image_bytes(se, R, a3[i].W, Wo) > FR_IMG_MAX) { ok = false; break; }
-      const int chunks = (Ho + R - 1) / R;
-      R = (Ho + chunks - 1) / chunks;
-      fg.p[i] = a3[i];
-      fg.r_per[i] = R;
-      fg.y_chunks[i] = chunks;
-      fg.n_items[i] = a3[i].B * a3[i].heads * chunks;
-      const size_t ib = fr_image_bytes(se, R, a3[i].W, Wo);
-      img = std::max(img, ib);
-      // item time (tools/pool_frame_stamps.py): ~0.03 us per 1-KiB piece to issue, ~0.7 us at the barrier, ~1 us per 64-token pass
-      const int passes = (R * Wo + 1 + a3[i].n_obj + 63) / 64;
-      cost[i] = fg.n_items[i] * (0.7 + 0.03 * (double)(ib >> 10) + 1.0 * passes);
-      cost_sum += cost[i];
-    }
-    if (ok) {
-      // workgroups per tensor in proportion to its work (one persistent workgroup per CU; each reads ONE tensor's weights)
-      int wgs[3], total_wgs = 256;
-      for (int i = 0; i < 3; ++i) wgs[i] = std::max(1, std::min(fg.n_items[i], (int)(total_wgs * cost[i] / cost_sum + 0.5)));
-      while (wgs[0] + wgs[1] + wgs[2] > total_wgs) {
-        int big = 0;
-        for (int i = 1; i < 3; ++i) if (wgs[i] > wgs[big]) big = i;
-        --wgs[big];
-      }
-      fg.wg_first[0] = 0;
-      for (int i = 0; i < 3; ++i) fg.wg_first[i + 1] = fg.wg_first[i] + wgs[i];
-      const int img_bytes = (int)((img + 1023) / 1024 * 1024);
-      const size_t flds = FR_HEAD + 2 * (size_t)img_bytes;
-      static SvitOnce once_fr;
-      if (int rc = svit_max_lds_once(once_fr, (const void*)pool_frame_fwd_kernel, FR_HEAD + 2 * FR_IMG_MAX)) return rc;
-      hipLaunchKernelGGL(pool_frame_fwd_kernel, dim3((unsigned)fg.wg_first[3]), dim3(FR_NT), flds, (hipStream_t)stream, fg, img_bytes);
-      SVIT_LAUNCH_CHECK();
-      *q_on_slab = 0;
-      return SVIT_OK;
-    }
+  if (g.T[0] == 1 && g.T[1] == 1 && g.T[2] == 1 && (fr_mode == 2 || (fr_mode == 1 && !g.pre[0] && !g.pre[1] && !g.pre[2])) &&
+      pool_clip_span_ok(1, g.H[0], g.W[0], g.n_obj[0], g.heads) && choose_frame(g, &c)) {
+    c.path = POOL_PATH_FRAME;
+    return c;
+  }
+  int n_slab = 0;
+  for (int i = 0; i < 3; ++i) {
+    if (g.sel) c.slab.plan[i] = plan_slab(g, i);
+    n_slab += c.slab.plan[i].on;
   }
   if (n_slab) {
     // round 4: the conv of the slab planes on the matrix pipe (pool_mfma_fwd_kernel) where its geometry holds for
     // all three tensors: W <= 14 (16 slots per image row with both x halos), T a multiple of 4 (t-quads), the
     // 16-channel image within the LDS of a CU; svit_debug_set_pool(0, 1) keeps the VALU slab kernel (A/B)
     bool mfma = n_slab == 3 && svit_knob(SVIT_K_POOL_FWD) != 1;
-    size_t mlds = 0;
+    size_t mlds = 0, slds = 0;
     for (int i = 0; i < 3 && mfma; ++i) {
-      mfma = a3[i].W <= 14 && a3[i].T % 4 == 0 && a3[i].T == a3[0].T && a3[i].H == a3[0].H;
-      mlds = std::max(mlds, pm_lds_bytes(a3[i].T, a3[i].H));
+      mfma = g.W[i] <= 14 && g.T[i] % 4 == 0 && g.T[i] == g.T[0] && g.H[i] == g.H[0];
+      mlds = std::max(mlds, pm_lds_bytes(g.T[i], g.H[i]));
     }
     if (mfma && mlds > 160 * 1024) mfma = false;
     // measured (tools/diag/pool_fwd_ab.sh, profiles/r04_pool_mfma_stencil.txt): ahead of the VALU slab kernel where its
     // 12 B heads workgroups are ONE round at two per CU (blocks 4-13 of 16x224^2: 24.6 against 28.4 us), level or
     // behind with more (blocks 14 / 15, 8 heads); svit_debug_set_pool(0, 3) forces it everywhere its geometry holds
-    if (mfma && svit_knob(SVIT_K_POOL_FWD) != 3 && ((long)a3[0].B * a3[0].heads * 12 > 512 || 2 * mlds > 160 * 1024)) mfma = false;
-    if (mfma) {
-      static SvitOnce once_mfma;
-      if (int rc = svit_max_lds_once(once_mfma, (const void*)pool_mfma_fwd_kernel, 160 * 1024)) return rc;
-      PoolMfma3 mg;
-      for (int i = 0; i < 3; ++i) mg.p[i] = a3[i];
-      hipLaunchKernelGGL(pool_mfma_fwd_kernel, dim3(a3[0].B * a3[0].heads * 2 * 6), dim3(PM_NT), mlds,
-                         (hipStream_t)stream, mg);
-      SVIT_LAUNCH_CHECK();
-    } else {
-    static SvitOnce once_slab;
-    if (int rc = svit_max_lds_once(once_slab, (const void*)pool_slab_fwd_kernel, 80 * 1024)) return rc;
-    sg.max_chunks = (int)sgx;
-    hipLaunchKernelGGL(pool_slab_fwd_kernel, dim3(sgx * a3[0].B * a3[0].heads * 12), dim3(SLAB_NT), slds,
-                       (hipStream_t)stream, sg);
-    SVIT_LAUNCH_CHECK();
+    if (mfma && svit_knob(SVIT_K_POOL_FWD) != 3 && ((long)BH * 12 > 512 || 2 * mlds > 160 * 1024)) mfma = false;
+    for (int i = 0; i < 3; ++i) {
+      const SlabPlan& pl = c.slab.plan[i];
+      if (!pl.on) continue;
+      const int pin = std::min(g.T[i], pl.TC + 2), rin = std::min(g.H[i], g.s[i] * (pl.YC - 1) + 3);
+      slds = std::max(slds, ((size_t)pin * rin * g.W[i] * 48 + 1023) / 1024 * 1024 + 64 + 96);
+      c.slab.max_chunks = std::max(c.slab.max_chunks, pl.nt * pl.ny);
     }
-    const size_t ln_lds = (sg.plan[0].on && sg.p[0].relq_R) ? (size_t)64 * SLN_QROW + (size_t)64 * a3[0].relq_lpad * 2 : 0;
-    hipLaunchKernelGGL(pool_slab_ln_kernel, dim3(ln_blocks, a3[0].B * a3[0].heads, 3), dim3(256), ln_lds,
-                       (hipStream_t)stream, sg);
-    SVIT_LAUNCH_CHECK();
-    if (n_slab == 3) return SVIT_OK;
+    c.path = mfma ? POOL_PATH_MFMA : POOL_PATH_SLAB;
+    if (mfma) add_launch(&c, POOL_KERNEL_MFMA, dim3(BH * 2 * 6), PM_NT, mlds);
+    else add_launch(&c, POOL_KERNEL_SLAB, dim3(c.slab.max_chunks * BH * 12), SLAB_NT, slds);
+    if (c.slab.plan[0].on) c.relq = relq_ln;
+    add_slab_ln(g, &c);
+    if (n_slab < 3) add_fwd3(g, &c);
+    return c;
   }
   // round 5: no tensor took the slab path (planes past 14x14: blocks 0-3) and every tensor saves `pre` (a training step):
   // the staged conv forward (input staged once in LDS, every stride) + the row-wise LayerNorm launch of the slab path;
   // svit_debug_set_pool(2, 0) keeps the streaming kernel below (A/B)
-  if (n_slab == 0 && a3[0].H * a3[0].W > 196 && svit_knob(SVIT_K_POOL_FWD_LARGE) != 0 && a3[0].pre && a3[1].pre && a3[2].pre &&
-      a3[1].T == a3[0].T && a3[2].T == a3[0].T && a3[1].H == a3[0].H && a3[2].H == a3[0].H && a3[1].W == a3[0].W &&
-      a3[2].W == a3[0].W && a3[1].n_obj == a3[0].n_obj && a3[2].n_obj == a3[0].n_obj) {
-    PoolFwdStaged fg;
-    size_t flds = 0;
-    if (plan_fwd_staged(a3, &fg, &flds)) {
-      for (int i = 0; i < 3; ++i) fg.p[i] = a3[i];
-      static SvitOnce once_ps;
-      if (int rc = svit_max_lds_once(once_ps, (const void*)pool_fwd_staged_kernel, SVIT_PS_LDS_KB * 1024)) return rc;
-      hipLaunchKernelGGL(pool_fwd_staged_kernel, dim3((unsigned)fg.first_item[3]), dim3(PS_NT), flds, (hipStream_t)stream, fg);
-      SVIT_LAUNCH_CHECK();
-      int blocks = 1;
-      for (int i = 0; i < 3; ++i) {
-        const int s = a3[i].stride_hw;
-        const int nout = 1 + a3[i].T * ((a3[i].H - 1) / s + 1) * ((a3[i].W - 1) / s + 1) + a3[i].n_obj;
-        blocks = std::max(blocks, (int)persistent_x((nout + 63) / 64, a3[0].B * a3[0].heads * 3, SVIT_SLAB_LN_WANT));
-        sg.plan[i].on = 1;
-      }
-      *q_on_slab = sg.p[0].relq_R != nullptr;       // (already cleared above when the product tile does not fit)
-      const size_t ln_lds = sg.p[0].relq_R ? (size_t)64 * SLN_QROW + (size_t)64 * a3[0].relq_lpad * 2 : 0;
-      hipLaunchKernelGGL(pool_slab_ln_kernel, dim3(blocks, a3[0].B * a3[0].heads, 3), dim3(256), ln_lds, (hipStream_t)stream, sg);
-      SVIT_LAUNCH_CHECK();
-      return SVIT_OK;
-    }
+  PoolChunkPlan cp;
+  if (g.H[0] * g.W[0] > 196 && svit_knob(SVIT_K_POOL_FWD_LARGE) != 0 && g.pre[0] && g.pre[1] && g.pre[2] &&
+      g.T[1] == g.T[0] && g.T[2] == g.T[0] && g.H[1] == g.H[0] && g.H[2] == g.H[0] && g.W[1] == g.W[0] &&
+      g.W[2] == g.W[0] && g.n_obj[1] == g.n_obj[0] && g.n_obj[2] == g.n_obj[0] && pool_chunk_plan(g, POOL_PLAN_STAGED, &cp)) {
+    c.path = POOL_PATH_STAGED;
+    c.relq = relq_ln;
+    chunk_plan_into(cp, &c.staged);
+    add_launch(&c, POOL_KERNEL_STAGED, dim3((unsigned)cp.first_item[3]), PS_NT, cp.lds);
+    for (int i = 0; i < 3; ++i) c.slab.plan[i].on = 1;
+    add_slab_ln(g, &c);
+    return c;
   }
-  for (int i = 0; i < 3; ++i) {
-    g.p[i] = a3[i];
-    g.sel[i] = sel3 ? sel3[i] : nullptr;
-    g.plan[i].tiled = 0;
-    if (g.skip[i]) continue;
-    const int s = a3[i].stride_hw;
-    const int nout = 1 + a3[i].T * ((a3[i].H - 1) / s + 1) * ((a3[i].W - 1) / s + 1) + a3[i].n_obj;
-    unsigned x = persistent_x((nout + 63) / 64, a3[0].B * a3[0].heads * 3);
-    if (s == 1 && g.sel[i]) {
-      g.plan[i] = plan_tiled(a3[i].T, a3[i].H, a3[i].W, a3[i].n_obj, a3[i].B * a3[i].heads);
-      x = (unsigned)(g.plan[i].n_wgs + g.plan[i].n_special);
-      const size_t need = tiled_lds_bytes(a3[i].W);
-      if (need > lds) lds = need;
-    }
-    if (x > gx) gx = x;
-  }
-  static SvitOnce once;
-  if (int rc = svit_max_lds_once(once, (const void*)pool_ln_fwd3_kernel, 64 * 1024)) return rc;
-  hipLaunchKernelGGL(pool_ln_fwd3_kernel, dim3(gx, a3[0].B * a3[0].heads, 3), dim3(256), lds,
-                     (hipStream_t)stream, g);
+  add_fwd3(g, &c);
+  return c;
+}
+
+// the launch functions execute a choice (svit_max_lds_once: the largest dynamic LDS a kernel is ever launched with)
+struct PoolCall { const svit_pool_args* a3; const uint32_t* const* sel3; hipStream_t stream; };
+template <class K> static K with_args(K k, const PoolCall& call) {
+  for (int i = 0; i < 3; ++i) k.p[i] = call.a3[i];
+  return k;
+}
+template <class K> static K with_args_sel(K k, const PoolCall& call) {
+  for (int i = 0; i < 3; ++i) k.sel[i] = call.sel3 ? call.sel3[i] : nullptr;
+  return with_args(k, call);
+}
+template <class K, class... A>
+static int pool_launch(K kernel, SvitOnce* once, size_t max_lds, const PoolLaunch& l, const PoolCall& call, const A&... args) {
+  if (int rc = once ? svit_max_lds_once(*once, (const void*)kernel, max_lds) : 0) return rc;
+  hipLaunchKernelGGL(kernel, dim3(l.gx, l.gy, l.gz), dim3(l.block), l.lds, call.stream, args...);
   SVIT_LAUNCH_CHECK();
   return SVIT_OK;
+}
+static int launch_frame(const PoolFwdChoice& c, const PoolLaunch& l, const PoolCall& call) {
+  static SvitOnce once;
+  return pool_launch(pool_frame_fwd_kernel, &once, FR_HEAD + 2 * FR_IMG_MAX, l, call, with_args(c.frame, call), c.frame_img_bytes);
+}
+static PoolSlab3 slab_args(const PoolFwdChoice& c, const PoolCall& call) {
+  PoolSlab3 sg = with_args_sel(c.slab, call);
+  if (c.relq != POOL_RELQ_SLAB_LN) sg.p[0].relq_R = nullptr;
+  return sg;
+}
+static int launch_slab_conv(const PoolFwdChoice& c, const PoolLaunch& l, const PoolCall& call) {      // MFMA or VALU
+  static SvitOnce once_mfma, once_slab;
+  if (l.kernel == POOL_KERNEL_MFMA) return pool_launch(pool_mfma_fwd_kernel, &once_mfma, 160 * 1024, l, call, with_args(PoolMfma3{}, call));
+  return pool_launch(pool_slab_fwd_kernel, &once_slab, 80 * 1024, l, call, slab_args(c, call));
+}
+static int launch_slab_ln(const PoolFwdChoice& c, const PoolLaunch& l, const PoolCall& call) {
+  return pool_launch(pool_slab_ln_kernel, nullptr, 0, l, call, slab_args(c, call));      // (at most 50 KiB: within the default limit)
+}
+static int launch_staged(const PoolFwdChoice& c, const PoolLaunch& l, const PoolCall& call) {
+  static SvitOnce once;
+  return pool_launch(pool_fwd_staged_kernel, &once, SVIT_PS_LDS_KB * 1024, l, call, with_args(c.staged, call));
+}
+static int launch_fwd3(const PoolFwdChoice& c, const PoolLaunch& l, const PoolCall& call) {
+  static SvitOnce once;
+  return pool_launch(pool_ln_fwd3_kernel, &once, 64 * 1024, l, call, with_args_sel(c.fwd3, call));
+}
+
+static int pool_ln_fwd_qkv_impl(const svit_pool_args* a3, const uint32_t* const* sel3, void* stream) {
+  if (!a3) return SVIT_ERR_ARG;
+  const svit_pool_args& q = a3[0];
+  if (q.relq_R) {
+    if (!q.relq_map || q.relq_lpad <= 0 || q.relq_lpad % 96 != 0 || q.which != 0 || q.mode != 0 ||
+        (q.ld_out != 128 && q.ld_out != 160) || (((uintptr_t)q.relq_R | (uintptr_t)q.relq_map) & 15))
+      return SVIT_ERR_ARG;
+  }
+  for (int i = 0; i < 3; ++i) {
+    if (int rc = check_pool_fwd(&a3[i])) return rc;
+    if (a3[i].B != a3[0].B || a3[i].heads != a3[0].heads) return SVIT_ERR_SHAPE;
+  }
+  const PoolFwdChoice c = pool_fwd_choose(pool_geom(a3, sel3 != nullptr));
+  const PoolCall call = {a3, sel3, (hipStream_t)stream};
+  for (int k = 0; k < c.n_launch; ++k) {
+    const PoolLaunch& l = c.launch[k];
+    const int rc = l.kernel == POOL_KERNEL_FRAME ? launch_frame(c, l, call)
+                 : l.kernel == POOL_KERNEL_SLAB_LN ? launch_slab_ln(c, l, call)
+                 : l.kernel == POOL_KERNEL_STAGED ? launch_staged(c, l, call)
+                 : l.kernel == POOL_KERNEL_FWD3 ? launch_fwd3(c, l, call) : launch_slab_conv(c, l, call);
+    if (rc) return rc;
+  }
+  if (c.relq != POOL_RELQ_GEMM) return SVIT_OK;
+  // rel-pos columns of the q tensor (svit_pool_args.relq_*): the product + gather as its own launch right behind the pooling
+  const int Nout = pool_out(q).Nout;
+  svit_gemm_args g = {};
+  g.A = q.out; g.lda = q.ld_out;
+  g.W = q.relq_R; g.ldw = HD;
+  g.M = q.B * q.heads * Nout; g.N = (q.relq_lpad + 95) / 96 * 96; g.K = HD;
+  g.epilogue = SVIT_EPI_RELQ;
+  g.relq_map = q.relq_map; g.relq_out = q.out; g.relq_ld = q.ld_out;
+  g.relq_extra = q.ld_out - HD; g.relq_rows = Nout; g.relq_scale = q.relq_scale;
+  return svit_gemm_nt(&g, stream);
+}
+
+// Host-only plan query (include/svit_hip.h, diagnostics): what the chooser and the chunk search above answer for a geometry.
+extern "C" int svit_debug_pool_plan(int kind, int B, int heads, int T, int H, int W, int n_obj, int sq, int sk, int sv,
+                                    int save_mask, int sel, int relq_lpad, int32_t* out, int n_out) {
+  if (!out || n_out < 24 || kind < 0 || kind > 2 || relq_lpad < 0) return SVIT_ERR_ARG;
+  PoolGeom g = pool_geom(B, heads, T, H, W, n_obj, sq, sk, sv);
+  for (int i = 0; i < 3; ++i) {
+    if (check_pool_dims(B, heads, T, H, W, n_obj, g.s[i])) return SVIT_ERR_SHAPE;
+    g.pre[i] = (save_mask >> i) & 1;
+  }
+  g.sel = sel != 0;
+  g.relq_lpad = relq_lpad;
+  if (kind == 0) {       // path, relq, n_launch, then per launch: kernel, grid x / y / z, block, dynamic LDS bytes
+    const PoolFwdChoice c = pool_fwd_choose(g);
+    static_assert(offsetof(PoolFwdChoice, frame) >= 21 * sizeof(int32_t) && sizeof(PoolLaunch) == 6 * sizeof(int32_t), "layout");
+    memcpy(out, &c, 21 * sizeof(int32_t));
+    return 3 + 6 * c.n_launch;
+  }
+  PoolChunkPlan p;       // the fields of PoolChunkPlan in their order
+  static_assert(sizeof p == 22 * sizeof(int32_t), "layout");
+  pool_chunk_plan(g, kind == 1 ? POOL_PLAN_STAGED : POOL_PLAN_BWD, &p);
+  memcpy(out, &p, sizeof p);
+  return 22;
 }
 
 extern "C" int svit_pool_ln_fwd_qkv(const svit_pool_args* a3, void* stream) {
@@ -2564,6 +2721,14 @@ static int check_pool_ln_bwd(const svit_pool_ln_bwd_args* a) {
   return SVIT_OK;
 }
 
+// workgroups of the LayerNorm backward: >= 4 token groups each, 128..1024, and no more partial rows than the workspace holds
+static int64_t pool_ln_bwd_blocks(int64_t total, int64_t workspace_floats, int row_floats) {
+  int64_t blocks = (total + 255) / 256;
+  if (blocks < 128) blocks = (total + 63) / 64 < 128 ? (total + 63) / 64 : 128;
+  if (blocks > 1024) blocks = 1024;
+  return std::min(blocks, workspace_floats / row_floats);
+}
+
 extern "C" int svit_pool_ln_bwd_qkv(const svit_pool_ln_bwd_args* a3, void* stream) {
   if (!a3 || !a3[0].workspace) return SVIT_ERR_ARG;
   PoolLnBwd3 g;
@@ -2575,11 +2740,7 @@ extern "C" int svit_pool_ln_bwd_qkv(const svit_pool_ln_bwd_args* a3, void* strea
     const int64_t total = (int64_t)a3[i].B * a3[i].heads * a3[i].Nout;
     if (total > max_total) max_total = total;
   }
-  constexpr int tpb = 256;
-  int64_t blocks = (max_total + tpb - 1) / tpb;
-  if (blocks < 128) blocks = (max_total + 63) / 64 < 128 ? (max_total + 63) / 64 : 128;
-  if (blocks > 1024) blocks = 1024;
-  if (blocks > a3[0].workspace_floats / (6 * HD)) blocks = a3[0].workspace_floats / (6 * HD);
+  const int64_t blocks = pool_ln_bwd_blocks(max_total, a3[0].workspace_floats, 6 * HD);
   if (blocks < 1) return SVIT_ERR_ARG;
   hipLaunchKernelGGL(pool_ln_bwd3_kernel, dim3((unsigned)blocks, 3), dim3(256), 0,
                      (hipStream_t)stream, g);
@@ -2597,133 +2758,6 @@ extern "C" int svit_pool_ln_bwd_qkv(const svit_pool_ln_bwd_args* a3, void* strea
 #undef SVIT_POOL_STREAMING_PART
 #endif
 
-// Planner of the fused conv backward: input planes (n) and unit rows (R) per chunk for each tensor, so that the items (one per
-// batch*head, tensor, 32-channel group, t-chunk, y-chunk) are about equally long and fill the chip's slots (two workgroups
-// per CU).  Item time, from the in-kernel stamps of round 5 (profiles/r05_pool_bwd_stamps.txt, MI355X): staging 3 us + 0.08 us
-// per 1-KiB piece and wave, then ceil(planes x units / 16 thread slots) steps of 0.47 us (stride 1: one token per unit), 0.96 us
-// (stride 2: four tokens -- four loads and four stores -- per unit) or ~2 us (stride >= 3: nine), 2.5 us of tail (+ 1.5 us for
-// the cls / object rows of chunk 0).  Estimate of the launch = the longest item if everything is resident at once, else the
-// average load of a slot plus half an item.  Returns false where not even one unit row of three planes fits.
-static bool plan_bwd_fused(const svit_pool_dgrad_args* d3, PoolBwdFused* g, size_t* lds_out) {
-  constexpr size_t LDS_MAX = 79 * 1024;       // two workgroups per CU (the image is staged in whole 1-KiB pieces)
-  constexpr double SLOTS = 512.0;
-  const int T = d3[0].T, BH = d3[0].B * d3[0].heads;
-  if (!pool_clip_span_ok(T, d3[0].H, d3[0].W, d3[0].n_obj, d3[0].heads)) return false;
-  int sc[3], UR[3], UC[3], Wo[3];
-  double step_us[3];
-  for (int i = 0; i < 3; ++i) {
-    const int s = d3[i].stride_hw;
-    if (s < 1) return false;
-    const int Ho = (d3[i].H - 1) / s + 1;
-    Wo[i] = (d3[i].W - 1) / s + 1;
-    sc[i] = pf_class(s);
-    UR[i] = pf_unit_rows(sc[i], d3[i].H, Ho);
-    UC[i] = sc[i] == 1 ? d3[i].W : sc[i] == 2 ? (d3[i].W + 1) / 2 : Wo[i];
-    step_us[i] = sc[i] == 1 ? 0.47 : sc[i] == 2 ? 0.96 : 2.0;
-    if (3 * (size_t)pf_plane_bytes(pf_image_rows(sc[i], 1), Wo[i]) + 1023 > LDS_MAX) return false;
-  }
-  auto lds_of = [&](int i, int n, int r) { return ((size_t)(n + 2) * pf_plane_bytes(pf_image_rows(sc[i], r), Wo[i]) + 1023) / 1024 * 1024; };
-  auto item_us = [&](int i, int n, int r, bool first) {
-    return 3.0 + 0.08 * (double)(lds_of(i, n, r) / 1024) / 4.0 + std::ceil((double)n * r * UC[i] / PF_SLOTS) * step_us[i] + 2.5 +
-           (first ? 1.5 : 0.0);
-  };
-  // candidate (n, r) per tensor: every n, r = ceil(UR / k); k and v share a choice (same stride in every block of the model)
-  auto candidates = [&](int i, std::vector<PfTensorPlan>* out) {
-    for (int n = 1; n <= T; ++n) {
-      int last_r = -1;
-      for (int k = 1; k <= UR[i]; ++k) {
-        const int r = (UR[i] + k - 1) / k;
-        if (r == last_r) continue;
-        last_r = r;
-        if (lds_of(i, n, r) <= LDS_MAX) out->push_back({n, r});
-      }
-    }
-  };
-  std::vector<PfTensorPlan> cq, ckv;
-  candidates(0, &cq);
-  {
-    std::vector<PfTensorPlan> c1, c2;
-    candidates(1, &c1);
-    candidates(2, &c2);
-    for (const auto& x : c1)
-      for (const auto& y : c2)
-        if (x.n == y.n && x.r == y.r) ckv.push_back(x);
-    if (sc[1] != sc[2] || UR[1] != UR[2]) ckv = c1.size() < c2.size() ? c1 : c2;      // (not the model's case: take the tighter list)
-  }
-  if (cq.empty() || ckv.empty()) return false;
-  double best = 1e300;
-  PfTensorPlan bq = cq[0], bkv = ckv[0];
-  for (const auto& pq : cq)
-    for (const auto& pkv : ckv) {
-      const PfTensorPlan pl[3] = {pq, pkv, pkv};
-      double items = 0, sum = 0, longest = 0;
-      bool fits = true;
-      for (int i = 0; i < 3 && fits; ++i) {
-        if (lds_of(i, pl[i].n, pl[i].r) > LDS_MAX) { fits = false; break; }
-        const int tc = (T + pl[i].n - 1) / pl[i].n, yc = (UR[i] + pl[i].r - 1) / pl[i].r;
-        const int nl = T - (tc - 1) * pl[i].n, rl = UR[i] - (yc - 1) * pl[i].r;
-        items += 3.0 * BH * tc * yc;
-        sum += 3.0 * BH * ((tc - 1) * (yc - 1) * item_us(i, pl[i].n, pl[i].r, false) + (tc - 1) * item_us(i, pl[i].n, rl, false) +
-                           (yc - 1) * item_us(i, nl, pl[i].r, false) + item_us(i, nl, rl, false) + 1.5);
-        longest = std::max(longest, item_us(i, pl[i].n, pl[i].r, tc * yc == 1));
-      }
-      if (!fits || (long)BH * std::max((T + pq.n - 1) / pq.n * ((UR[0] + pq.r - 1) / pq.r),
-                                      (T + pkv.n - 1) / pkv.n * ((UR[1] + pkv.r - 1) / pkv.r)) > 4096) continue;
-      const double est = items <= SLOTS ? std::max(longest, sum / SLOTS) : sum / SLOTS + 0.5 * longest;
-      if (est < best) { best = est; bq = pq; bkv = pkv; }
-    }
-  if (best >= 1e300) return false;
-  const PfTensorPlan pl[3] = {bq, bkv, bkv};
-  size_t lds = 4 * 16 * 54 * sizeof(float);
-  double len[3];
-  g->max_chunks = 1;
-  for (int i = 0; i < 3; ++i) {
-    g->n_per[i] = pl[i].n;
-    g->r_per[i] = pl[i].r;
-    g->t_chunks[i] = (T + pl[i].n - 1) / pl[i].n;
-    g->y_chunks[i] = (UR[i] + pl[i].r - 1) / pl[i].r;
-    g->max_chunks = std::max(g->max_chunks, g->t_chunks[i] * g->y_chunks[i]);
-    lds = std::max(lds, lds_of(i, pl[i].n, pl[i].r));
-    len[i] = item_us(i, pl[i].n, pl[i].r, false);
-  }
-  // launch order: longest items first (the dispatcher fills the second slot of every CU with the shorter ones)
-  int ord[3] = {0, 1, 2};
-  std::sort(ord, ord + 3, [&](int x, int y) { return len[x] > len[y] || (len[x] == len[y] && x < y); });
-  int first = 0;
-  for (int j = 0; j < 3; ++j) {
-    g->order[j] = ord[j];
-    g->first_item[j] = first;
-    first += 3 * BH * g->t_chunks[ord[j]] * g->y_chunks[ord[j]];
-  }
-  g->first_item[3] = first;
-  *lds_out = lds;
-  return true;
-}
-
-// The search above costs ~1 ms of host time: its result is a pure function of the geometry, so it is memoised (a training
-// step has at most 16 distinct geometries; the table is append-only, mutex-guarded, and holds no device state).
-struct PfPlanEntry { PfPlanKey key; bool ok; PoolBwdFused plan; size_t lds; };
-static std::mutex g_pf_plan_mu;
-static std::vector<PfPlanEntry> g_pf_plans;
-static bool plan_bwd_fused_cached(const svit_pool_dgrad_args* d3, PoolBwdFused* g, size_t* lds_out) {
-  const PfPlanKey key = {{d3[0].B * d3[0].heads, d3[0].T, d3[0].H, d3[0].W, d3[0].stride_hw, d3[1].stride_hw, d3[2].stride_hw, 0}};
-  {
-    std::lock_guard<std::mutex> lk(g_pf_plan_mu);
-    for (const auto& e : g_pf_plans)
-      if (e.key == key) { *g = e.plan; *lds_out = e.lds; return e.ok; }
-  }
-  PfPlanEntry e;
-  e.key = key;
-  e.lds = 0;
-  e.ok = plan_bwd_fused(d3, &e.plan, &e.lds);
-  {
-    std::lock_guard<std::mutex> lk(g_pf_plan_mu);
-    if (g_pf_plans.size() < 256) g_pf_plans.push_back(e);
-  }
-  *g = e.plan; *lds_out = e.lds;
-  return e.ok;
-}
-
 // floats of workspace svit_pool_conv_bwd_qkv needs for these three tensors (one partial row of the three dw per (batch, head, chunk) of
 // its plan); -1 where the fused kernel has no plan.  Callers with a fixed scratch region ask first and bring a larger buffer when the
 // batch outgrows it (the entry point refuses a workspace that is too small: the product library has no other conv backward).
@@ -2731,10 +2765,9 @@ extern "C" int64_t svit_pool_conv_bwd_workspace(const svit_pool_dgrad_args* d3) 
   if (!d3) return SVIT_ERR_ARG;
   for (int i = 0; i < 3; ++i)
     if (check_pool_dims(d3[i].B, d3[i].heads, d3[i].T, d3[i].H, d3[i].W, d3[i].n_obj, d3[i].stride_hw)) return SVIT_ERR_SHAPE;
-  PoolBwdFused g;
-  size_t lds = 0;
-  if (!plan_bwd_fused_cached(d3, &g, &lds)) return -1;
-  return (int64_t)d3[0].B * d3[0].heads * g.max_chunks * 3 * 27 * HD;
+  PoolChunkPlan cp;
+  if (!pool_chunk_plan(pool_geom(d3), POOL_PLAN_BWD, &cp)) return -1;
+  return (int64_t)d3[0].B * d3[0].heads * cp.max_chunks * 3 * 27 * HD;
 }
 
 // which path the last svit_pool_conv_bwd_qkv call of this process took: 1 the fused plane-walk kernel, 0 the two streaming launches
@@ -2757,10 +2790,9 @@ extern "C" int svit_pool_conv_bwd_qkv(const svit_pool_dgrad_args* d3, const svit
         d.n_obj != d3[0].n_obj)
       return SVIT_ERR_SHAPE;
   }
-  PoolBwdFused g;
-  size_t lds = 0;
-  bool fused = svit_knob(SVIT_K_POOL_BWD) != 0 && plan_bwd_fused_cached(d3, &g, &lds);
-  const int64_t prows = fused ? (int64_t)d3[0].B * d3[0].heads * g.max_chunks : 0;
+  PoolChunkPlan cp;
+  bool fused = svit_knob(SVIT_K_POOL_BWD) != 0 && pool_chunk_plan(pool_geom(d3), POOL_PLAN_BWD, &cp);
+  const int64_t prows = fused ? (int64_t)d3[0].B * d3[0].heads * cp.max_chunks : 0;
   if (fused && (!w3[0].workspace || w3[0].workspace_floats < prows * 3 * 27 * HD || prows > 65536)) fused = false;
   __atomic_store_n(&g_pool_bwd_last_path, fused ? 1 : 0, __ATOMIC_RELAXED);
   if (!fused) {
@@ -2774,12 +2806,15 @@ extern "C" int svit_pool_conv_bwd_qkv(const svit_pool_dgrad_args* d3, const svit
     return SVIT_ERR_SHAPE;
 #endif
   }
+  PoolBwdFused g;
+  chunk_plan_into(cp, &g);
+  g.max_chunks = cp.max_chunks;
   for (int i = 0; i < 3; ++i) g.d[i] = d3[i];
   g.qkv = w3[0].qkv;
   g.partial = w3[0].workspace;
   static SvitOnce once;
   if (int rc = svit_max_lds_once(once, (const void*)pool_bwd_fused_kernel, 80 * 1024)) return rc;
-  hipLaunchKernelGGL(pool_bwd_fused_kernel, dim3((unsigned)g.first_item[3]), dim3(PF_NT), lds, (hipStream_t)stream, g);
+  hipLaunchKernelGGL(pool_bwd_fused_kernel, dim3((unsigned)g.first_item[3]), dim3(PF_NT), cp.lds, (hipStream_t)stream, g);
   SVIT_LAUNCH_CHECK();
   SvitReduceDst dst = {{w3[0].dw, w3[1].dw, w3[2].dw, w3[2].dw, w3[2].dw, w3[2].dw},
                        {27 * HD, 2 * 27 * HD, 3 * 27 * HD, 3 * 27 * HD, 3 * 27 * HD, 3 * 27 * HD}};
@@ -2789,16 +2824,10 @@ extern "C" int svit_pool_conv_bwd_qkv(const svit_pool_dgrad_args* d3, const svit
 }
 
 extern "C" int svit_pool_ln_bwd(const svit_pool_ln_bwd_args* a, void* stream) {
-  if (!a || !a->pre || !a->mean || !a->rstd || !a->gamma || !a->dpre || !a->dgamma || !a->dbeta)
-    return SVIT_ERR_ARG;
-  if (a->B <= 0 || a->heads <= 0 || a->Nout <= 0) return SVIT_ERR_SHAPE;
-  if (a->d_main && (a->ld_main < HD || a->ld_main % 8 != 0)) return SVIT_ERR_ALIGN;
+  if (!a) return SVIT_ERR_ARG;
+  if (int rc = check_pool_ln_bwd(a)) return rc;
   if (!a->workspace) return SVIT_ERR_ARG;
-  const int64_t total = (int64_t)a->B * a->heads * a->Nout;
-  int64_t blocks = (total + 255) / 256;            // >= 4 token groups per block
-  if (blocks < 128) blocks = (total + 63) / 64 < 128 ? (total + 63) / 64 : 128;
-  if (blocks > 1024) blocks = 1024;
-  if (blocks > a->workspace_floats / (2 * HD)) blocks = a->workspace_floats / (2 * HD);
+  const int64_t blocks = pool_ln_bwd_blocks((int64_t)a->B * a->heads * a->Nout, a->workspace_floats, 2 * HD);
   if (blocks < 1) return SVIT_ERR_ARG;
   hipLaunchKernelGGL(pool_ln_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, *a);
   SVIT_LAUNCH_CHECK();
@@ -2820,45 +2849,36 @@ static int check_relq(int ld, int kh, int kw, int kt) {
   if (kh + kw + kt > extra) return SVIT_ERR_SHAPE;
   return SVIT_OK;
 }
+// tokens of a rel-pos launch, and the grid of its per-token kernels: 256 / extra tokens per workgroup
+template <class A> static int64_t relq_tokens(const A* a) { return (int64_t)a->B * a->heads * (1 + a->qt * a->qh * a->qw + a->n_obj); }
+template <class A> static dim3 relq_grid(const A* a) {
+  const int tpb = 256 / (a->ld - HD);
+  return dim3((unsigned)((relq_tokens(a) + tpb - 1) / tpb));
+}
 
 extern "C" int svit_relpos_q_fwd(const svit_relq_args* a, void* stream) {
   if (!a || !a->qa || !a->rel_h || !a->rel_w || !a->rel_t || !a->idx_h || !a->idx_w || !a->idx_t)
     return SVIT_ERR_ARG;
-  int rc = check_relq(a->ld, a->kh, a->kw, a->kt);
-  if (rc) return rc;
-  const int extra = a->ld - HD;
-  const int64_t total = (int64_t)a->B * a->heads * (1 + a->qt * a->qh * a->qw + a->n_obj);
-  const int tpb = 256 / extra;
-  hipLaunchKernelGGL(relq_fwd_kernel, dim3((unsigned)((total + tpb - 1) / tpb)), dim3(256), 0,
-                     (hipStream_t)stream, *a);
+  if (int rc = check_relq(a->ld, a->kh, a->kw, a->kt)) return rc;
+  hipLaunchKernelGGL(relq_fwd_kernel, relq_grid(a), dim3(256), 0, (hipStream_t)stream, *a);
   SVIT_LAUNCH_CHECK();
   return SVIT_OK;
 }
 
 extern "C" int svit_relpos_gather(const svit_relq_gather_args* a, void* stream) {
   if (!a || !a->P || !a->qa || !a->idx_h || !a->idx_w || !a->idx_t) return SVIT_ERR_ARG;
-  int rc = check_relq(a->ld, a->kh, a->kw, a->kt);
-  if (rc) return rc;
-  const int extra = a->ld - HD;
-  const int64_t total = (int64_t)a->B * a->heads * (1 + a->qt * a->qh * a->qw + a->n_obj);
-  const int tpb = 256 / extra;
-  hipLaunchKernelGGL(relq_gather_kernel, dim3((unsigned)((total + tpb - 1) / tpb)), dim3(256), 0,
-                     (hipStream_t)stream, *a);
+  if (int rc = check_relq(a->ld, a->kh, a->kw, a->kt)) return rc;
+  hipLaunchKernelGGL(relq_gather_kernel, relq_grid(a), dim3(256), 0, (hipStream_t)stream, *a);
   SVIT_LAUNCH_CHECK();
   return SVIT_OK;
 }
 
 extern "C" int svit_relpos_scatter(const svit_relq_scatter_args* a, void* stream) {
   if (!a || !a->dqa || !a->D || !a->idx_h || !a->idx_w || !a->idx_t) return SVIT_ERR_ARG;
-  int rc = check_relq(a->ld, a->kh, a->kw, a->kt);
-  if (rc) return rc;
+  if (int rc = check_relq(a->ld, a->kh, a->kw, a->kt)) return rc;
   if (a->ldd % 8 != 0 || a->off_h < 0 || a->off_w < a->off_h || a->off_t < a->off_w) return SVIT_ERR_ARG;
-  const int extra = a->ld - HD;
-  const int64_t total = (int64_t)a->B * a->heads * (1 + a->qt * a->qh * a->qw + a->n_obj);
   if ((uintptr_t)a->D & 15) return SVIT_ERR_ALIGN;
-  const int tpb = 256 / extra;
-  hipLaunchKernelGGL(relq_scatter_kernel, dim3((unsigned)((total + tpb - 1) / tpb)), dim3(256), 0,
-                     (hipStream_t)stream, *a);
+  hipLaunchKernelGGL(relq_scatter_kernel, relq_grid(a), dim3(256), 0, (hipStream_t)stream, *a);
   SVIT_LAUNCH_CHECK();
   return SVIT_OK;
 }
@@ -2866,13 +2886,12 @@ extern "C" int svit_relpos_scatter(const svit_relq_scatter_args* a, void* stream
 extern "C" int svit_relpos_q_bwd(const svit_relq_bwd_args* a, void* stream) {
   if (!a || !a->qa || !a->dqa || !a->dq_extra || !a->drel_h || !a->drel_w || !a->drel_t)
     return SVIT_ERR_ARG;
-  int rc = check_relq(a->ld, a->kh, a->kw, a->kt);
-  if (rc) return rc;
+  if (int rc = check_relq(a->ld, a->kh, a->kw, a->kt)) return rc;
   const size_t lds = (size_t)(a->rows_h + a->rows_w + a->rows_t) * HD * sizeof(float);
   if (lds > 150 * 1024) return SVIT_ERR_SHAPE;
   static SvitOnce once;      // sized for the largest table set the shape check admits
   if (int rc = svit_max_lds_once(once, (const void*)relq_bwd_kernel, 150 * 1024)) return rc;
-  const int64_t total = (int64_t)a->B * a->heads * (1 + a->qt * a->qh * a->qw + a->n_obj);
+  const int64_t total = relq_tokens(a);
   if (!a->workspace) return SVIT_ERR_ARG;
   const int tab_n = (a->rows_h + a->rows_w + a->rows_t) * HD;
   int64_t blocks = (total + 7) / 8;

@@ -205,6 +205,7 @@ _SIGS = {
     "svit_attn_debug_set": (i32, [i32, i32]),
     "svit_debug_reset": (i32, []),
     "svit_debug_pool_bwd_path": (i32, []),
+    "svit_debug_pool_plan": (i32, [i32] * 13 + [C.POINTER(C.c_int32), i32]),
 }
 EXPORTS = tuple(sorted(_SIGS))
 

@@ -567,15 +567,11 @@ def _pool_dgrad_args(a, dpre, conv_w, dqkv, which, B, heads, thw, n_obj, stride_
     a.B, a.heads, (a.T, a.H, a.W), a.n_obj, a.stride_hw = B, heads, thw, n_obj, stride_hw
 
 
-
-
 def _pool_wgrad_args(a, dpre, qkv, which, dw, B, heads, thw, n_obj, stride_hw, ws=None):
     a.dpre, a.qkv, a.which, a.dw = ptr(dpre), ptr(qkv), which, ptr(dw)
     a.B, a.heads, (a.T, a.H, a.W), a.n_obj, a.stride_hw = B, heads, thw, n_obj, stride_hw
     ws = scratch(dpre.device) if ws is None else ws
     a.workspace, a.workspace_floats = ptr(ws), ws.numel()
-
-
 
 
 def pool_conv_bwd_workspace(B, heads, thw, n_obj, strides):
@@ -584,6 +580,26 @@ def pool_conv_bwd_workspace(B, heads, thw, n_obj, strides):
     for i in range(3):
         da[i].B, da[i].heads, (da[i].T, da[i].H, da[i].W), da[i].n_obj, da[i].stride_hw, da[i].which = B, heads, thw, n_obj, strides[i], i
     return int(hip.load().svit_pool_conv_bwd_workspace(da))
+
+
+POOL_PATHS = ("frame", "mfma", "slab", "staged", "stream")      # path codes of pool_plan(0, ...)
+POOL_KERNELS = ("pool_frame_fwd", "pool_mfma_fwd", "pool_slab_fwd", "pool_slab_ln", "pool_fwd_staged", "pool_ln_fwd3")
+POOL_RELQ = ("nobody", "pool_slab_ln", "gemm")
+
+
+def pool_plan(kind, B, heads, thw, n_obj, strides, save=True, sels=False, relq_lpad=0):
+    """What the host would decide for this geometry (svit_debug_pool_plan: launches nothing, needs no device).  kind 0: the
+    forward of pool_ln_fwd_qkv -> (path, who writes q's rel-pos columns, [(kernel, grid x, y, z, block, LDS bytes)]);
+    kind 1 / 2: the chunk plan of the staged forward / the fused backward -> {field: ints}, None where there is no plan."""
+    out = (C.c_int32 * 24)()
+    n = hip.load().svit_debug_pool_plan(kind, B, heads, *thw, n_obj, *strides, 7 if save else 0, int(sels), relq_lpad, out, 24)
+    hip.check(min(n, 0), "svit_debug_pool_plan")
+    if kind == 0:
+        return POOL_PATHS[out[0]], POOL_RELQ[out[1]], [(POOL_KERNELS[out[i]],) + tuple(out[i + 1:i + 6]) for i in range(3, n, 6)]
+    names = ("n_per", "r_per", "t_chunks", "y_chunks", "order")
+    plan = {k: tuple(out[1 + 3 * i:4 + 3 * i]) for i, k in enumerate(names)}
+    plan.update(first_item=tuple(out[16:20]), lds=out[20], max_chunks=out[21])
+    return plan if out[0] else None
 
 
 def pool_conv_bwd_qkv(dpres, conv_ws, dqkv, qkv, dws, B, heads, thw, n_obj, strides, ws=None):

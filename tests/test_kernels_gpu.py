@@ -862,7 +862,7 @@ def test_pool_slab_forward_vs_conv3d(ops, B, h, thw, sq, skv, n_obj):
     """Round-3 slab stencil (csrc/pool.hip::pool_slab_fwd_kernel + pool_slab_ln_kernel; the path the
     engine takes on planes <= 14x14): pre-LN values against torch's depthwise conv3d on the same bf16
     operands, object / cls rows against the closed form, and out / mean / rstd against the streaming
-    kernels of the same library (svit_debug_set_pool switches the path)."""
+    kernels of the same library (svit_debug_set_pool switches the path; the plan query says which one each arm took)."""
     import ctypes as C
     from svit_amd import hip
     lib = hip.load()
@@ -880,16 +880,20 @@ def test_pool_slab_forward_vs_conv3d(ops, B, h, thw, sq, skv, n_obj):
     sels = [sel[i] for i in range(3)]
     J = 2 * ops.pooled(H, skv) + T
     da = 128 if J <= 32 else 160
-    res = []
+    res, paths = [], []
     try:
+        if T == 1:                 # (by default a one-plane volume takes the frame kernel in every arm)
+            assert lib.svit_debug_set_pool(3, 0) == 0
         for on in (0, 1, 3):       # streaming kernels / VALU slab conv / MFMA conv wherever its geometry holds (else the slab)
             lib.svit_debug_set_pool(0, on)
+            paths.append(ops.pool_plan(0, B, h, thw, n_obj, (sq, skv, skv), sels=True)[0])
             r = ops.pool_ln_fwd_qkv(qkv, ws, g, b, B, h, thw, n_obj, (sq, skv, skv), (da, da, 96), (0, 1, 0),
                                     sels=sels, out_scales=(1.0, KSC, 1.0))
             torch.cuda.synchronize()
             res.append(r)
     finally:
         lib.svit_debug_reset()
+    assert paths == ["stream", "slab", "mfma" if T % 4 == 0 else "slab"]      # (the MFMA conv walks t-quads)
     for which, s in ((0, sq), (1, skv), (2, skv)):
         x = qkv[:, 1:1 + L, which].float()
         vol = x.reshape(B, T, H, W, h, 96).permute(0, 4, 5, 1, 2, 3).reshape(B * h, 96, T, H, W)
@@ -928,7 +932,8 @@ def test_pool_slab_forward_vs_conv3d(ops, B, h, thw, sq, skv, n_obj):
 def test_pool_forward_staged_large_planes(ops, B, h, thw, sq, skv, n_obj):
     """Round 5: the staged conv forward of the planes past 14x14 (csrc/pool.hip::pool_fwd_staged_kernel + the row-wise
     LayerNorm launch) against torch's depthwise conv3d on the same bf16 operands, the closed form of the object / cls rows,
-    and the streaming kernel of the same library (svit_debug_set_pool(2, 0)) incl. the rel-pos columns of q."""
+    and the streaming kernel of the same library (svit_debug_set_pool(2, 0)) incl. the rel-pos columns of q.  The plan query
+    says which path each arm took."""
     import ctypes as C
     from svit_amd import hip
     lib = hip.load()
@@ -943,16 +948,20 @@ def test_pool_forward_staged_large_planes(ops, B, h, thw, sq, skv, n_obj):
     da = 128 if J <= 32 else 160
     if J > 64:
         pytest.skip("key grid too large for the in-MFMA rel-pos columns")
-    res = []
+    res, paths = [], []
     try:
+        if T == 1:                 # (by default a one-plane volume takes the frame kernel in both arms)
+            assert lib.svit_debug_set_pool(3, 0) == 0
         for on in (0, 1):
             assert lib.svit_debug_set_pool(2, on) == 0
+            paths.append(ops.pool_plan(0, B, h, thw, n_obj, (sq, skv, skv))[0])
             r = ops.pool_ln_fwd_qkv(qkv, ws, g, b, B, h, thw, n_obj, (sq, skv, skv), (da, da, 96), (0, 1, 0),
                                     out_scales=(1.0, KSC, 1.0))
             torch.cuda.synchronize()
             res.append(r)
     finally:
         lib.svit_debug_reset()
+    assert paths == ["stream", "staged"]
     for which, s in ((0, sq), (1, skv), (2, skv)):
         x = qkv[:, 1:1 + L, which].float()
         vol = x.reshape(B, T, H, W, h, 96).permute(0, 4, 5, 1, 2, 3).reshape(B * h, 96, T, H, W)
@@ -1031,16 +1040,19 @@ def test_pool_forward_one_plane_volumes(ops, B, h, hw, sq, skv, n_obj, save):
     if J > 64:
         pytest.skip("key grid too large for the in-MFMA rel-pos columns")
     da = 128 if J <= 32 else 160
-    res = []
+    res, paths = [], []
     try:
         for on in (0, 2):        # 2: also where the trio is saved (the default takes the kernel in no-grad passes only)
             assert lib.svit_debug_set_pool(3, on) == 0
+            paths.append(ops.pool_plan(0, B, h, thw, n_obj, (sq, skv, skv), save=save)[0])
             r = ops.pool_ln_fwd_qkv(qkv, ws, g, b, B, h, thw, n_obj, (sq, skv, skv), (da, da, 96), (0, 1, 0),
                                     out_scales=(1.0, KSC, 1.0), save=save)
             torch.cuda.synchronize()
             res.append(r)
     finally:
         lib.svit_debug_reset()
+    # without the frame kernel: the staged conv where the trio is saved and the plane is past 14x14, else the streaming kernel
+    assert paths == ["staged" if save and H * W > 196 else "stream", "frame"]
     for which, s in ((0, sq), (1, skv), (2, skv)):
         x = qkv[:, 1:1 + L, which].float()
         vol = x.reshape(B, 1, H, W, h, 96).permute(0, 4, 5, 1, 2, 3).reshape(B * h, 96, 1, H, W)
