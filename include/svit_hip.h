@@ -652,6 +652,21 @@ int svit_ensemble_update(const float* preds, const int64_t* labels, const int64_
  * nk <= 8; counts int32 [nk] pre-zeroed. */
 int svit_topk_correct(const float* video_preds, const int64_t* video_labels, int V, int C,
                       const int* ks, int nk, int* counts, int* err, void* stream);
+/* One iteration of the train / val meters (slowfast/utils/meters.py:454-709; the .item() of every loss in every
+ * iteration of tools/train_net.py:153-167 and of the two top-k errors of :325-335) recorded on the device: row
+ * state[0] % W of ring (f32 [W,K]) takes the iteration, then state[0] += 1.  state: int64 [2] in device memory, read and
+ * written only by the launch itself (a replayed HIP graph walks the rows by itself) = {pushes, labels out of range}.
+ * Columns of a row: n_scalars <= SVIT_METER_MAX_SCALARS fp32 scalars fetched through the DEVICE addresses listed in the
+ * HOST array `scalars` (read during the call; the 0-d loss tensors; their bits are copied, NaN payloads included), then,
+ * if logits (f32 [N,C]) is not NULL, two more: the numbers of rows whose label (int64 [N]) ranks among the first k0 /
+ * k1 classes, as fp32 (exact below 2^24).  Ranking is svit_topk_correct's: a class is ahead of the label if its score
+ * is larger, or equal with a lower index.  A label outside [0,C) reads nothing, counts as wrong and increments state[1].
+ * One workgroup, no float arithmetic.  Before any launch: SVIT_ERR_ARG for a NULL ring / state / listed address (or
+ * logits without labels), SVIT_ERR_SHAPE for W <= 0, K != n_scalars + (logits ? 2 : 0), n_scalars > 16 and, with logits,
+ * N <= 0, C <= 0 or a k outside [1,C]. */
+#define SVIT_METER_MAX_SCALARS 16
+int svit_meter_push(float* ring, int W, int K, int64_t* state, const float* const* scalars, int n_scalars,
+                    const float* logits, const int64_t* labels, int N, int C, int k0, int k1, void* stream);
 /* ------------------------------------------------ diagnostics (tools/ only) ------------------ */
 /* Process-wide tuning knobs for the measurement scripts under tools/ and for the variant-parity tests (A/B runs of
  * kernel variants inside one process).  NOT part of the drop-in surface: the product path (svit_amd/engine.py,

@@ -38,7 +38,8 @@ from . import hip, ops
 
 
 class GraphedTrainStep:
-    def __init__(self, model, loss_fun, inputs, labels, warmup=2, frames_pass=False, mixup=None, optimizer=None):
+    def __init__(self, model, loss_fun, inputs, labels, warmup=2, frames_pass=False, mixup=None, optimizer=None,
+                 meter=None):
         """model: SViT or its DataParallel wrapper (train mode); loss_fun(preds, extra, labels) ->
         scalar; inputs: the reference's `inputs` list ([video f32 [B,3,T,S,S]]); labels: any
         tensor (or tuple/dict of tensors) `loss_fun` takes -- copied into static buffers.  The static input may be an
@@ -62,8 +63,19 @@ class GraphedTrainStep:
         AdamW, behind the last weight-gradient join; with data parallelism a last segment of its own, replayed after
         the final bucket's all-reduce has been waited for) and `__call__` uploads its host record before the first
         segment: the caller no longer calls `optimizer.step()`.  The warm-up runs of the body leave the tail out, so
-        building the step moves no weight.  None: the same segments as ever."""
+        building the step moves no weight.  None: the same segments as ever.
+        meter: a meters.TrainMeter on the step's device -- `loss_fun` may then return a dict (its "loss" entry is
+        differentiated, as tools/train_net.py:124-125 adds it; the other entries are only logged; a scalar return logs
+        {"loss": ...}) and the captured body holds the meter's push (one launch behind the loss: the row counter lives
+        in device memory, every replay fills the next row of the ring).  `__call__` does the host half of
+        `meter.update_stats` (lr -- the optimizer's, or the `lr` argument -- and mb_size = batch x ranks), so the loop
+        only calls `meter.log_iter_stats`.  The warm-up runs only fix the meter's columns and the capture run executes
+        nothing: the meter is empty after construction.  None: the same segments and launches as ever."""
         self.optimizer = optimizer
+        self.meter = meter
+        if meter is not None and torch.device(meter.device) != inputs[0].device:
+            raise hip.SvitHipError("GraphedTrainStep(meter=...): the meter lives on %s, the step on %s"
+                                   % (meter.device, inputs[0].device))
         if optimizer is not None:
             from .optim import GuardedClipAdamW
             if not isinstance(optimizer, GuardedClipAdamW):
@@ -120,6 +132,21 @@ class GraphedTrainStep:
         self._capture(warmup)
 
     # ------------------------------------------------------------------------------------------
+    def _loss(self, preds, extra, labels, tail):
+        """loss_fun -> the scalar to differentiate; with a meter, the push of what it returned (warm-up runs: the column
+        names only)"""
+        out = self.loss_fun(preds, extra, labels)
+        if isinstance(out, dict):
+            if "loss" not in out:
+                raise hip.SvitHipError("loss_fun returned a dict without a \"loss\" entry: %s" % sorted(out))
+            loss, logged = out["loss"], out
+        else:
+            loss, logged = out, {"loss": out}
+        if self.meter is not None:
+            (self.meter.push if tail else self.meter.bind)(logged)
+        self.loss_dict = {k: v.detach() for k, v in logged.items() if torch.is_tensor(v)}
+        return loss
+
     def _body(self, boundary, tail=False):
         core = self.core
         eng, flat = core.engine, core.flat
@@ -160,7 +187,7 @@ class GraphedTrainStep:
                 if frames_out is not None:
                     extra = dict(extra)
                     extra["frames_output"] = frames_out
-                loss = self.loss_fun(preds, extra, labels)
+                loss = self._loss(preds, extra, labels, tail)
             dy, = torch.autograd.grad(loss, [yt])
             feat = yt
         else:
@@ -175,7 +202,7 @@ class GraphedTrainStep:
                 if frames_out is not None:
                     extra = dict(extra)
                     extra["frames_output"] = frames_out
-                loss = self.loss_fun(preds, extra, labels)
+                loss = self._loss(preds, extra, labels, tail)
             grads = torch.autograd.grad(loss, [feat] + [alias[n] for n, _ in named], allow_unused=True)
             with torch.no_grad():
                 for (n, p), g in zip(named, grads[1:]):
@@ -256,9 +283,9 @@ class GraphedTrainStep:
         self._side = torch.cuda.Stream(device=dev)
 
     # ------------------------------------------------------------------------------------------
-    def __call__(self, inputs, labels, mix=None):
+    def __call__(self, inputs, labels, mix=None, lr=None):
         """mix: this step's mixup.MixRecord (mixup steps only; drawn from np.random when None, as the reference's
-        MixUp call would)."""
+        MixUp call would).  lr: what the meter logs for this step when the step holds no optimizer."""
         x = inputs[0]
         if x.shape != self.x.shape:
             raise hip.SvitHipError("GraphedTrainStep was captured for input %s, got %s"
@@ -283,6 +310,10 @@ class GraphedTrainStep:
             raise hip.SvitHipError("a mix record was passed to a GraphedTrainStep built without mixup")
         if self.optimizer is not None:
             self.optimizer.upload()
+        if self.meter is not None:
+            if lr is None and self.optimizer is not None:
+                lr = self.optimizer.param_groups[0]["lr"]
+            self.meter.host_update(lr, self.x.shape[0] * getattr(self.wrapper, "world_size", 1))
         main = torch.cuda.current_stream(self.x.device)
         for kind, val in self.segments:
             if kind == "graph":

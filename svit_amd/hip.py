@@ -197,6 +197,7 @@ _SIGS = {
     "svit_step_draws": (i32, [vp, vp, i32, i32, vp, i32, C.c_float, vp, vp]),
     "svit_ensemble_update": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
     "svit_topk_correct": (i32, [vp, vp, i32, i32, vp, i32, vp, vp, vp]),
+    "svit_meter_push": (i32, [vp, i32, i32, vp, vp, i32, vp, vp, i32, i32, i32, i32, vp]),
     # diagnostics block of the header: knobs for tools/ (never called by the product path)
     "svit_debug_set": (i32, [i32, i32]),
     "svit_debug_set_tn": (i32, [i32, i32]),

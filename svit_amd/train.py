@@ -1,0 +1,115 @@
+"""The loops around the step: `train_epoch` and `eval_epoch` of the reference (tools/train_net.py:33-178, 181-368) for
+single-label classification, without a host read per iteration.
+
+What the reference does per iteration and this does per cfg.LOG_PERIOD: `.item()` on every entry of the loss dict
+(train_net.py:153-167) and on the two top-k errors (train_net.py:325-335).  The numbers go through meters.TrainMeter /
+meters.ValMeter, which keep them in device memory between periods; with a graph.GraphedTrainStep(meter=train_meter) the
+push is part of the replayed step.
+
+Not here: detection, Epic-Kitchens dict labels, multi-label mAP, `update_predictions` / TensorBoard, multigrid.
+"""
+import torch
+import torch.distributed as dist
+
+from . import losses, optim
+from .graph import GraphedTrainStep
+
+
+def _min_length(n):
+    """du.all_gather_unaligned(len(loader)) -> min (train_net.py:73-74): ranks with loaders of different lengths stop
+    together"""
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        got = [None] * dist.get_world_size()
+        dist.all_gather_object(got, n)
+        return min(got)
+    return n
+
+
+def _lr_value(lr):
+    return lr["lr"] if isinstance(lr, dict) else lr
+
+
+def train_epoch(train_loader, step_or_model, optimizer, train_meter, cur_epoch, cfg):
+    """tools/train_net.py:33-178.  step_or_model: a GraphedTrainStep built with `optimizer=` and `meter=train_meter`
+    (the whole iteration is one replay; nothing here touches the device but the input copy) or the model itself (the
+    eager step: forward, video_image_loss, backward, optimizer.step(), one meter push).  The loader yields
+    (inputs, labels, video_idx, meta) like the reference's."""
+    graphed = isinstance(step_or_model, GraphedTrainStep)
+    if graphed:
+        if step_or_model.meter is not train_meter or step_or_model.optimizer is not optimizer:
+            raise ValueError("train_epoch: the GraphedTrainStep must be built with optimizer= and meter= the ones passed "
+                             "here (its replay ends with the optimizer's launches and holds the meter's push)")
+        dev = step_or_model.x.device
+    else:
+        model = step_or_model
+        model.train()
+        dev = train_meter.device
+        loss_fun = losses.get_loss_func(cfg)(reduction="mean")
+        wloss = losses.get_lambdas_dict(cfg)
+    train_meter.iter_tic()
+    data_size = len(train_loader)
+    min_length = _min_length(data_size)
+    world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
+    for cur_iter, (inputs, labels, _vid_idx, meta) in enumerate(train_loader):
+        if cur_iter >= min_length:
+            break
+        inputs = [x.to(dev, non_blocking=True) for x in inputs]
+        labels = labels.to(dev, non_blocking=True)
+        lr = _lr_value(optim.get_lr_at_epoch(cfg, cur_epoch + float(cur_iter) / data_size))
+        optim.set_lr(optimizer, lr)
+        train_meter.data_toc()
+        if graphed:
+            step_or_model(inputs, labels)            # (host half of update_stats included)
+        else:
+            meta = {k: v.to(dev, non_blocking=True) if torch.is_tensor(v) else v for k, v in (meta or {}).items()}
+            preds, extra_preds = model(inputs, meta)
+            loss_dict = loss_fun(preds, extra_preds, labels, meta)
+            loss_dict["loss"] = sum(wloss[k] * loss_dict[k] for k in loss_dict)
+            optimizer.zero_grad()
+            loss_dict["loss"].backward()
+            optimizer.step()
+            train_meter.update_stats(lr, inputs[0].size(0) * world, dloss=loss_dict)
+        train_meter.iter_toc()
+        train_meter.log_iter_stats(cur_epoch, cur_iter)
+        train_meter.iter_tic()
+    stats = train_meter.log_epoch_stats(cur_epoch)
+    train_meter.reset()
+    return stats
+
+
+def eval_extra_metrics(cfg, preds, extra_preds, labels, metadata):
+    """slowfast/utils/meters.py:869-883: the validation losses as device tensors"""
+    loss_fun = losses.get_loss_func(cfg, state="val")(reduction="mean")
+    loss_fun.eval()
+    loss_dict = loss_fun(preds, extra_preds, labels, metadata)
+    wloss = losses.get_lambdas_dict(cfg)
+    loss_dict["loss"] = sum(wloss[k] * loss_dict[k] for k in loss_dict if k in wloss)
+    return loss_dict
+
+
+@torch.no_grad()
+def eval_epoch(val_loader, model, val_meter, cur_epoch, cfg):
+    """tools/train_net.py:181-368, classification branch: per iteration one forward and one meter push (top-k hits and
+    the extra losses), no host read between periods."""
+    model.eval()
+    val_meter.iter_tic()
+    dev = val_meter.device
+    world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
+    for cur_iter, (inputs, labels, _, meta) in enumerate(val_loader):
+        inputs = [x.to(dev, non_blocking=True) for x in inputs]
+        labels = labels.to(dev, non_blocking=True)
+        meta = {k: v.to(dev, non_blocking=True) if torch.is_tensor(v) else v for k, v in (meta or {}).items()}
+        val_meter.data_toc()
+        preds = model(inputs, meta)
+        preds, extra_preds = preds if isinstance(preds, tuple) else (preds, None)
+        if cfg.TRAIN.FORWARD_VIDEO_FRAMES and inputs[0].size(2) > 1:         # train_net.py:243-248
+            _preds, _extra_preds = model([inputs[0].transpose(1, 2).flatten(0, 1).unsqueeze(2)], {})
+            extra_preds["frames_output"] = {"preds": _preds, "extra_preds": _extra_preds}
+        extra_metrics = eval_extra_metrics(cfg, preds, extra_preds, labels, meta)
+        val_meter.iter_toc()
+        val_meter.update_stats(preds, labels, inputs[0].size(0) * world, extra_metrices=extra_metrics)
+        val_meter.log_iter_stats(cur_epoch, cur_iter)
+        val_meter.iter_tic()
+    stats = val_meter.log_epoch_stats(cur_epoch)
+    val_meter.reset()
+    return stats
