@@ -234,6 +234,24 @@ int svit_im2col_patch_u8_aug_frames(const uint8_t* frames, int64_t frames_bytes,
                                     const void* mix, void* cols, int B, int T, int Hs, int Ws, int S, void* stream);
 int svit_u8_clips_render(const uint8_t* frames, int64_t frames_bytes, const float* lut_f32, const void* aug,
                          float* out_f32, int B, int T, int Hs, int Ws, int S, void* stream);
+/* PER-VIDEO EXTENTS: clips of different source sizes in one batch.  The batch is still one padded buffer u8
+ * [V,T,Hs,Ws,3]; `extents` int32 [V,2] = (h_v, w_v) in DEVICE memory (4-byte aligned) holds each video's true size: video
+ * v occupies rows [0, h_v) and columns [0, w_v) of each of its frames, the row pitch stays Ws and the rest of the frame is
+ * padding nobody interprets.  The table is read at run time, like the records, so one captured step serves batches of any
+ * mix of sizes up to (Hs, Ws).  Every kernel clamps an extent into [1,Hs] x [1,Ws] before use, so no table addresses
+ * outside the buffer.  NULL: every video fills the buffer -- the `_ext` entry points then run exactly what the plain ones
+ * run (the plain ones forward NULL).
+ * The three kernels above clamp a record's rectangle into ITS VIDEO'S extent instead of the buffer (h into [1, h_v], i
+ * into [0, h_v - h], likewise the width); the mix partner's record is clamped with the partner video's extent.  Nothing
+ * else changes. */
+int svit_im2col_patch_u8_aug_ext(const uint8_t* frames, int64_t frames_bytes, const float* lut_f32, const void* aug,
+                                 const int32_t* extents, const void* mix, void* cols, int B, int T, int Hs, int Ws, int S,
+                                 void* stream);
+int svit_im2col_patch_u8_aug_frames_ext(const uint8_t* frames, int64_t frames_bytes, const float* lut_f32, const void* aug,
+                                        const int32_t* extents, const void* mix, void* cols, int B, int T, int Hs, int Ws,
+                                        int S, void* stream);
+int svit_u8_clips_render_ext(const uint8_t* frames, int64_t frames_bytes, const float* lut_f32, const void* aug,
+                             const int32_t* extents, float* out_f32, int B, int T, int Hs, int Ws, int S, void* stream);
 /* RandAugment on the uint8 frames (cfg.AUG.AA_TYPE / INTERPOLATION; svit_amd/randaug.py, csrc/randaug.hip): the reference's
  * `create_random_augment` (slowfast/datasets/ssv2.py:345-375, rand_augment.py) -- N PIL operations per clip on every frame
  * at source resolution, before normalisation -- with PIL's bytes.  frames u8 [V,T,Hs,Ws,3]; `records` is the table
@@ -264,6 +282,16 @@ int svit_randaug_stats(const uint8_t* frames, const void* records, int layer, vo
                        int Ws, int N, void* stream);
 int svit_randaug_apply(const uint8_t* src, uint8_t* dst, const void* records, int layer, const void* workspace, int V,
                        int T, int Hs, int Ws, int N, void* stream);
+/* The same with per-video extents (the table defined at svit_im2col_patch_u8_aug_ext; NULL = the plain entry points).
+ * Inside its extent a video is treated as the tight h_v x w_v image: histograms and the Contrast mean run over h_v*w_v
+ * pixels, the AFFINE in-range test and every tap clamp use (w_v, h_v) -- the matrix is the caller's, built for the video's
+ * own size -- and the SHARPNESS border ring is row 0, row h_v-1, column 0 and column w_v-1.  Bytes of dst outside the
+ * extent are copies of src, so every byte of dst is still written; the grid stays over Hs*Ws and addressing uses the
+ * pitch Ws (w_v*3 need not be a multiple of anything). */
+int svit_randaug_stats_ext(const uint8_t* frames, const void* records, const int32_t* extents, int layer, void* workspace,
+                           int V, int T, int Hs, int Ws, int N, void* stream);
+int svit_randaug_apply_ext(const uint8_t* src, uint8_t* dst, const void* records, const int32_t* extents, int layer,
+                           const void* workspace, int V, int T, int Hs, int Ws, int N, void* stream);
 /* cls / object token rows of the block-0 input (video_model_builder.py:326-363). */
 int svit_fill_special_tokens(float* x, const float* cls, const float* objq, const float* pos_t,
                              int B, int N, int L, int Tx, int O, int C, int add_pos, void* stream);

@@ -35,7 +35,22 @@ and nothing is drawn; a rescaled side SHORTER than the crop (a crop of the wrong
 RandAugment (cfg.AUG.AA_TYPE, the stage BEFORE this pipeline) runs on the device as well: `AugClips(..., randaug=table)`
 with the table of svit_amd/randaug.py keeps the raw frames and runs the chain raw -> `frames` ahead of every read.
 
-Out of scope: colour jitter (AUG.COLOR_JITTER, which the reference's loader never reads), DATA.TRAIN_JITTER_MOTION_SHIFT,
+Videos of different sizes in one batch (Something-Something v2 is distributed at a fixed height and a width that varies
+from video to video; the reference augments each clip alone at its own size and batches only after the crop): the buffer
+is padded to a common `[V,T,Hs,Ws,3]` and a table `extents` int32 [V,2] = (h_v, w_v) in device memory says where each
+video lies -- rows [0, h_v), columns [0, w_v) of each of its frames, row pitch Ws.  Draw every clip for its OWN size:
+
+    frames, extents = pack_videos(videos)                       # host u8 [T,h_v,w_v,3] each -> padded buffer + table
+    table = pack_table([ra.draw(T, h, w, video=v) for v, (h, w) in enumerate(extents.tolist())])
+    records = [sampler.draw(h, w, video=v) for v, (h, w) in enumerate(extents.tolist())]
+    clips = AugClips(frames.cuda(), size, records, mean, std, randaug=table, extents=extents)
+
+Every clip then gets the bytes it would get if its video had been augmented alone: RandAugment treats the extent as the
+whole image and the records are validated (host) and clamped (device) against their own video, never the padding.  The
+kernels read the table at run time, so one captured step serves any mix of sizes up to the captured (Hs, Ws).
+`extents=None` is every video filling the buffer: the launches and bytes of before.
+
+Out of scope: tightly packed storage with per-video offsets, per-frame sizes inside one video, colour jitter (AUG.COLOR_JITTER, which the reference's loader never reads), DATA.TRAIN_JITTER_MOTION_SHIFT,
 boxes, the image ranks, AUG.RE_COUNT > 1 and bicubic resampling.  The reference's frames pass reads the same frames and
 records: `input.FramesView(clips)` is the B*T frames as single-frame clips (`svit_im2col_patch_u8_aug_frames`; frame
 (b, t) through clip b's record, erase noise and mix partner included) and `GraphedTrainStep(..., frames_pass="u8")` runs
@@ -92,15 +107,33 @@ def unpack_records(table):
     return [AugRecord.unpack(row) for row in table.detach().cpu().numpy()]
 
 
-def validate_records(table, V, Hs, Ws, S):
+def pack_extents(extents, V, Hs, Ws, min_side=1):
+    """list of (h, w) or an int [V,2] array / tensor -> int32 [V,2] tensor on the host; ValueError for an extent above
+    the Hs x Ws buffer or below min_side (3 under RandAugment)"""
+    from .randaug import pack_extents as pack
+    return torch.from_numpy(pack(extents, V, Hs, Ws, min_side))
+
+
+def clamp_extents(extents, Hs, Ws):
+    """What the kernels make of ANY int32 [V,2] table: every extent clamped into [1,Hs] x [1,Ws] (int64 NumPy [V,2])"""
+    e = np.array(torch.as_tensor(extents).detach().cpu().numpy(), dtype=np.int64).reshape(-1, 2)
+    return np.stack([np.clip(e[:, 0], 1, Hs), np.clip(e[:, 1], 1, Ws)], axis=1)
+
+
+def validate_records(table, V, Hs, Ws, S, extents=None):
     """ValueError unless every row describes a rectangle inside the frame, a window inside the resampled image and a
-    box inside the window (the device additionally clamps: `clamp_records`)."""
+    box inside the window (the device additionally clamps: `clamp_records`).  extents (int [V,2], validated): the
+    rectangle must lie inside the record's own video, not merely the buffer."""
     t = table.to(torch.int64)
     f = {n: t[:, k] for k, n in enumerate(FIELDS.split())}
+    where, hv, wv = "%dx%d frame" % (Hs, Ws), Hs, Ws
+    if extents is not None:
+        e = torch.as_tensor(extents).to(t.device, torch.int64)[f["video"].clamp(0, V - 1)]
+        where, hv, wv = "extent of its video", e[:, 0], e[:, 1]
     checks = (
         ("video outside [0, %d)" % V, (f["video"] >= 0) & (f["video"] < V)),
-        ("source rectangle outside the %dx%d frame" % (Hs, Ws),
-         (f["h"] >= 1) & (f["w"] >= 1) & (f["i"] >= 0) & (f["j"] >= 0) & (f["i"] + f["h"] <= Hs) & (f["j"] + f["w"] <= Ws)),
+        ("source rectangle outside the %s" % where,
+         (f["h"] >= 1) & (f["w"] >= 1) & (f["i"] >= 0) & (f["j"] >= 0) & (f["i"] + f["h"] <= hv) & (f["j"] + f["w"] <= wv)),
         ("resampled size outside [1, 2^24]",
          (f["out_h"] >= 1) & (f["out_w"] >= 1) & (f["out_h"] <= MAX_OUT) & (f["out_w"] <= MAX_OUT)),
         ("%dx%d window outside the resampled image" % (S, S),
@@ -114,12 +147,16 @@ def validate_records(table, V, Hs, Ws, S):
             raise ValueError("augmentation record %d: %s" % (int((~ok).nonzero()[0, 0]), what))
 
 
-def clamp_records(table, V, Hs, Ws, S):
+def clamp_records(table, V, Hs, Ws, S, extents=None):
     """What the kernels make of ANY int32 [B,16] table (aug_geom of csrc/input.hip) -- a valid table is unchanged except
-    that flip becomes 0 / 1."""
+    that flip becomes 0 / 1.  extents: ANY int [V,2] table; the rectangle is clamped into the (clamped) extent of the
+    record's (clamped) video."""
     t = np.array(torch.as_tensor(table).detach().cpu().numpy(), dtype=np.int64).reshape(-1, 16)
     f = {n: t[:, k].copy() for k, n in enumerate(FIELDS.split())}
     f["video"] = np.clip(f["video"], 0, V - 1)
+    if extents is not None:
+        e = clamp_extents(extents, Hs, Ws)[f["video"]]
+        Hs, Ws = e[:, 0], e[:, 1]
     f["h"], f["w"] = np.clip(f["h"], 1, Hs), np.clip(f["w"], 1, Ws)
     f["i"], f["j"] = np.clip(f["i"], 0, Hs - f["h"]), np.clip(f["j"], 0, Ws - f["w"])
     f["out_h"], f["out_w"] = np.clip(f["out_h"], 1, MAX_OUT), np.clip(f["out_w"], 1, MAX_OUT)
@@ -132,6 +169,37 @@ def clamp_records(table, V, Hs, Ws, S):
     return torch.from_numpy(np.stack([f[n] for n in FIELDS.split()], axis=1).astype(np.int32))
 
 
+def pack_videos(videos, Hs=None, Ws=None, out=None, pin_memory=False):
+    """Videos of different sizes -> one padded batch.  videos: a list of V host u8 [T,h_v,w_v,3] tensors (one T).
+    -> (frames u8 [V,T,Hs,Ws,3] on the host, zero outside each video; extents int32 [V,2] = (h_v, w_v)).  Hs / Ws default
+    to the batch maxima; give the captured step's so that every batch has its buffer shape (a larger video raises).
+    out: a buffer of that shape to reuse (e.g. a pinned one from an earlier call); pin_memory: allocate a pinned one."""
+    if len(videos) == 0:
+        raise ValueError("pack_videos needs at least one video")
+    for v, x in enumerate(videos):
+        if not torch.is_tensor(x) or x.dtype != torch.uint8 or x.dim() != 4 or x.shape[-1] != 3 or x.is_cuda:
+            raise ValueError("video %d: expected a host uint8 [T,h,w,3] tensor" % v)
+        if x.shape[0] != videos[0].shape[0]:
+            raise ValueError("video %d has %d frames, video 0 has %d" % (v, x.shape[0], videos[0].shape[0]))
+        if x.shape[1] < 1 or x.shape[2] < 1:
+            raise ValueError("video %d is empty: %s" % (v, tuple(x.shape)))
+    Hs = max(x.shape[1] for x in videos) if Hs is None else int(Hs)
+    Ws = max(x.shape[2] for x in videos) if Ws is None else int(Ws)
+    for v, x in enumerate(videos):
+        if x.shape[1] > Hs or x.shape[2] > Ws:
+            raise ValueError("video %d is %dx%d, larger than the %dx%d buffer" % (v, x.shape[1], x.shape[2], Hs, Ws))
+    shape = (len(videos), videos[0].shape[0], Hs, Ws, 3)
+    if out is None:
+        out = torch.zeros(shape, dtype=torch.uint8, pin_memory=bool(pin_memory))
+    else:
+        if out.dtype != torch.uint8 or tuple(out.shape) != shape or out.is_cuda or not out.is_contiguous():
+            raise ValueError("out must be a contiguous host uint8 %s tensor, got %s %s" % (shape, out.dtype, tuple(out.shape)))
+        out.zero_()
+    for v, x in enumerate(videos):
+        out[v, :, :x.shape[1], :x.shape[2]] = x
+    return out, torch.tensor([[x.shape[1], x.shape[2]] for x in videos], dtype=torch.int32)
+
+
 class AugClips(U8Input):
     """B augmented clips over V uint8 videos: `frames` u8 [V,T,Hs,Ws,3] on the GPU, `size` = S, `records` a list of
     AugRecord (or an int32 [B,16] table).  Quacks like `input.U8Clips` where the model and GraphedTrainStep look at it;
@@ -139,19 +207,26 @@ class AugClips(U8Input):
     randaug: the int32 [V,N,16] table of svit_amd/randaug.py (`pack_table`) -- the object then keeps the frames it was
     given as `raw` (never written), the table in device memory and one scratch buffer, and `frames` becomes the chain's
     output: ops.im2col_patch_u8_aug / ops.u8_clips_render launch the 2N kernels raw -> frames first, eager and inside a
-    captured step alike.  None: the same launches and bytes as ever."""
+    captured step alike.  None: the same launches and bytes as ever.
+    extents: a list of (h, w) or an int [V,2] table -- `frames` is a padded buffer and video v its top-left h_v x w_v
+    corner (module docstring; `pack_videos`).  The table lives in device memory next to the records and every kernel of
+    the route reads it (`svit_*_ext`); records are checked against their own video.  None: every video fills the
+    buffer, the same launches and bytes as ever."""
 
     _rows = "records"
 
     def __init__(self, frames, size, records, mean=(0.45, 0.45, 0.45), std=(0.225, 0.225, 0.225), lut_f32=None,
-                 randaug=None):
+                 randaug=None, extents=None):
         V, T, Hs, Ws = self._take_frames(frames)
         self.size = int(size)
         if self.size < 1:
             raise ValueError("size must be positive")
+        self._min_side = 1 if randaug is None else 3           # (RandAugment: the Hs, Ws >= 3 rule, per video)
+        ext = None if extents is None else pack_extents(extents, V, Hs, Ws, self._min_side)
         table = pack_records(records)
-        validate_records(table, V, Hs, Ws, self.size)          # one tiny reduction + sync; the kernels also clamp
+        validate_records(table, V, Hs, Ws, self.size, ext)     # one tiny reduction + sync; the kernels also clamp
         self.records = table.to(frames.device)
+        self.extents = None if ext is None else ext.to(frames.device)
         self.mean, self.std = tuple(mean), tuple(std)
         # the fp32 table is built here, outside any capture
         self.lut_f32 = normalize_lut_f32(mean, std, frames.device) if lut_f32 is None else lut_f32
@@ -176,21 +251,29 @@ class AugClips(U8Input):
         """raw -> frames through the table's N layers (2N launches on the current stream); nothing without a table"""
         if self.ra_table is not None:
             from . import randaug as ra
-            ra.apply(self.raw, self.ra_table, self.frames, self.ra_tmp, self.ra_ws)
+            ra.apply(self.raw, self.ra_table, self.frames, self.ra_tmp, self.ra_ws, extents=self.extents)
 
     def data_ptr(self):
         return (self.frames if self.raw is None else self.raw).data_ptr()
 
     def clone(self):
+        ext = None if self.extents is None else self.extents.clone()
         if self.raw is not None:
             return AugClips(self.raw.clone(), self.size, self.records.clone(), mean=self.mean, std=self.std,
-                            lut_f32=self.lut_f32, randaug=self.ra_table.clone())
+                            lut_f32=self.lut_f32, randaug=self.ra_table.clone(), extents=ext)
         return AugClips(self.frames.clone(), self.size, self.records.clone(), mean=self.mean, std=self.std,
-                        lut_f32=self.lut_f32)
+                        lut_f32=self.lut_f32, extents=ext)
 
     def copy_(self, other, non_blocking=False):
         if (self.raw is None) != (other.raw is None) or (self.raw is not None and self.ra_table.shape != other.ra_table.shape):
             raise ValueError("copy_ between AugClips with and without RandAugment, or with tables of different shapes")
+        if (self.extents is None) != (other.extents is None):
+            raise ValueError("copy_ between AugClips with and without extents")
+        if self.frames.shape != other.frames.shape:
+            raise ValueError("copy_ between AugClips over buffers of different shapes: %s and %s"
+                             % (tuple(self.frames.shape), tuple(other.frames.shape)))
+        if self.extents is not None:
+            self.extents.copy_(other.extents, non_blocking=non_blocking)
         if self.raw is not None:
             self.raw.copy_(other.raw, non_blocking=non_blocking)
             self.ra_table.copy_(other.ra_table, non_blocking=non_blocking)
@@ -209,6 +292,19 @@ class AugClips(U8Input):
         self.ra_table.copy_(t, non_blocking=True)
         return self
 
+    def set_extents(self, extents, validate=True):
+        """rewrite the extents table in place (same V) -- BEFORE set_records, which checks against the table it finds;
+        validate=False skips the host check (the kernels clamp into the buffer)"""
+        if self.extents is None:
+            raise ValueError("this AugClips was built without extents")
+        V, _, Hs, Ws, _ = self.frames.shape
+        if validate:
+            ext = pack_extents(extents, V, Hs, Ws, self._min_side)
+        else:
+            ext = torch.as_tensor(extents).to(torch.int32).reshape(V, 2).contiguous()
+        self.extents.copy_(ext, non_blocking=True)
+        return self
+
     def set_records(self, records, validate=True):
         """rewrite the record table in place (same B); validate=False skips the host check (the kernels clamp)"""
         table = pack_records(records)
@@ -216,7 +312,7 @@ class AugClips(U8Input):
             raise ValueError("the record table is int32 %s, got %s" % (tuple(self.records.shape), tuple(table.shape)))
         if validate:
             V, _, Hs, Ws, _ = self.frames.shape
-            validate_records(table, V, Hs, Ws, self.size)
+            validate_records(table, V, Hs, Ws, self.size, self.extents)
         self.records.copy_(table, non_blocking=True)
         return self
 

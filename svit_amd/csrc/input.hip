@@ -283,8 +283,10 @@ struct SvitAug {
   int video, i, j, h, w, out_h, out_w, oy, ox, flip, erase_mode, et, el, eh, ew, seed;
 };
 
-// a record clamped into the buffer (the host validates at construction, svit_amd/augment.py; a record rewritten on the
-// device can then still never address outside `frames_bytes`) + the two resampling scales
+// a record clamped into its video's extent (the host validates at construction, svit_amd/augment.py; a record rewritten
+// on the device can then still never address outside `frames_bytes`) + the two resampling scales.  `extents` int32
+// [V,2] = (h_v, w_v), itself clamped into [1,Hs] x [1,Ws]: video v is the top-left h_v x w_v of each of its frames, the
+// pitch stays Ws; null = every video fills the buffer.
 struct AugGeom {
   int64_t vbase;                        // byte offset of the source video
   int i, j, h, w, oy, ox, flip, mode;
@@ -296,15 +298,17 @@ constexpr int AUG_MAX_OUT = 1 << 24;    // resampled sizes stay exact in fp32
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return max(lo, min(v, hi)); }
 
-__device__ __forceinline__ AugGeom aug_geom(const SvitAug* __restrict__ aug, int b, int64_t n_videos, int T, int Hs, int Ws,
-                                            int S) {
+__device__ __forceinline__ AugGeom aug_geom(const SvitAug* __restrict__ aug, const int32_t* __restrict__ extents, int b,
+                                            int64_t n_videos, int T, int Hs, int Ws, int S) {
   const SvitAug r = aug[b];
   AugGeom g;
-  g.vbase = (int64_t)clampi(r.video, 0, (int)n_videos - 1) * T * Hs * Ws * 3;
-  g.h = clampi(r.h, 1, Hs);
-  g.w = clampi(r.w, 1, Ws);
-  g.i = clampi(r.i, 0, Hs - g.h);
-  g.j = clampi(r.j, 0, Ws - g.w);
+  const int v = clampi(r.video, 0, (int)n_videos - 1);
+  g.vbase = (int64_t)v * T * Hs * Ws * 3;
+  const int hv = extents ? clampi(extents[2 * v], 1, Hs) : Hs, wv = extents ? clampi(extents[2 * v + 1], 1, Ws) : Ws;
+  g.h = clampi(r.h, 1, hv);
+  g.w = clampi(r.w, 1, wv);
+  g.i = clampi(r.i, 0, hv - g.h);
+  g.j = clampi(r.j, 0, wv - g.w);
   const int out_h = clampi(r.out_h, 1, AUG_MAX_OUT), out_w = clampi(r.out_w, 1, AUG_MAX_OUT);
   g.oy = clampi(r.oy, 0, max(out_h - S, 0));
   g.ox = clampi(r.ox, 0, max(out_w - S, 0));
@@ -391,11 +395,12 @@ __device__ __forceinline__ void aug_pixel(const AugGeom& g, const float* tab, co
 
 __global__ __launch_bounds__(256) void u8_clips_render_kernel(
     const uint8_t* __restrict__ frames, int64_t frames_bytes, const float* __restrict__ lut,
-    const SvitAug* __restrict__ aug, float* __restrict__ out, int T, int Hs, int Ws, int S) {
+    const SvitAug* __restrict__ aug, const int32_t* __restrict__ extents, float* __restrict__ out, int T, int Hs, int Ws,
+    int S) {
   __shared__ float tab[768];
   const int b = blockIdx.y / T, t = blockIdx.y % T;
   const int64_t n_videos = frames_bytes / ((int64_t)T * Hs * Ws * 3);
-  const AugGeom g = aug_geom(aug, b, n_videos, T, Hs, Ws, S);
+  const AugGeom g = aug_geom(aug, extents, b, n_videos, T, Hs, Ws, S);
   const AugGlobalFetch fetch{frames, g.vbase, Hs, Ws, g.i, g.j};
   for (int i = threadIdx.x; i < 768; i += 256) tab[i] = lut[i];
   __syncthreads();
@@ -444,8 +449,8 @@ struct AugStageFetch {
 template <bool FRAMES>
 __global__ __launch_bounds__(256) void im2col_patch_u8_aug_kernel(
     const uint8_t* __restrict__ frames, int64_t frames_bytes, const float* __restrict__ lut,
-    const SvitAug* __restrict__ aug, const SvitMix* __restrict__ mix, bf16_t* __restrict__ cols,
-    int B, int T, int Hs, int Ws, int S, int To, int Ho, int Wo) {
+    const SvitAug* __restrict__ aug, const int32_t* __restrict__ extents, const SvitMix* __restrict__ mix,
+    bf16_t* __restrict__ cols, int B, int T, int Hs, int Ws, int S, int To, int Ho, int Wo) {
   constexpr int KT = FRAMES ? 1 : 3;             // frames a block reads
   constexpr int LINE0 = FRAMES ? 7 : 0;          // first (kt, ky) line the fill writes, KT * 7 of them
   constexpr int STAGE = FRAMES ? AUG_STAGE_FRAMES : AUG_STAGE;
@@ -460,8 +465,8 @@ __global__ __launch_bounds__(256) void im2col_patch_u8_aug_kernel(
   const int b = FRAMES ? n / T : n / To;
   const int pb = B - 1 - b;
   const int64_t n_videos = frames_bytes / ((int64_t)T * Hs * Ws * 3);
-  const AugGeom g = aug_geom(aug, b, n_videos, T, Hs, Ws, S);
-  const AugGeom g2 = aug_geom(aug, pb, n_videos, T, Hs, Ws, S);
+  const AugGeom g = aug_geom(aug, extents, b, n_videos, T, Hs, Ws, S);
+  const AugGeom g2 = aug_geom(aug, extents, pb, n_videos, T, Hs, Ws, S);
   const AugGlobalFetch gfetch{frames, g.vbase, Hs, Ws, g.i, g.j};
   const AugGlobalFetch gfetch2{frames, g2.vbase, Hs, Ws, g2.i, g2.j};
   for (int i = threadIdx.x; i < 768; i += 256) tab[i] = lut[i];
@@ -584,29 +589,58 @@ extern "C" int svit_mixup_clips(float* x, const void* mix, int B, int planes, in
   return SVIT_OK;
 }
 
-static int aug_args_ok(const void* frames, int64_t frames_bytes, const void* lut_f32, const void* aug, const void* out,
-                       int B, int T, int Hs, int Ws, int S) {
+static int aug_args_ok(const void* frames, int64_t frames_bytes, const void* lut_f32, const void* aug,
+                       const void* extents, const void* out, int B, int T, int Hs, int Ws, int S) {
   if (!frames || !lut_f32 || !aug || !out) return SVIT_ERR_ARG;
   if (B <= 0 || T <= 0 || Hs <= 0 || Ws <= 0 || S <= 0 || S > 16384 || Hs > 32768 || Ws > 32768) return SVIT_ERR_SHAPE;
   if (frames_bytes < (int64_t)T * Hs * Ws * 3) return SVIT_ERR_SHAPE;                 // at least one whole video
   if (frames_bytes / ((int64_t)T * Hs * Ws * 3) > 0x7fffffff) return SVIT_ERR_SHAPE;
-  if (((uintptr_t)frames | (uintptr_t)lut_f32 | (uintptr_t)aug | (uintptr_t)out) & 3) return SVIT_ERR_ALIGN;
+  if (((uintptr_t)frames | (uintptr_t)lut_f32 | (uintptr_t)aug | (uintptr_t)extents | (uintptr_t)out) & 3)
+    return SVIT_ERR_ALIGN;
   return SVIT_OK;
 }
 
 // both passes of the augmented im2col: FRAMES = the B*T frames as single-frame clips (To = 1)
 template <bool FRAMES>
 static int launch_im2col_aug(const uint8_t* frames, int64_t frames_bytes, const float* lut_f32, const void* aug,
-                             const void* mix, void* cols, int B, int T, int Hs, int Ws, int S, void* stream) {
-  const int rc = aug_args_ok(frames, frames_bytes, lut_f32, aug, cols, B, T, Hs, Ws, S);
+                             const int32_t* extents, const void* mix, void* cols, int B, int T, int Hs, int Ws, int S,
+                             void* stream) {
+  const int rc = aug_args_ok(frames, frames_bytes, lut_f32, aug, extents, cols, B, T, Hs, Ws, S);
   if (rc != SVIT_OK) return rc;
   if (((uintptr_t)mix & 3) || ((uintptr_t)cols & 15)) return SVIT_ERR_ALIGN;
   const PatchGrid g = patch_grid(FRAMES ? 1 : T, S);
   const int64_t blocks = (int64_t)B * (FRAMES ? T : g.To) * g.Ho;
   if (blocks > 0x7fffffff) return SVIT_ERR_SHAPE;
   hipLaunchKernelGGL(im2col_patch_u8_aug_kernel<FRAMES>, dim3((unsigned)blocks), dim3(256), 0,
-                     (hipStream_t)stream, frames, frames_bytes, lut_f32, (const SvitAug*)aug, (const SvitMix*)mix,
-                     (bf16_t*)cols, B, T, Hs, Ws, S, g.To, g.Ho, g.Wo);
+                     (hipStream_t)stream, frames, frames_bytes, lut_f32, (const SvitAug*)aug, extents,
+                     (const SvitMix*)mix, (bf16_t*)cols, B, T, Hs, Ws, S, g.To, g.Ho, g.Wo);
+  SVIT_LAUNCH_CHECK();
+  return SVIT_OK;
+}
+
+extern "C" int svit_im2col_patch_u8_aug_ext(const uint8_t* frames, int64_t frames_bytes, const float* lut_f32,
+                                            const void* aug, const int32_t* extents, const void* mix, void* cols, int B,
+                                            int T, int Hs, int Ws, int S, void* stream) {
+  return launch_im2col_aug<false>(frames, frames_bytes, lut_f32, aug, extents, mix, cols, B, T, Hs, Ws, S, stream);
+}
+
+extern "C" int svit_im2col_patch_u8_aug_frames_ext(const uint8_t* frames, int64_t frames_bytes, const float* lut_f32,
+                                                   const void* aug, const int32_t* extents, const void* mix, void* cols,
+                                                   int B, int T, int Hs, int Ws, int S, void* stream) {
+  return launch_im2col_aug<true>(frames, frames_bytes, lut_f32, aug, extents, mix, cols, B, T, Hs, Ws, S, stream);
+}
+
+extern "C" int svit_u8_clips_render_ext(const uint8_t* frames, int64_t frames_bytes, const float* lut_f32,
+                                        const void* aug, const int32_t* extents, float* out_f32, int B, int T, int Hs,
+                                        int Ws, int S, void* stream) {
+  const int rc = aug_args_ok(frames, frames_bytes, lut_f32, aug, extents, out_f32, B, T, Hs, Ws, S);
+  if (rc != SVIT_OK) return rc;
+  if ((int64_t)B * T > 65535) return SVIT_ERR_SHAPE;
+  int blocks = (S * S + 255) / 256;
+  if (blocks > 1024) blocks = 1024;
+  hipLaunchKernelGGL(u8_clips_render_kernel, dim3((unsigned)blocks, (unsigned)(B * T)), dim3(256), 0,
+                     (hipStream_t)stream, frames, frames_bytes, lut_f32, (const SvitAug*)aug, extents, out_f32, T, Hs,
+                     Ws, S);
   SVIT_LAUNCH_CHECK();
   return SVIT_OK;
 }
@@ -614,25 +648,18 @@ static int launch_im2col_aug(const uint8_t* frames, int64_t frames_bytes, const 
 extern "C" int svit_im2col_patch_u8_aug(const uint8_t* frames, int64_t frames_bytes, const float* lut_f32,
                                         const void* aug, const void* mix, void* cols, int B, int T, int Hs,
                                         int Ws, int S, void* stream) {
-  return launch_im2col_aug<false>(frames, frames_bytes, lut_f32, aug, mix, cols, B, T, Hs, Ws, S, stream);
+  return svit_im2col_patch_u8_aug_ext(frames, frames_bytes, lut_f32, aug, nullptr, mix, cols, B, T, Hs, Ws, S, stream);
 }
 
 extern "C" int svit_im2col_patch_u8_aug_frames(const uint8_t* frames, int64_t frames_bytes, const float* lut_f32,
                                                const void* aug, const void* mix, void* cols, int B, int T, int Hs,
                                                int Ws, int S, void* stream) {
-  return launch_im2col_aug<true>(frames, frames_bytes, lut_f32, aug, mix, cols, B, T, Hs, Ws, S, stream);
+  return svit_im2col_patch_u8_aug_frames_ext(frames, frames_bytes, lut_f32, aug, nullptr, mix, cols, B, T, Hs, Ws, S,
+                                             stream);
 }
 
 extern "C" int svit_u8_clips_render(const uint8_t* frames, int64_t frames_bytes, const float* lut_f32,
                                     const void* aug, float* out_f32, int B, int T, int Hs, int Ws, int S,
                                     void* stream) {
-  const int rc = aug_args_ok(frames, frames_bytes, lut_f32, aug, out_f32, B, T, Hs, Ws, S);
-  if (rc != SVIT_OK) return rc;
-  if ((int64_t)B * T > 65535) return SVIT_ERR_SHAPE;
-  int blocks = (S * S + 255) / 256;
-  if (blocks > 1024) blocks = 1024;
-  hipLaunchKernelGGL(u8_clips_render_kernel, dim3((unsigned)blocks, (unsigned)(B * T)), dim3(256), 0,
-                     (hipStream_t)stream, frames, frames_bytes, lut_f32, (const SvitAug*)aug, out_f32, T, Hs, Ws, S);
-  SVIT_LAUNCH_CHECK();
-  return SVIT_OK;
+  return svit_u8_clips_render_ext(frames, frames_bytes, lut_f32, aug, nullptr, out_f32, B, T, Hs, Ws, S, stream);
 }

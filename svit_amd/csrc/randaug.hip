@@ -7,6 +7,10 @@
 // launches for every draw.  Per layer: `svit_randaug_stats` (histogram -> AutoContrast / Equalize table, Contrast
 // mean; per FRAME, as PIL sees one image at a time) and `svit_randaug_apply` (src -> dst, every byte written).
 //
+// Per-video extents (the `_ext` entry points; include/svit_hip.h): the buffer is padded, video v is the tight
+// h_v x w_v image in the top-left corner of each of its frames, row pitch Ws.  Statistics, the affine in-range test,
+// the tap clamps and the Sharpness interior all see that image; the padding is copied.  The grid stays over Hs*Ws.
+//
 // The bar is PIL's bytes, so every operation keeps PIL's arithmetic and its ORDER: integer tables, the fp32 blend of
 // ImagingBlend and the fp32 3x3 smooth of ImagingFilter with product and sum rounded separately, the fp64
 // coordinates and bilinear / bicubic filters of ImagingGenericTransform.  This file is therefore compiled WITHOUT
@@ -30,9 +34,20 @@ __device__ __forceinline__ int ra_clampi(int v, int lo, int hi) { return v < lo 
 __device__ __forceinline__ int ra_clip8(float t) { return !(t > 0.0f) ? 0 : (t >= 255.0f ? 255 : (int)t); }
 __device__ __forceinline__ int ra_clip8(double t) { return !(t > 0.0) ? 0 : (t >= 255.0 ? 255 : (int)t); }
 
+// the extent of video v clamped into the buffer (a table rewritten on the device never addresses outside it); a null
+// table is the whole frame
+__device__ __forceinline__ void ra_extent(const int32_t* __restrict__ extents, int v, int Hs, int Ws, int& h, int& w) {
+  h = Hs, w = Ws;
+  if (extents) {
+    h = ra_clampi(extents[2 * v], 1, Hs);
+    w = ra_clampi(extents[2 * v + 1], 1, Ws);
+  }
+}
+
 // ---- per-frame statistics ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void randaug_stats_kernel(const uint8_t* __restrict__ frames,
-                                                            const SvitRandAugOp* __restrict__ recs, int layer,
+                                                            const SvitRandAugOp* __restrict__ recs,
+                                                            const int32_t* __restrict__ extents, int layer,
                                                             uint8_t* __restrict__ ws, int T, int Hs, int Ws, int N) {
   const int vt = blockIdx.x, tid = threadIdx.x;
   const int op = recs[(size_t)(vt / T) * N + layer].op;
@@ -42,20 +57,29 @@ __global__ __launch_bounds__(256) void randaug_stats_kernel(const uint8_t* __res
   __shared__ int lohi[6];
   for (int i = tid; i < 768; i += 256) hist[i] = 0;
   __syncthreads();
-  const int npix = Hs * Ws;
-  const uint8_t* f = frames + (size_t)vt * npix * 3;
-  if (op == RA_CONTRAST) {
-    for (int p = tid; p < npix; p += 256) {
-      const uint8_t* q = f + (size_t)p * 3;
-      atomicAdd(&hist[ra_luma(q[0], q[1], q[2])], 1u);
+  int h, w;
+  ra_extent(extents, vt / T, Hs, Ws, h, w);
+  const int npix = h * w;
+  const uint8_t* f = frames + (size_t)vt * Hs * Ws * 3;
+  // every pixel of the extent once; full-width rows are one contiguous run of pixels (the loop of the plain entry points)
+  const auto walk = [&](const auto& count) {
+    if (w == Ws) {
+      for (int p = tid; p < npix; p += 256) count(f + (size_t)p * 3);
+    } else {
+      for (int p = tid; p < npix; p += 256) {
+        const int y = p / w, x = p - y * w;
+        count(f + ((size_t)y * Ws + x) * 3);
+      }
     }
+  };
+  if (op == RA_CONTRAST) {
+    walk([&](const uint8_t* q) { atomicAdd(&hist[ra_luma(q[0], q[1], q[2])], 1u); });
   } else {
-    for (int p = tid; p < npix; p += 256) {
-      const uint8_t* q = f + (size_t)p * 3;
+    walk([&](const uint8_t* q) {
       atomicAdd(&hist[q[0]], 1u);
       atomicAdd(&hist[256 + q[1]], 1u);
       atomicAdd(&hist[512 + q[2]], 1u);
-    }
+    });
   }
   __syncthreads();
   uint8_t* slot = ws + (size_t)vt * RA_SLOT;
@@ -132,8 +156,9 @@ __device__ __forceinline__ double ra_cubic(double v1, double v2, double v3, doub
 }
 
 __global__ __launch_bounds__(256) void randaug_apply_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
-                                                            const SvitRandAugOp* __restrict__ recs, int layer,
-                                                            const uint8_t* __restrict__ ws, int T, int Hs, int Ws, int N,
+                                                            const SvitRandAugOp* __restrict__ recs,
+                                                            const int32_t* __restrict__ extents, int layer,
+                                                            const uint8_t* __restrict__ ws, int T, int Hb, int Wb, int N,
                                                             int blocks_per_frame) {
   const int vt = blockIdx.x / blocks_per_frame, blk = blockIdx.x % blocks_per_frame, tid = threadIdx.x;
   const int t = vt % T;
@@ -145,14 +170,20 @@ __global__ __launch_bounds__(256) void randaug_apply_kernel(const uint8_t* __res
     for (int i = tid; i < 768; i += 256) lut[i] = slot[i];
     __syncthreads();
   }
-  const int npix = Hs * Ws;
+  const int npix = Hb * Wb;                                  // the grid is over the padded buffer Hb x Wb, pitch Wb
   const int p = blk * 256 + tid;
   if (p >= npix) return;
-  const int y = p / Ws, x = p - y * Ws;
+  const int y = p / Wb, x = p - y * Wb;
   const uint8_t* f = src + (size_t)vt * npix * 3;
   const uint8_t* q = f + (size_t)p * 3;
   uint8_t* o = dst + (size_t)vt * npix * 3 + (size_t)p * 3;
   int c0 = q[0], c1 = q[1], c2 = q[2];
+  int Hs, Ws;                                                // the video's own image; outside it dst is a copy
+  ra_extent(extents, vt / T, Hb, Wb, Hs, Ws);
+  if (y >= Hs || x >= Ws) {                                  // (no barrier below; `op` stays uniform for the switch)
+    o[0] = (uint8_t)c0, o[1] = (uint8_t)c1, o[2] = (uint8_t)c2;
+    return;
+  }
   switch (op) {
     case RA_AUTOCONTRAST:
     case RA_EQUALIZE:
@@ -198,7 +229,7 @@ __global__ __launch_bounds__(256) void randaug_apply_kernel(const uint8_t* __res
           float ss[3] = {0.5f, 0.5f, 0.5f};
 #pragma unroll
           for (int r = 1; r >= -1; --r) {                    // rows y+1, y, y-1 as ImagingFilter3x3 adds them
-            const uint8_t* row = q + (ptrdiff_t)r * Ws * 3;
+            const uint8_t* row = q + (ptrdiff_t)r * Wb * 3;
             const float kc = r == 0 ? k5 : k1;
 #pragma unroll
             for (int c = 0; c < 3; ++c)
@@ -235,7 +266,7 @@ __global__ __launch_bounds__(256) void randaug_apply_kernel(const uint8_t* __res
           for (int r = 0; r < 4; ++r) {
             const int yy = iy - 1 + r;
             if (r == 0 || (yy >= 0 && yy < Hs)) {
-              const uint8_t* row = f + (size_t)ra_clampi(yy, 0, Hs - 1) * Ws * 3 + c;
+              const uint8_t* row = f + (size_t)ra_clampi(yy, 0, Hs - 1) * Wb * 3 + c;
               v[r] = ra_cubic((double)row[xa], (double)row[xb], (double)row[xc], (double)row[xd], dx);
             } else {
               v[r] = v[r - 1];
@@ -245,9 +276,9 @@ __global__ __launch_bounds__(256) void randaug_apply_kernel(const uint8_t* __res
         }
       } else {
         const int xa = ra_clampi(ix, 0, Ws - 1) * 3, xb = ra_clampi(ix + 1, 0, Ws - 1) * 3;
-        const uint8_t* row0 = f + (size_t)ra_clampi(iy, 0, Hs - 1) * Ws * 3;
+        const uint8_t* row0 = f + (size_t)ra_clampi(iy, 0, Hs - 1) * Wb * 3;
         const bool second = iy + 1 >= 0 && iy + 1 < Hs;
-        const uint8_t* row1 = f + (size_t)ra_clampi(iy + 1, 0, Hs - 1) * Ws * 3;
+        const uint8_t* row1 = f + (size_t)ra_clampi(iy + 1, 0, Hs - 1) * Wb * 3;
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
           const int a = row0[xa + c], b = row0[xb + c];
@@ -282,24 +313,37 @@ int ra_args_ok(const void* frames, const void* recs, int layer, const void* ws, 
 }
 }  // namespace
 
-extern "C" int svit_randaug_stats(const uint8_t* frames, const void* records, int layer, void* workspace, int V, int T,
-                                  int Hs, int Ws, int N, void* stream) {
+extern "C" int svit_randaug_stats_ext(const uint8_t* frames, const void* records, const int32_t* extents, int layer,
+                                      void* workspace, int V, int T, int Hs, int Ws, int N, void* stream) {
   const int rc = ra_args_ok(frames, records, layer, workspace, V, T, Hs, Ws, N);
   if (rc != SVIT_OK) return rc;
+  if ((uintptr_t)extents % 4) return SVIT_ERR_ALIGN;
   hipLaunchKernelGGL(randaug_stats_kernel, dim3((unsigned)(V * T)), dim3(256), 0, (hipStream_t)stream, frames,
-                     (const SvitRandAugOp*)records, layer, (uint8_t*)workspace, T, Hs, Ws, N);
+                     (const SvitRandAugOp*)records, extents, layer, (uint8_t*)workspace, T, Hs, Ws, N);
   SVIT_LAUNCH_CHECK();
   return SVIT_OK;
 }
 
-extern "C" int svit_randaug_apply(const uint8_t* src, uint8_t* dst, const void* records, int layer, const void* workspace,
-                                  int V, int T, int Hs, int Ws, int N, void* stream) {
+extern "C" int svit_randaug_apply_ext(const uint8_t* src, uint8_t* dst, const void* records, const int32_t* extents,
+                                      int layer, const void* workspace, int V, int T, int Hs, int Ws, int N,
+                                      void* stream) {
   const int rc = ra_args_ok(src, records, layer, workspace, V, T, Hs, Ws, N);
   if (rc != SVIT_OK) return rc;
   if (!dst || dst == src) return SVIT_ERR_ARG;
+  if ((uintptr_t)extents % 4) return SVIT_ERR_ALIGN;
   const int bpf = (Hs * Ws + 255) / 256;
   hipLaunchKernelGGL(randaug_apply_kernel, dim3((unsigned)(V * T * bpf)), dim3(256), 0, (hipStream_t)stream, src, dst,
-                     (const SvitRandAugOp*)records, layer, (const uint8_t*)workspace, T, Hs, Ws, N, bpf);
+                     (const SvitRandAugOp*)records, extents, layer, (const uint8_t*)workspace, T, Hs, Ws, N, bpf);
   SVIT_LAUNCH_CHECK();
   return SVIT_OK;
+}
+
+extern "C" int svit_randaug_stats(const uint8_t* frames, const void* records, int layer, void* workspace, int V, int T,
+                                  int Hs, int Ws, int N, void* stream) {
+  return svit_randaug_stats_ext(frames, records, nullptr, layer, workspace, V, T, Hs, Ws, N, stream);
+}
+
+extern "C" int svit_randaug_apply(const uint8_t* src, uint8_t* dst, const void* records, int layer, const void* workspace,
+                                  int V, int T, int Hs, int Ws, int N, void* stream) {
+  return svit_randaug_apply_ext(src, dst, records, nullptr, layer, workspace, V, T, Hs, Ws, N, stream);
 }

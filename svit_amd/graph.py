@@ -44,7 +44,10 @@ class GraphedTrainStep:
         scalar; inputs: the reference's `inputs` list ([video f32 [B,3,T,S,S]]); labels: any
         tensor (or tuple/dict of tensors) `loss_fun` takes -- copied into static buffers.  The static input may be an
         input.U8Clips or an augment.AugClips (uint8 frames + crop table / augmentation records, read by the im2col at
-        replay time: `__call__` copies frames and table into the static ones).
+        replay time: `__call__` copies frames and table into the static ones).  Built with `extents=`, the static input
+        is a padded buffer captured at its (Hs, Ws): `__call__` also copies the V x 8 bytes of the extents table and one
+        capture serves batches of any mix of video sizes up to that buffer; a batch over a buffer of another shape is
+        refused.
         frames_pass: also run the reference's no-grad single-frame forward of every clip
         (tools/train_net.py:105-110) inside the graph; its outputs reach `loss_fun` as
         extra["frames_output"] = {"preds", "extra_preds"} (the consistency-loss operand).  True: the fp32 route (the
@@ -290,6 +293,13 @@ class GraphedTrainStep:
         if x.shape != self.x.shape:
             raise hip.SvitHipError("GraphedTrainStep was captured for input %s, got %s"
                                    % (tuple(self.x.shape), tuple(x.shape)))
+        if not torch.is_tensor(x):
+            # uint8 route: the kernels were captured with the static buffer's (Hs, Ws) as launch arguments; videos of
+            # other sizes travel inside a buffer of that shape with their extents (augment.pack_videos(..., Hs, Ws))
+            if not hasattr(x, "frames") or x.frames.shape != self.x.frames.shape:
+                raise hip.SvitHipError("GraphedTrainStep was captured for a frame buffer %s, got %s: pad the batch to "
+                                       "the captured size and pass the videos' extents"
+                                       % (tuple(self.x.frames.shape), tuple(getattr(x, "frames", x).shape)))
         if x.data_ptr() != self.x.data_ptr():
             self.x.copy_(x, non_blocking=True)
         _tree_copy(self.labels, labels)

@@ -160,9 +160,15 @@ _SIGS = {
     "svit_im2col_patch_u8_aug": (i32, [vp, i64, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     "svit_im2col_patch_u8_aug_frames": (i32, [vp, i64, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     "svit_u8_clips_render": (i32, [vp, i64, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
+    # per-video extents: the same plus `extents` int32 [V,2] after the records
+    "svit_im2col_patch_u8_aug_ext": (i32, [vp, i64, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
+    "svit_im2col_patch_u8_aug_frames_ext": (i32, [vp, i64, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
+    "svit_u8_clips_render_ext": (i32, [vp, i64, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     "svit_mixup_clips": (i32, [vp, vp, i32, i32, i32, i32, vp]),
     "svit_randaug_stats": (i32, [vp, vp, i32, vp, i32, i32, i32, i32, i32, vp]),
     "svit_randaug_apply": (i32, [vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, vp]),
+    "svit_randaug_stats_ext": (i32, [vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, vp]),
+    "svit_randaug_apply_ext": (i32, [vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, vp]),
     "svit_fill_special_tokens": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
     "svit_special_token_grads": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
     "svit_pool_ln_fwd": (i32, [C.POINTER(PoolArgs), vp]),

@@ -66,7 +66,7 @@ class U8Clips(U8Input):
     _rows = "crops"
 
     def __init__(self, frames, size, crops=None, mean=(0.45, 0.45, 0.45), std=(0.225, 0.225, 0.225),
-                 lut=None, lut_f32=None):
+                 lut=None, lut_f32=None, extents=None):
         V, T, Hs, Ws = self._take_frames(frames)
         self.size = int(size)
         if self.size > Hs or self.size > Ws:
@@ -83,6 +83,16 @@ class U8Clips(U8Input):
               (c[:, 2] >= 0) & (c[:, 2] + self.size <= Ws))
         if not bool(ok.all()):
             raise ValueError("crop table outside the frames")
+        # extents (list of (h, w) or int [V,2]; augment.pack_videos): `frames` is a padded buffer and video v its
+        # top-left h_v x w_v corner.  Checked here, on the host, row by row; the kernel neither reads nor needs them.
+        self.extents = None
+        if extents is not None:
+            from .augment import pack_extents
+            self.extents = pack_extents(extents, V, Hs, Ws)
+            e = self.extents.to(c.device, torch.int64)[c[:, 0].to(torch.int64)]
+            ok = (c[:, 1] + self.size <= e[:, 0]) & (c[:, 2] + self.size <= e[:, 1])
+            if not bool(ok.all()):
+                raise ValueError("crop %d reaches outside the extent of its video" % int((~ok).nonzero()[0, 0]))
         self.crops = crops.to(frames.device).contiguous()
         self.lut = normalize_lut(mean, std, frames.device) if lut is None else lut
         self.mean, self.std = tuple(mean), tuple(std)
@@ -107,11 +117,15 @@ class U8Clips(U8Input):
 
     def clone(self):
         return U8Clips(self.frames.clone(), self.size, self.crops.clone(), mean=self.mean, std=self.std,
-                       lut=self.lut, lut_f32=self._lut_f32)
+                       lut=self.lut, lut_f32=self._lut_f32, extents=self.extents)
 
     def copy_(self, other, non_blocking=False):
+        if self.frames.shape != other.frames.shape:
+            raise ValueError("copy_ between U8Clips over buffers of different shapes: %s and %s"
+                             % (tuple(self.frames.shape), tuple(other.frames.shape)))
         self.frames.copy_(other.frames, non_blocking=non_blocking)
         self.crops.copy_(other.crops, non_blocking=non_blocking)
+        self.extents = other.extents            # (host side: what the crop table was checked against)
         return self
 
 
@@ -145,6 +159,8 @@ class FramesView(U8Input):
     lut_f32 = property(lambda self: self.clips.lut_f32)
     mix = property(lambda self: self.clips.mix)
     size = property(lambda self: self.clips.size)
+    # the device extents table of an AugClips (a U8Clips checks its crops on the host: its kernels take none)
+    extents = property(lambda self: self.clips.extents if hasattr(self.clips, "records") else None)
 
     def device_records(self):
         """the int32 [B,16] records the kernel reads: the AugClips' own table, or the identity records of the crop table"""

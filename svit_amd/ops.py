@@ -339,10 +339,22 @@ def im2col_patch(video):
     return cols, (To, Ho, Wo)
 
 
-def _im2col_u8(name, fr, lut, table, S, mix=(), frames_pass=False):
+def _chk_extents(extents, fr):
+    """the per-video extents of an AugClips -> the `_ext` suffix and the extra argument; None: the plain entry point"""
+    if extents is None:
+        return "", ()
+    if (extents.dtype != torch.int32 or tuple(extents.shape) != (fr.shape[0], 2) or not extents.is_contiguous()
+            or extents.device != fr.device):
+        raise hip.SvitHipError("the extents must be contiguous int32 [%d,2] on %s (got %s %s on %s)"
+                               % (fr.shape[0], fr.device, extents.dtype, tuple(extents.shape), extents.device))
+    return "_ext", (ptr(extents),)
+
+
+def _im2col_u8(name, fr, lut, table, S, mix=(), frames_pass=False, extents=None):
     """One launch of a uint8 im2col kernel: frames u8 [V,T,Hs,Ws,3], its normalisation table, the per-clip table (crop
     rows or augmentation records) and, for the kernels that take one, the mix record (`mix` = (record or None,)).
-    -> (cols bf16 [rows, 448], (To, Ho, Wo)); frames_pass: the B*T frames as single-frame clips."""
+    -> (cols bf16 [rows, 448], (To, Ho, Wo)); frames_pass: the B*T frames as single-frame clips; extents: the int32
+    [V,2] table of the `_ext` form of an augmentation kernel."""
     _chk_dev(fr)
     V, T, Hs, Ws, _ = fr.shape
     B = table.shape[0]
@@ -352,7 +364,9 @@ def _im2col_u8(name, fr, lut, table, S, mix=(), frames_pass=False):
     for m in mix:
         if m is not None:
             _chk_mix(m, fr.device)
-    hip.call(name, ptr(fr), fr.numel(), ptr(lut), ptr(table), *[ptr(m) for m in mix], ptr(cols), B, T, Hs, Ws, S)
+    suffix, ext = _chk_extents(extents, fr)
+    hip.call(name + suffix, ptr(fr), fr.numel(), ptr(lut), ptr(table), *ext, *[ptr(m) for m in mix], ptr(cols),
+             B, T, Hs, Ws, S)
     return cols, (To, Ho, Wo)
 
 
@@ -380,7 +394,7 @@ def im2col_patch_u8_aug(clips):
     _chk_aug(clips.frames, clips.records, clips.lut_f32)
     clips.run_randaug()         # (cfg.AUG.AA_TYPE: raw -> frames on this stream first; nothing without a table)
     return _im2col_u8("svit_im2col_patch_u8_aug", clips.frames, clips.lut_f32, clips.records, clips.size,
-                      (getattr(clips, "mix", None),))
+                      (getattr(clips, "mix", None),), extents=clips.extents)
 
 
 def im2col_patch_u8_aug_frames(view):
@@ -393,7 +407,8 @@ def im2col_patch_u8_aug_frames(view):
         clips.run_randaug()
     fr, rec, lut = view.frames, view.device_records(), view.lut_f32
     _chk_aug(fr, rec, lut)
-    return _im2col_u8("svit_im2col_patch_u8_aug_frames", fr, lut, rec, view.size, (view.mix,), frames_pass=True)
+    return _im2col_u8("svit_im2col_patch_u8_aug_frames", fr, lut, rec, view.size, (view.mix,), frames_pass=True,
+                      extents=view.extents)
 
 
 def u8_clips_render(clips):
@@ -404,8 +419,9 @@ def u8_clips_render(clips):
     V, T, Hs, Ws, _ = fr.shape
     B, S = clips.records.shape[0], clips.size
     out = torch.empty((B, 3, T, S, S), device=fr.device, dtype=F32)
-    hip.call("svit_u8_clips_render", ptr(fr), fr.numel(), ptr(clips.lut_f32), ptr(clips.records), ptr(out),
-             B, T, Hs, Ws, S)
+    suffix, ext = _chk_extents(clips.extents, fr)
+    hip.call("svit_u8_clips_render" + suffix, ptr(fr), fr.numel(), ptr(clips.lut_f32), ptr(clips.records), *ext,
+             ptr(out), B, T, Hs, Ws, S)
     return out
 
 

@@ -21,6 +21,13 @@ increasing set (`bool("0")`), and the `w0` weights are listed by the plain set's
 reference also sets `translate_const = int(min(Hs, Ws) * 0.45)`; only the absolute translations read it and neither set
 holds one.
 
+Videos of different sizes in one batch: the buffer is padded to a common [V,T,Hs,Ws,3] and `extents` int32 [V,2] =
+(h_v, w_v) says where each video lies (top-left corner, pitch Ws; `augment.pack_videos` builds both).  Draw each clip for
+its OWN size -- `ra.draw(T, h_v, w_v)` -- and pass the table to `apply(..., extents=)` / `apply_host(..., extents=)`:
+inside its extent every video gets the bytes it would get alone as a tight h_v x w_v clip (histograms, the Contrast mean,
+the affine fill boundary and tap clamps, the Sharpness border ring); the padding is copied.  None: every video fills the
+buffer, the launches and bytes of before.
+
 Out of scope: boxes, the image ranks, AUG.NUM_SAMPLE > 1, AUG.COLOR_JITTER (the reference's loader never reads it),
 policies other than `rand-...`, frames smaller than 3 x 3.
 """
@@ -405,22 +412,44 @@ def apply_frame(img, rec, t=0):
     return img.copy()
 
 
-def apply_host(frames, table):
-    """frames u8 [V,T,Hs,Ws,3] (NumPy) through the N layers of `table` (int32 [V,N,16] or lists of RandAugOp)"""
+def pack_extents(extents, V, Hs, Ws, min_side=1):
+    """list of (h, w) or an int [V,2] array -> int32 [V,2] NumPy array; ValueError unless min_side <= h_v <= Hs and
+    min_side <= w_v <= Ws for every video (RandAugment needs 3 x 3, as it does of the frames)"""
+    e = np.asarray(extents.detach().cpu().numpy() if hasattr(extents, "detach") else extents)
+    if e.dtype.kind not in "iu" or e.shape != (V, 2):
+        raise ValueError("extents are int [%d,2] = (h, w) per video, got %s %s" % (V, e.dtype, tuple(e.shape)))
+    e = np.ascontiguousarray(e.astype(np.int64))
+    for v in range(V):
+        h, w = int(e[v, 0]), int(e[v, 1])
+        if h > Hs or w > Ws:
+            raise ValueError("extent %d: %dx%d is larger than the %dx%d buffer" % (v, h, w, Hs, Ws))
+        if h < min_side or w < min_side:
+            raise ValueError("extent %d: %dx%d is smaller than %dx%d" % (v, h, w, min_side, min_side))
+    return e.astype(np.int32)
+
+
+def apply_host(frames, table, extents=None):
+    """frames u8 [V,T,Hs,Ws,3] (NumPy) through the N layers of `table` (int32 [V,N,16] or lists of RandAugOp).
+    extents (int [V,2] or None): video v is its tight [h_v, w_v] slice and goes through the chain as that image; the
+    padding around it comes out as it went in."""
     frames = np.asarray(frames)
     if frames.dtype != np.uint8 or frames.ndim != 5 or frames.shape[-1] != 3:
         raise ValueError("frames must be uint8 [V,T,H,W,3]")
     table = pack_table(table)
     if table.shape[0] != frames.shape[0]:
         raise ValueError("the table has %d rows for %d videos" % (table.shape[0], frames.shape[0]))
-    out = np.empty_like(frames)
+    Hs, Ws = frames.shape[2:4]
+    if extents is not None:
+        extents = pack_extents(extents, frames.shape[0], Hs, Ws, min_side=3)
+    out = frames.copy()
     for v in range(frames.shape[0]):
         recs = [RandAugOp.unpack(w) for w in table[v]]
+        h, w = (Hs, Ws) if extents is None else (int(extents[v, 0]), int(extents[v, 1]))
         for t in range(frames.shape[1]):
-            img = frames[v, t]
+            img = frames[v, t, :h, :w]
             for rec in recs:
                 img = apply_frame(img, rec, t)
-            out[v, t] = img
+            out[v, t, :h, :w] = img
     return out
 
 
@@ -429,10 +458,12 @@ def workspace_bytes(V, T):
     return V * T * SLOT_BYTES
 
 
-def apply(src, table, dst, tmp, workspace):
+def apply(src, table, dst, tmp, workspace, extents=None):
     """Launch the 2N kernels: src u8 [V,T,Hs,Ws,3] through the N layers of `table` (int32 [V,N,16] on the device) into
     dst.  The layers ping-pong between tmp and dst so that the LAST one lands in dst; src is never written.  tmp (same
-    shape; None is fine for N == 1) and workspace (uint8, workspace_bytes(V, T)) are scratch."""
+    shape; None is fine for N == 1) and workspace (uint8, workspace_bytes(V, T)) are scratch.
+    extents: int32 [V,2] = (h_v, w_v) on the device (`svit_randaug_*_ext`; the kernels read it at run time and clamp it
+    into the buffer, range checks are the caller's: `pack_extents`); None: the plain entry points."""
     import torch
     from . import hip
     V, T, Hs, Ws, _ = src.shape
@@ -453,10 +484,18 @@ def apply(src, table, dst, tmp, workspace):
         raise hip.SvitHipError("RandAugment src, dst and tmp must be distinct buffers")
     if workspace.dtype != torch.uint8 or workspace.numel() < workspace_bytes(V, T):
         raise hip.SvitHipError("RandAugment workspace must be uint8 with %d bytes" % workspace_bytes(V, T))
+    ext, suffix = (), ""
+    if extents is not None:
+        if (extents.dtype != torch.int32 or tuple(extents.shape) != (V, 2) or not extents.is_contiguous()
+                or extents.device != src.device):
+            raise hip.SvitHipError("the extents must be contiguous int32 [%d,2] on %s, got %s %s on %s"
+                                   % (V, src.device, extents.dtype, tuple(extents.shape), extents.device))
+        ext, suffix = (hip.ptr(extents),), "_ext"
     cur = src
     for k in range(N):
         out = dst if (N - 1 - k) % 2 == 0 else tmp
-        hip.call("svit_randaug_stats", hip.ptr(cur), hip.ptr(table), k, hip.ptr(workspace), V, T, Hs, Ws, N)
-        hip.call("svit_randaug_apply", hip.ptr(cur), hip.ptr(out), hip.ptr(table), k, hip.ptr(workspace), V, T, Hs, Ws, N)
+        hip.call("svit_randaug_stats" + suffix, hip.ptr(cur), hip.ptr(table), *ext, k, hip.ptr(workspace), V, T, Hs, Ws, N)
+        hip.call("svit_randaug_apply" + suffix, hip.ptr(cur), hip.ptr(out), hip.ptr(table), *ext, k, hip.ptr(workspace),
+                 V, T, Hs, Ws, N)
         cur = out
     return dst
