@@ -50,8 +50,27 @@ whole image and the records are validated (host) and clamped (device) against th
 kernels read the table at run time, so one captured step serves any mix of sizes up to the captured (Hs, Ws).
 `extents=None` is every video filling the buffer: the launches and bytes of before.
 
-Out of scope: tightly packed storage with per-video offsets, per-frame sizes inside one video, colour jitter (AUG.COLOR_JITTER, which the reference's loader never reads), DATA.TRAIN_JITTER_MOTION_SHIFT,
-boxes, the image ranks, AUG.RE_COUNT > 1 and bicubic resampling.  The reference's frames pass reads the same frames and
+Image ranks (IMAGE_TRAIN.GPU_IDS; the reference's `Ssv2_frames`, ssv2_frames.py:296-362,373-452): a still is a clip with
+T = 1 and runs the same pixel pipeline, and its hand / object boxes move with the pixels.  The boxes stay on the host --
+16 floats per still, NumPy in the reference too -- and follow the draws: `ra.draw(1, h, w, boxes=b)` (svit_amd/randaug.py),
+`sampler.draw(h, w, boxes=b)` (`boxes_through`: the reference's float32 arithmetic for `random_resized_crop`, the scale
+jitter + `random_crop` / `uniform_crop`, `horizontal_flip`; erasing leaves boxes alone) and `haog_targets(b, S)` (divide by
+S, clip to [0, 1], cxcywh, rows no larger than 0.05 zeroed).  `draw_still` does the three in the reference's order:
+
+    stills, extents = pack_videos([img[None] for img in images])            # host u8 [1,h,w,3] each
+    drawn = [draw_still(ra, sampler, h, w, boxes[v], video=v) for v, (h, w) in enumerate(extents.tolist())]
+    clips = AugClips(stills.cuda(), size, [r for _, r, _ in drawn], mean, std, randaug=pack_table([o for o, _, _ in drawn]),
+                     extents=extents)
+    meta = {"haog_bboxes": torch.stack([t for _, _, t in drawn]).cuda(), "contact_state": contact.cuda()}
+    model([clips], meta)          # or GraphedTrainStep(model, haog_loss, [clips], meta[, optimizer=...])
+
+One captured step serves every draw: a replay uploads stills, records, tables and extents through `AugClips.copy_` and
+the targets / contact states through the label tree.  The Shear boxes are geometric, not the reference's (randaug.py).
+
+Out of scope: tightly packed storage with per-video offsets, per-frame sizes inside one video, colour jitter
+(AUG.COLOR_JITTER, which the reference's loader never reads), DATA.TRAIN_JITTER_MOTION_SHIFT, the dataset class of the
+image ranks (JSON parsing, `match_haog`, JPEG decoding), mixup on image ranks, AUG.RE_COUNT > 1 and bicubic
+resampling.  The reference's frames pass reads the same frames and
 records: `input.FramesView(clips)` is the B*T frames as single-frame clips (`svit_im2col_patch_u8_aug_frames`; frame
 (b, t) through clip b's record, erase noise and mix partner included) and `GraphedTrainStep(..., frames_pass="u8")` runs
 it inside the replayed step; `frames_pass=True` stays the fp32 route and refuses an `AugClips`.
@@ -416,8 +435,16 @@ class SpatialSampler:
         self.trace.update(erase_tries=100)
         return None
 
-    def draw(self, Hs, Ws, video=0, spatial_idx=1):
-        """One clip's record for a Hs x Ws source.  spatial_idx: the test-time crop (0, 1, 2), "uniform" sampling only."""
+    def draw(self, Hs, Ws, video=0, spatial_idx=1, boxes=None):
+        """One clip's record for a Hs x Ws source.  spatial_idx: the test-time crop (0, 1, 2), "uniform" sampling only.
+        boxes: float32 [..., 4] xyxy in source pixels -> (record, boxes_out) with the boxes in the S x S window's pixels
+        (`boxes_through`; the draws are the same with and without them, erasing does not touch boxes)."""
+        rec = self._draw(Hs, Ws, video, spatial_idx)
+        if boxes is None:
+            return rec
+        return rec, boxes_through(rec, boxes, self.size, resized_crop=not self.uniform and self.scale is not None)
+
+    def _draw(self, Hs, Ws, video, spatial_idx):
         S = self.size
         self.trace = {}
         if self.uniform:
@@ -454,6 +481,56 @@ class SpatialSampler:
                 if mode in (ERASE_RAND, ERASE_PIXEL):
                     seed = random.getrandbits(31)       # the ONE draw the reference does not make (module docstring)
         return AugRecord(video, *geom, flip, mode, *box, seed)
+
+
+def boxes_through(rec, boxes, S, resized_crop):
+    """The boxes of a clip through its record, in the reference's float32 arithmetic (datasets/transform.py): boxes
+    float32 [..., 4] xyxy in source pixels -> the same shape in the S x S window's pixels.
+    resized_crop: `random_resized_crop` -- shift by (j, i), clip to [0, w] / [0, h], scale by S / w, S / h.  Otherwise
+    `random_short_side_scale_jitter` (ONE factor for both axes, none on its early return) and `crop_clip_boxes` with the
+    window's offsets (`random_crop`, `uniform_crop`).  Then `horizontal_flip`: S - boxes[:, [2, 0]] - 1."""
+    from .randaug import as_boxes
+    src = as_boxes(boxes)
+    b = src.reshape(-1, 4)
+    out = b.copy()
+    if resized_crop:
+        out[:, [0, 2]] = np.clip(b[:, [0, 2]] - rec.j, 0, rec.w) * float(S) / rec.w
+        out[:, [1, 3]] = np.clip(b[:, [1, 3]] - rec.i, 0, rec.h) * float(S) / rec.h
+    else:
+        if (rec.out_h, rec.out_w) != (rec.h, rec.w):
+            b = b * float(rec.out_h) / rec.h if rec.w < rec.h else b * float(rec.out_w) / rec.w
+        out[:, [0, 2]] = np.clip(b[:, [0, 2]] - rec.ox, 0, S)
+        out[:, [1, 3]] = np.clip(b[:, [1, 3]] - rec.oy, 0, S)
+    if rec.flip:
+        out[:, [0, 2]] = S - out[:, [2, 0]] - 1
+    return out.reshape(src.shape)
+
+
+def haog_targets(boxes, S):
+    """The HAOG box targets of ssv2_frames.py:347-353: boxes float32 [T,O,4] xyxy in the S x S window's pixels -> float32
+    tensor [T,O,4] cxcywh in [0, 1]; a box no wider or no higher than 0.05 (an absent or cropped-away object) is a zero
+    row (`box_ops.zero_empty_boxes`)."""
+    from .randaug import as_boxes
+    b = as_boxes(boxes)
+    b = np.clip(b / int(S), 0, 1)
+    x0, y0, x1, y1 = b[..., 0], b[..., 1], b[..., 2], b[..., 3]
+    out = np.stack([(x0 + x1) / 2, (y0 + y1) / 2, x1 - x0, y1 - y0], axis=-1)
+    if bool((out[..., 2:] < 0).any()):
+        raise ValueError("a box with x1 < x0 or y1 < y0 (the reference asserts on it as well)")
+    out[(out[..., 2:] <= 0.05).any(axis=-1)] = 0
+    return torch.from_numpy(out)
+
+
+def draw_still(randaug, sampler, Hs, Ws, boxes, video=0, spatial_idx=1):
+    """One still of an image rank in the reference's order (ssv2_frames.py:373-452: RandAugment BEFORE the spatial draw,
+    erasing last): boxes float32 [1,O,4] xyxy in the still's pixels -> (ops, record, target).  ops: the N RandAugOp of
+    `randaug.draw` (None without a RandAugSampler: AUG off, val / test); record: the AugRecord; target: `haog_targets`
+    of the boxes moved through both stages, float32 [1,O,4]."""
+    ops = None
+    if randaug is not None:
+        ops, boxes = randaug.draw(1, Hs, Ws, video=video, boxes=boxes)
+    rec, boxes = sampler.draw(Hs, Ws, video=video, spatial_idx=spatial_idx, boxes=boxes)
+    return ops, rec, haog_targets(boxes, sampler.size)
 
 
 def build_sampler(cfg, mode="train"):

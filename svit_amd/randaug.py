@@ -28,7 +28,18 @@ inside its extent every video gets the bytes it would get alone as a tight h_v x
 the affine fill boundary and tap clamps, the Sharpness border ring); the padding is copied.  None: every video fills the
 buffer, the launches and bytes of before.
 
-Out of scope: boxes, the image ranks, AUG.NUM_SAMPLE > 1, AUG.COLOR_JITTER (the reference's loader never reads it),
+Boxes (the image ranks: `Ssv2_frames` sends every still through `create_random_augment(..., with_boxes=True)`,
+ssv2_frames.py:373-398, and its hand / object boxes move with the pixels).  `ra.draw(T, Hs, Ws, boxes=b)` with b float32
+[T,O,4] (xyxy, source pixels) returns `(records, boxes_out)`; the draws are those of the box-aware transform
+(ssv2_MF/autoaugment.py), which consumes both streams exactly as the plain one.  Per layer (`boxes_layer`) the
+photometric operations leave the boxes, TranslateXRel / TranslateYRel and Rotate are the reference's arithmetic
+(boxes_autoaugment.py, boxes_aug/bbox_util.py::rotate_boxes with its `clip_box(..., 0.25)` zeroing), and all-zero rows
+are zero again after every layer.  ShearX / ShearY are NOT the reference's numbers: its box functions go through imgaug's
+fitted canvas; here the box is the enclosing box of the four corners under the affine map the pixel kernel applies for
+that record (x' = x - f y; ShearY y' = y - f x), clipped to the image -- consistent with the pixels produced, a
+documented deviation for 2 of the 15 operations.
+
+Out of scope: AUG.NUM_SAMPLE > 1, AUG.COLOR_JITTER (the reference's loader never reads it),
 policies other than `rand-...`, frames smaller than 3 x 3.
 """
 import collections
@@ -210,6 +221,96 @@ def make_op(name, args, filters, Hs, Ws):
     return RandAugOp(OP_AFFINE, bicubic_mask=mask, m=m)
 
 
+# ---- the box side of a layer (ssv2_MF/autoaugment.py::AugmentOp.__call__, boxes_autoaugment.py, boxes_aug/bbox_util.py) ----
+def as_boxes(boxes, ndim=None):
+    """a tensor or array of boxes -> a float32 NumPy copy [..., 4] (ndim: the rank it must have)"""
+    b = np.array(boxes.detach().cpu().numpy() if hasattr(boxes, "detach") else boxes, dtype=np.float32)
+    if b.shape[-1:] != (4,) or (ndim is not None and b.ndim != ndim):
+        raise ValueError("boxes are float32 %s (xyxy), got %s" % ("[T,O,4]" if ndim == 3 else "[..., 4]", tuple(b.shape)))
+    return b
+
+
+def rotate_boxes(boxes, degrees, Hs, Ws):
+    """`bbox_util.rotate_boxes` restated for float32 [N,4]: the corners through OpenCV's rotation matrix about
+    (Ws // 2, Hs // 2) on the fitted canvas, their enclosing box, the centre crop back to Ws x Hs and `clip_box(...,
+    0.25)` -- a box that keeps less than a quarter of its area inside the image (or has none) becomes a zero row."""
+    b = np.asarray(boxes, dtype=np.float32).reshape(-1, 4)
+    w, h = int(Ws), int(Hs)
+    cx, cy = w // 2, h // 2
+    a = math.radians(degrees)
+    alpha, beta = math.cos(a), math.sin(a)
+    nW, nH = int(h * abs(beta) + w * abs(alpha)), int(h * abs(alpha) + w * abs(beta))
+    M = np.array([[alpha, beta, (1 - alpha) * cx - beta * cy + (nW / 2 - cx)],
+                  [-beta, alpha, beta * cx + (1 - alpha) * cy + (nH / 2 - cy)]], dtype=np.float64)
+    x1, y1 = b[:, 0], b[:, 1]
+    x2, y3 = x1 + (b[:, 2] - b[:, 0]), y1 + (b[:, 3] - b[:, 1])
+    px = np.stack([x1, x2, x1, b[:, 2]], axis=1)                               # the reference's corner order
+    py = np.stack([y1, y1, y3, b[:, 3]], axis=1)
+    pts = np.stack([px, py, np.ones_like(px)], axis=2).reshape(-1, 3)         # float32 [4N,3]
+    moved = np.dot(M, pts.T).T.reshape(-1, 4, 2).astype(np.float32)
+    out = np.stack([moved[..., 0].min(1), moved[..., 1].min(1), moved[..., 0].max(1), moved[..., 1].max(1)], axis=1)
+    w_delta, h_delta = (nW - w) / 2, (nH - h) / 2
+    out[:, [0, 2]] = np.clip(out[:, [0, 2]], w_delta, nW - w_delta) - w_delta
+    out[:, [1, 3]] = np.clip(out[:, [1, 3]], h_delta, nH - h_delta) - h_delta
+    with np.errstate(all="ignore"):
+        area = (out[:, 2] - out[:, 0]) * (out[:, 3] - out[:, 1])
+        cl = np.stack([np.maximum(out[:, 0], 0), np.maximum(out[:, 1], 0), np.minimum(out[:, 2], w),
+                       np.minimum(out[:, 3], h)], axis=1)
+        lost = (area - (cl[:, 2] - cl[:, 0]) * (cl[:, 3] - cl[:, 1])) / area
+        cl[~(lost < 1 - 0.25)] = 0
+    return cl
+
+
+def shear_boxes(boxes, factor, Hs, Ws, axis):
+    """The GEOMETRIC box side of ShearX (axis 0) / ShearY (axis 1): the enclosing box of the four corners moved by the
+    map the pixels of that record follow -- PIL's (1, f, 0, 0, 1, 0) takes output to source, so x' = x - f y (ShearY:
+    y' = y - f x) -- in float64, clipped to [0, Ws] x [0, Hs], one rounding to float32.  Factor 0 returns the boxes.
+    NOT the reference's numbers: its `shear_x_iaa` / `shear_y_iaa` go through imgaug's fitted canvas."""
+    b = np.asarray(boxes, dtype=np.float32).reshape(-1, 4)
+    if factor == 0:
+        return b.copy()
+    d = b.astype(np.float64)
+    f = float(factor)
+    out = d.copy()
+    if axis == 0:
+        out[:, 0] = np.minimum(d[:, 0] - f * d[:, 1], d[:, 0] - f * d[:, 3])
+        out[:, 2] = np.maximum(d[:, 2] - f * d[:, 1], d[:, 2] - f * d[:, 3])
+    else:
+        out[:, 1] = np.minimum(d[:, 1] - f * d[:, 0], d[:, 1] - f * d[:, 2])
+        out[:, 3] = np.maximum(d[:, 3] - f * d[:, 0], d[:, 3] - f * d[:, 2])
+    out[:, [0, 2]] = np.clip(out[:, [0, 2]], 0, Ws)
+    out[:, [1, 3]] = np.clip(out[:, [1, 3]], 0, Hs)
+    return out.astype(np.float32)
+
+
+def boxes_layer(name, args, boxes, Hs, Ws):
+    """One layer's box side, a pure function of (operation name, level arguments, size): boxes float32 [T,O,4] xyxy ->
+    a new array.  Photometric operations leave them; TranslateXRel / TranslateYRel and Rotate are the reference's
+    arithmetic (float32); ShearX / ShearY are `shear_boxes`.  Rows that were all zero (absent objects) are zero again
+    afterwards, as AugmentOp.__call__ restores them."""
+    base = name.replace("Increasing", "")
+    if base not in GEOMETRIC:
+        return boxes
+    zero = (boxes == 0).all(axis=-1)
+    b = boxes.reshape(-1, 4)
+    v = args[0]
+    if base == "Rotate":
+        out = rotate_boxes(b, v, Hs, Ws)
+    elif base == "ShearX":
+        out = shear_boxes(b, v, Hs, Ws, 0)
+    elif base == "ShearY":
+        out = shear_boxes(b, v, Hs, Ws, 1)
+    else:
+        out = b.copy()
+        if base == "TranslateXRel":
+            out[:, [0, 2]] = b[:, [0, 2]] - Ws * v
+        else:
+            out[:, [1, 3]] = b[:, [1, 3]] - Hs * v
+    out = out.reshape(boxes.shape)
+    out[zero] = 0
+    return out
+
+
 class RandAugSampler:
     """The reference's `create_random_augment(...)` for one clip as N RandAugOp."""
 
@@ -226,10 +327,14 @@ class RandAugSampler:
             raise NotImplementedError("AUG.INTERPOLATION %r: PIL's affine transform refuses it too" % (interpolation,))
         self.trace = []         # what the last draw() chose: [(name, level arguments, per-frame filters)] per layer
 
-    def draw(self, T, Hs, Ws, video=0):
-        """One clip's N records for T frames of Hs x Ws (`video` names the table row they are meant for)."""
+    def draw(self, T, Hs, Ws, video=0, boxes=None):
+        """One clip's N records for T frames of Hs x Ws (`video` names the table row they are meant for).
+        boxes: float32 [T,O,4] xyxy in source pixels -> (records, boxes_out): the boxes moved through the same layers
+        (`boxes_layer`; the draws are the same with and without them)."""
         if self.filter is None and T > 32:
             raise NotImplementedError("INTERPOLATION random draws one filter per frame: T <= 32 (bicubic_mask is 32 bits)")
+        if boxes is not None:
+            boxes = as_boxes(boxes, 3)
         picks = np.random.choice(len(self.transforms), self.num_layers, replace=self.weights is None, p=self.weights)
         self.trace, ops = [], []
         for k in picks:
@@ -251,7 +356,9 @@ class RandAugSampler:
                     filters = (self.filter,) * T
             self.trace.append((name, args, filters))
             ops.append(make_op(name, args, filters, Hs, Ws))
-        return ops
+            if boxes is not None:
+                boxes = boxes_layer(name, args, boxes, Hs, Ws)
+        return ops if boxes is None else (ops, boxes)
 
 
 def build_randaug(cfg):
