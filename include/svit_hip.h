@@ -706,6 +706,15 @@ int svit_meter_push(float* ring, int W, int K, int64_t* state, const float* cons
 /* NT GEMM (csrc/gemm_nt.hip): key 0 = pipeline stages (2..4, 0 = heuristic), key 1 = forced tile/ring
  * configuration (-1 = heuristic, 0..10; 8 = the pre-ring v2 heuristic), key 2 = forced K-step (32 / 64, 0 = heuristic). */
 int svit_debug_set(int key, int val);
+/* Which kernel svit_gemm_nt would launch for a shape and an epilogue, and how -- the launch path's own chooser (csrc/gemm_nt.hip,
+ * nt_choose), asked with plain integers under the current values of the three keys above.  Launches nothing and needs no
+ * device.  The shape is checked as svit_gemm_nt checks it (SVIT_ERR_SHAPE: M, N, K <= 0, K % 32, N % 96; SVIT_ERR_ARG: no
+ * such epilogue).  Fills out (n_out >= 13) and returns the number of values written, or an error code:
+ *   family (0 gemm_nt_v2_kernel, 1 gemm_nt_ring_kernel); the template parameters RB, NB, WAVES_M, WAVES_N, loader waves
+ *   (0 for v2), STAGES, K-step -- the tile is 32 RB WAVES_M rows x 32 NB WAVES_N columns; grid x, grid y; block size;
+ *   dynamic LDS bytes; the rule that decided the tile (0 forced by key 1 / 2, 1 ring_few_long_tiles, 2 ring_long_k_narrow,
+ *   3 bk64_narrow_long_k, 4 one_round_160x256, 5 one_round_192x192, 6 square_128x128, 7 big_128x192, 8 default_128x96). */
+int svit_debug_gemm_nt_plan(int M, int N, int K, int epilogue, int32_t* out, int n_out);
 /* grouped TN GEMM (csrc/gemm_tn.hip): cost-model constants of the row-chunk planner (x 0.01: microseconds per
  * k-step, TB/s of the fp32-atomic flush; <= 0 leaves a constant unchanged), and the tile mode (0: 128x96 only,
  * 1: per-problem heuristic fitted on isolated launches, 2: 128x192 everywhere (default), 3: 128x192 where

@@ -14,6 +14,7 @@
 // (wave-uniform base + lane*16); the four 16-B chunks of a row are XOR-swizzled with
 // ((row>>2)&3) on the per-lane SOURCE address, and the same XOR is applied on the fragment
 // reads -> ds_read_b128 of 16 consecutive rows hits 16 distinct slots of the 256-B bank row.
+#include <cstring>
 #include "gemm_epilogue.h"
 #include "attn_common.h"   // Int / static_for / lds_read128 / lgkm_release1
 
@@ -141,42 +142,6 @@ gemm_nt_v2_kernel(svit_gemm_args p) {
   // (staging regions are per wave: no workgroup barrier inside the epilogue -- eight of them per 128x128 tile
   // kept the four waves in lock step through their stores)
   nt_epilogue<RB, NB, EPI, true>(p, acc, smem, m0, n0, wm, wn, lane, wave);
-}
-
-template <int RB, int NB, int WAVES_M, int WAVES_N, int STAGES, int BK2 = 32>
-int launch_v2(const svit_gemm_args& a, hipStream_t st) {
-  constexpr int BM = 32 * RB * WAVES_M, BN = 32 * NB * WAVES_N;
-  constexpr int NT = WAVES_M * WAVES_N * 64;
-  constexpr int RPR = NT / (BK2 / 8);
-  size_t lds = (size_t)STAGES * ((BM + BN + RPR - 1) / RPR * RPR) * BK2 * 2;
-  const size_t lds_epi = (size_t)WAVES_M * WAVES_N * 16 * (32 * NB + 4) * sizeof(float);
-  if (lds < lds_epi) lds = lds_epi;
-  dim3 grid((a.N + BN - 1) / BN, (a.M + BM - 1) / BM);
-  static SvitOnce once[6];
-#define SVIT_V2_ATTR(E)                                                                              \
-  if (int rc = svit_max_lds_once(once[E], (const void*)gemm_nt_v2_kernel<RB, NB, WAVES_M, WAVES_N, STAGES, E, BK2>, lds)) \
-    return rc
-  SVIT_V2_ATTR(SVIT_EPI_BF16); SVIT_V2_ATTR(SVIT_EPI_GELU); SVIT_V2_ATTR(SVIT_EPI_RESID);
-  SVIT_V2_ATTR(SVIT_EPI_F32); SVIT_V2_ATTR(SVIT_EPI_DGELU); SVIT_V2_ATTR(SVIT_EPI_RELQ);
-#undef SVIT_V2_ATTR
-#define SVIT_V2_CASE(E)                                                                       \
-  case E:                                                                                     \
-    hipLaunchKernelGGL((gemm_nt_v2_kernel<RB, NB, WAVES_M, WAVES_N, STAGES, E, BK2>), grid, dim3(NT), \
-                       lds, st, a);                                                           \
-    break;
-  switch (a.epilogue) {
-    SVIT_V2_CASE(SVIT_EPI_BF16)
-    SVIT_V2_CASE(SVIT_EPI_GELU)
-    SVIT_V2_CASE(SVIT_EPI_RESID)
-    SVIT_V2_CASE(SVIT_EPI_F32)
-    SVIT_V2_CASE(SVIT_EPI_DGELU)
-    SVIT_V2_CASE(SVIT_EPI_RELQ)
-    default:
-      return SVIT_ERR_ARG;
-  }
-#undef SVIT_V2_CASE
-  SVIT_LAUNCH_CHECK();
-  return SVIT_OK;
 }
 
 // ---- ring form: loader waves + MFMA waves (long-K GEMMs) ---------------------------------------------
@@ -339,56 +304,185 @@ __global__ __launch_bounds__((WAVES_M * WAVES_N + NL) * 64, 1) void gemm_nt_ring
   nt_epilogue<RB, NB, EPI, true>(p, acc, epi, m0, n0, wm, wn, lane, wave);
 }
 
-template <int RB, int NB, int WAVES_M, int WAVES_N, int NL, int STAGES>
-int launch_ring(const svit_gemm_args& a, hipStream_t st) {
-  constexpr int BM = 32 * RB * WAVES_M, BN = 32 * NB * WAVES_N, NT = (WAVES_M * WAVES_N + NL) * 64;
-  constexpr size_t lds = (size_t)STAGES * (BM + BN) * 128;
-  static_assert((size_t)WAVES_M * WAVES_N * 16 * (32 * NB + 4) * sizeof(float) <= (size_t)(BM + BN) * 128, "epilogue staging fits a slot");
-  static_assert(lds <= 160 * 1024, "LDS");
-  dim3 grid((a.N + BN - 1) / BN, (a.M + BM - 1) / BM);
-  static SvitOnce once[5];
-#define SVIT_RING_ATTR(E)                                                                              \
-  if (int rc = svit_max_lds_once(once[E], (const void*)gemm_nt_ring_kernel<RB, NB, WAVES_M, WAVES_N, NL, STAGES, E>, lds)) \
-    return rc
-  SVIT_RING_ATTR(SVIT_EPI_BF16); SVIT_RING_ATTR(SVIT_EPI_GELU); SVIT_RING_ATTR(SVIT_EPI_RESID);
-  SVIT_RING_ATTR(SVIT_EPI_F32); SVIT_RING_ATTR(SVIT_EPI_DGELU);
-#undef SVIT_RING_ATTR
-#define SVIT_RING_CASE(E)                                                                       \
-  case E:                                                                                       \
-    hipLaunchKernelGGL((gemm_nt_ring_kernel<RB, NB, WAVES_M, WAVES_N, NL, STAGES, E>), grid, dim3(NT), lds, st, a); \
-    break;
-  switch (a.epilogue) {
-    SVIT_RING_CASE(SVIT_EPI_BF16)
-    SVIT_RING_CASE(SVIT_EPI_GELU)
-    SVIT_RING_CASE(SVIT_EPI_RESID)
-    SVIT_RING_CASE(SVIT_EPI_F32)
-    SVIT_RING_CASE(SVIT_EPI_DGELU)
-    default:
-      return SVIT_ERR_ARG;
+// ---- host side: shape -> choice (nt_choose) -> row of nt_forms -> launch ---------------------------------------
+// The template parameters of a kernel as integers: NL loader waves (0: gemm_nt_v2_kernel, else gemm_nt_ring_kernel).
+struct NtParams { int family /* 0 v2, 1 ring */, RB, NB, WM, WN, NL, stages, BK; };
+// One instantiated form: its kernel per epilogue (nullptr: no ring kernel takes SVIT_EPI_RELQ) and the per-device state
+// of svit_max_lds_once.
+typedef void (*NtKernel)(svit_gemm_args);
+struct NtForm { NtParams p; NtKernel kernel[6]; SvitOnce once[6]; };
+template <int RB, int NB, int WM, int WN, int ST, int BK>
+constexpr NtForm v2_form() {
+  return {{0, RB, NB, WM, WN, 0, ST, BK},
+          {gemm_nt_v2_kernel<RB, NB, WM, WN, ST, SVIT_EPI_BF16, BK>, gemm_nt_v2_kernel<RB, NB, WM, WN, ST, SVIT_EPI_GELU, BK>,
+           gemm_nt_v2_kernel<RB, NB, WM, WN, ST, SVIT_EPI_RESID, BK>, gemm_nt_v2_kernel<RB, NB, WM, WN, ST, SVIT_EPI_F32, BK>,
+           gemm_nt_v2_kernel<RB, NB, WM, WN, ST, SVIT_EPI_DGELU, BK>, gemm_nt_v2_kernel<RB, NB, WM, WN, ST, SVIT_EPI_RELQ, BK>}, {}};
+}
+template <int RB, int NB, int WM, int WN, int NL, int ST>
+constexpr NtForm ring_form() {
+  constexpr int BM = 32 * RB * WM, BN = 32 * NB * WN;
+  static_assert((size_t)WM * WN * 16 * (32 * NB + 4) * sizeof(float) <= (size_t)(BM + BN) * 128, "epilogue staging fits a slot");
+  static_assert((size_t)ST * (BM + BN) * 128 <= 160 * 1024, "LDS");
+  return {{1, RB, NB, WM, WN, NL, ST, 64},
+          {gemm_nt_ring_kernel<RB, NB, WM, WN, NL, ST, SVIT_EPI_BF16>, gemm_nt_ring_kernel<RB, NB, WM, WN, NL, ST, SVIT_EPI_GELU>,
+           gemm_nt_ring_kernel<RB, NB, WM, WN, NL, ST, SVIT_EPI_RESID>, gemm_nt_ring_kernel<RB, NB, WM, WN, NL, ST, SVIT_EPI_F32>,
+           gemm_nt_ring_kernel<RB, NB, WM, WN, NL, ST, SVIT_EPI_DGELU>, nullptr}, {}};
+}
+// Every kernel the library holds (29 forms, 165 kernels), in the order nt_choose's rules name the tiles.  Only the knobs
+// (tools, variant and parity tests) reach 3 stages on a v2 tile, K-step 64 on any tile but 128x96 at depth 2, the
+// 128x128 ring tile and the ring depths a rule does not name.
+NtForm nt_forms[] = {
+    ring_form<2, 3, 2, 2, 4, 2>(), ring_form<2, 3, 2, 2, 4, 3>(), ring_form<2, 3, 2, 2, 4, 4>(),   // 128x192 ring
+    ring_form<1, 3, 4, 1, 4, 2>(), ring_form<1, 3, 4, 1, 4, 3>(), ring_form<1, 3, 4, 1, 4, 4>(),   // 128x96 ring
+    ring_form<2, 2, 2, 2, 4, 2>(), ring_form<2, 2, 2, 2, 4, 3>(), ring_form<2, 2, 2, 2, 4, 4>(),   // 128x128 ring
+    v2_form<1, 3, 4, 1, 2, 64>(),                                                                  // 128x96, K-step 64
+    v2_form<5, 2, 1, 4, 2, 32>(), v2_form<3, 3, 2, 2, 2, 32>(),                                    // 160x256, 192x192
+    v2_form<2, 2, 2, 2, 2, 64>(), v2_form<2, 2, 2, 2, 3, 64>(), v2_form<2, 2, 2, 2, 4, 64>(),      // 128x128
+    v2_form<2, 2, 2, 2, 2, 32>(), v2_form<2, 2, 2, 2, 3, 32>(), v2_form<2, 2, 2, 2, 4, 32>(),
+    v2_form<2, 3, 2, 2, 2, 64>(), v2_form<2, 3, 2, 2, 3, 64>(), v2_form<2, 3, 2, 2, 4, 64>(),      // 128x192
+    v2_form<2, 3, 2, 2, 2, 32>(), v2_form<2, 3, 2, 2, 3, 32>(), v2_form<2, 3, 2, 2, 4, 32>(),
+    v2_form<1, 3, 4, 1, 3, 64>(), v2_form<1, 3, 4, 1, 4, 64>(),                                    // 128x96
+    v2_form<1, 3, 4, 1, 2, 32>(), v2_form<1, 3, 4, 1, 3, 32>(), v2_form<1, 3, 4, 1, 4, 32>(),
+};
+
+enum NtRule { NT_FORCED, NT_RING_FEW_LONG_TILES, NT_RING_LONG_K_NARROW, NT_BK64_NARROW_LONG_K, NT_ONE_ROUND_160X256,
+              NT_ONE_ROUND_192X192, NT_SQUARE_128X128, NT_BIG_128X192, NT_DEFAULT_128X96 };
+struct NtKnobs { int cfg, stages, bk; };      // SVIT_K_NT_CFG / _STAGES / _BK (svit_debug_set; tools and variant tests only)
+struct NtChoice { NtParams p; unsigned gx, gy, block; size_t lds; int rule /* the NtRule that decided the tile */; };
+
+// a tile and its launch geometry (stages: anything but 2 / 3 is 4 -- the knob admits 0 and 2..4 only)
+NtChoice nt_tile(int family, int RB, int NB, int WM, int WN, int stages, int BK, int rule, int M, int N) {
+  NtChoice c = {{family, RB, NB, WM, WN, family ? 4 : 0, stages == 2 || stages == 3 ? stages : 4, BK}};
+  const int BM = 32 * RB * WM, BN = 32 * NB * WN, waves = WM * WN;
+  c.gx = (N + BN - 1) / BN, c.gy = (M + BM - 1) / BM, c.block = (waves + c.p.NL) * 64, c.rule = rule;
+  if (family) {
+    c.lds = (size_t)c.p.stages * (BM + BN) * 128;      // (the epilogue's staging fits a slot: ring_form)
+  } else {   // rows per stage padded to whole rounds of loads; at least the epilogue's staging
+    const int RPR = waves * 64 / (BK / 8);
+    c.lds = (size_t)c.p.stages * ((BM + BN + RPR - 1) / RPR * RPR) * BK * 2;
+    const size_t lds_epi = (size_t)waves * 16 * (32 * NB + 4) * sizeof(float);
+    if (c.lds < lds_epi) c.lds = lds_epi;
   }
-#undef SVIT_RING_CASE
-  SVIT_LAUNCH_CHECK();
-  return SVIT_OK;
+  return c;
+}
+
+// Which kernel, for a shape that passed nt_check_shape.  Pure: svit_gemm_nt launches what it answers and
+// svit_debug_gemm_nt_plan reports it.  The rules stand in their order of precedence; the first that holds returns.
+//
+// What the tile rules rest on (measured on MI355X, tools/bench_kernels.py ntstages): 128x192 blocks (2x2 waves of 64x96) win
+// whenever they still give >= 1 tile per CU; otherwise, and for N = 96 (mod 192), 128x96 blocks (4 waves of 32x96) double
+// the number of workgroups.  A 256x192 / 8-wave tile (fewer LDS-fill bytes per flop) was measured too and never won.  At
+// M = 13064 every variant lands within 10 % of the others: the bound is the per-CU LDS fill rate (~40 GB/s per CU,
+// ~10 TB/s chip-wide for the mix of L2 and Infinity-Cache hits), not the pipeline depth, the fragment-read scheduling or
+// the tile shape.  Also measured and rejected:
+//  * a persistent form (a workgroup walks several tiles and issues the next tile's first LDS-DMA from inside the epilogue
+//    of the current one; commit "experiment: persistent NT GEMM", profiles/r02_nt_persistent_tiles.txt): -10..-17 % on the
+//    many-tile K = 384 shapes of the 56x56 stage, +5..10 % wherever the epilogue writes two outputs or fp32 rows -- the
+//    next tile's first s_waitcnt vmcnt(0) also waits for this tile's stores, which a finishing workgroup never does.
+//    Net zero over the step; not kept.
+//  * a register-staged form (global_load_dwordx4 -> VGPR -> ds_write_b128, K-step 64, loads a whole K-step ahead; commit
+//    "experiment: register-staged NT GEMM variant", profiles/r02_nt_tile_sweep.txt column REG): 5-10 % slower than
+//    LDS-DMA on every shape -- the bound is the CU's vector-memory path itself (SQ counters, profiles/
+//    r02_nt_pmc_13064x384x1536.txt: waves spend 51 % of their cycles stalled at instruction issue with the MFMA pipe
+//    28 % busy; ~35 cycles per 1-KiB load instruction per CU = 29 B/clk/CU = 56 GB/s/CU), not how the bytes reach LDS.
+//  * a row-stationary form for K <= 384 (8-wave workgroups, A rows held in registers as MFMA fragments, only W streamed
+//    through a 4-deep LDS ring: 4x fewer fill bytes per flop) -- 0.6-0.9x the speed of these tiles on every shape of
+//    the model: one barrier-locked workgroup per CU leaves nothing to overlap its epilogues and barriers with.
+NtChoice nt_choose(int M, int N, int K, int epilogue, NtKnobs kn) {
+  // cfg: 0 / 2 / 4 = v2 tiles 128x192 / 128x96 / 128x128, 5 / 6 / 7 = the same as ring tiles, 9 / 10 = the one-round
+  // tiles, -1 = heuristic.  Knob value 8 is no tile: it means "the v2 heuristic, no ring".
+  const int cfg = kn.cfg == 8 ? -1 : kn.cfg;
+  const bool heuristic = cfg < 0 && !kn.stages && !kn.bk;   // nothing forced at all
+  const long tm = (M + 127) / 128;                           // 128-row tiles along M
+
+  // ---- 1. ring kernels (loader waves + MFMA waves, K-steps of 64) ----------------------------------------------
+  // They exist for K % 64 == 0 only, and none has the SVIT_EPI_RELQ epilogue: both fall through to the v2 rules, a
+  // forced ring tile included (it then switches rules 3 to 6 off and leaves 7 / 8 to the heuristic).
+  if (K % 64 == 0 && epilogue != SVIT_EPI_RELQ) {
+    const int rs = kn.stages ? kn.stages : 3;                // a forced ring tile is 3 deep unless told otherwise
+    if (cfg == 5) return nt_tile(1, 2, 3, 2, 2, rs, 64, NT_FORCED, M, N);
+    if (cfg == 6) return nt_tile(1, 1, 3, 4, 1, rs, 64, NT_FORCED, M, N);
+    if (cfg == 7) return nt_tile(1, 2, 2, 2, 2, rs, 64, NT_FORCED, M, N);
+    // Which ring kernel, if any.  Two sets of measurements on MI355X decide (profiles/r03_nt_ring.txt): isolated
+    // loops per epilogue family (tools/bench_kernels.py ntring <epilogue>), where the ring kernels win almost
+    // everywhere K % 64 == 0, and the replayed training step with every NT launch matched by position
+    // (tools/nt_by_position.py), where the short-K wins do NOT survive (a launch's neighbours are other kernels, not
+    // copies of itself: 128x128 / 2 stages for fc1 was +5 % there, 128x96 / 2 stages at K = 384 +11 %).  Kept are
+    // the two rules that win in both.  Knob value 8 switches them off, and so does ANY forced K-step (a set
+    // SVIT_K_NT_BK asks for a v2 kernel); a forced stage count does not reach them: they bring their own depth.
+    if (cfg < 0 && kn.cfg != 8 && !kn.bk) {
+      const long t192 = N % 192 == 0 ? tm * (N / 192) : 0, t96 = tm * ((N + 95) / 96);
+      // few, long tiles: every 128x96 tile has a CU to itself -> 4-deep ring (3656 x 768 x 768..3072: -30 %)
+      constexpr int k_min5 = 1024, t_max6 = 256, s6 = 4;     // (swept inside the step in round 4: profiles/r04_in_step_sweeps.txt)
+      // (> 256 tiles: two workgroups per CU need the 2-stage ring -- an arm no shape takes while t_max6 is 256)
+      if (t96 <= t_max6 && K >= 768) return nt_tile(1, 1, 3, 4, 1, t96 > 256 ? 2 : s6, 64, NT_RING_FEW_LONG_TILES, M, N);
+      // long K, narrow output, enough 128x192 tiles for most CUs (13064 x 384 x 1152..2304: -6..-10 % in the
+      // step, -15..-20 % isolated; on a par with hipBLASLt's 128x160x64 macro-tile)
+      if (t192 >= 160 && N <= 768 && K >= k_min5) return nt_tile(1, 2, 3, 2, 2, 3, 64, NT_RING_LONG_K_NARROW, M, N);
+    }
+  }
+
+  // ---- 2. the v2 kernel's depth and K-step ----------------------------------------------------------------------
+  // pipeline depth (measured, tools/bench_kernels.py ntstages): short K loops prefer 2 stages (less LDS -> more resident
+  // workgroups), K >= 2048 wants the 4-deep prefetch
+  const int stages = kn.stages ? kn.stages : (K >= 2048 ? 4 : 2);
+  // K-step of 64 (whole 128-B lines per tile row; half as many barriers): measured 5-14 % faster for the narrow-output,
+  // long-K GEMMs (fc2, proj, qkv dgrad: N <= 768, K >= 384) as 128x96 blocks at depth 2, and slower elsewhere -- the 2x LDS
+  // per stage costs a resident workgroup (tools/bench_kernels.py ntstages, profiles/r02_nt_tile_sweep.txt).  A forced
+  // K-step of 64 is 32 where K % 64 != 0.
+  const bool bk64 = kn.bk ? kn.bk == 64 && K % 64 == 0 : K % 64 == 0 && N <= 768 && K >= 384;
+  const int BK = bk64 ? 64 : 32;
+
+  // ---- 3. K-step 64 takes the 128x96 tile at depth 2, whatever the tile rules below would say -- unless a tile or a
+  // depth is forced (a forced K-step of 64 alone lands here too)
+  if (bk64 && cfg < 0 && !kn.stages) return nt_tile(0, 1, 3, 4, 1, 2, 64, kn.bk ? NT_FORCED : NT_BK64_NARROW_LONG_K, M, N);
+
+  // ---- 4. / 5. ONE-ROUND tiles for the wide short-K GEMMs of the 14x14 stage (round 4) ------------------------------
+  // At M = 13064 the 128-row tiles below put 824 (128x192) or 1236 (128x128) workgroups on 512-768 slots: a second,
+  // part-filled round in which the chip mostly stores.  160x256 (1 x 4 waves of 160x64) covers 13064 x 1536 with
+  // 82 x 6 = 492 workgroups, 192x192 (2 x 2 waves of 96x96) covers 13064 x 1152 with 69 x 6 = 414: every workgroup
+  // resident at once (two per CU), more flops per LDS-fill byte (91 / 96 against 77 / 64).  Heuristic: only where the
+  // grid is one round and the 128-row grid is not, and nothing is forced.  cfg 9 / 10 force them, always at depth 2 and
+  // K-step 32 (forced stages / K-step are not looked at); a forced one whose width does not divide N falls through.
+  const long t160 = N % 256 == 0 ? (long)((M + 159) / 160) * (N / 256) : 0;
+  const long t192 = N % 192 == 0 ? (long)((M + 191) / 192) * (N / 192) : 0;
+  const bool auto_ok = heuristic && K <= 512 && tm * ((N + 191) / 192) > 512;
+  if (N % 256 == 0 && (cfg == 9 || (auto_ok && t160 > 256 && t160 <= 512)))
+    return nt_tile(0, 5, 2, 1, 4, 2, 32, cfg == 9 ? NT_FORCED : NT_ONE_ROUND_160X256, M, N);
+  if (N % 192 == 0 && (cfg == 10 || (auto_ok && t192 > 256 && t192 <= 512)))
+    return nt_tile(0, 3, 3, 2, 2, 2, 32, cfg == 10 ? NT_FORCED : NT_ONE_ROUND_192X192, M, N);
+
+  // ---- 6. 128x128 blocks (2x2 waves of 64x64): measured ~10 % faster than 128x192 for the wide, short-K
+  // GEMMs of the 14x14 stage (M = 13064, N = 1152 / 1536, K = 384: fc1, fc2-dgrad, qkv).  Any forced tile but cfg 4
+  // switches the rule off; cfg 4 where 128 does not divide N falls through.
+  if (cfg == 4 ? N % 128 == 0 : cfg < 0 && N % 128 == 0 && N >= 1024 && K <= 512 && tm * (N / 128) <= 2048)
+    return nt_tile(0, 2, 2, 2, 2, stages, BK, cfg == 4 ? NT_FORCED : NT_SQUARE_128X128, M, N);
+
+  // ---- 7. 128x192 blocks where they give a tile per CU.  cfg 0 forces them where 192 divides N (else it falls through
+  // to rule 8); cfg 2 switches the rule off; every other forced tile that came this far (5..7, 9, 10, a 4 that did not
+  // divide) leaves it to the heuristic.
+  if (N % 192 == 0 && cfg != 2 && (cfg == 0 || tm * (N / 192) >= 256))
+    return nt_tile(0, 2, 3, 2, 2, stages, BK, cfg == 0 ? NT_FORCED : NT_BIG_128X192, M, N);
+
+  // ---- 8. 128x96 blocks: every N the entry point accepts
+  return nt_tile(0, 1, 3, 4, 1, stages, BK, cfg == 2 ? NT_FORCED : NT_DEFAULT_128X96, M, N);
+}
+
+// the row of nt_forms a choice names and its kernel for an epilogue; nullptr: nt_choose and nt_forms disagree
+NtForm* nt_form_of(const NtChoice& c, int epilogue) {
+  for (NtForm& r : nt_forms)      // (family follows from NL)
+    if (r.p.RB == c.p.RB && r.p.NB == c.p.NB && r.p.WM == c.p.WM && r.p.WN == c.p.WN && r.p.NL == c.p.NL &&
+        r.p.stages == c.p.stages && r.p.BK == c.p.BK)
+      return epilogue >= 0 && epilogue <= SVIT_EPI_RELQ && r.kernel[epilogue] ? &r : nullptr;
+  return nullptr;
+}
+
+NtKnobs nt_knobs() { return {svit_knob(SVIT_K_NT_CFG), svit_knob(SVIT_K_NT_STAGES), svit_knob(SVIT_K_NT_BK)}; }
+
+int nt_check_shape(int M, int N, int K) {
+  return M <= 0 || N <= 0 || K <= 0 || K % 32 != 0 || N % 96 != 0 ? SVIT_ERR_SHAPE : SVIT_OK;
 }
 }  // namespace
-
-// tuning knobs: SVIT_K_NT_STAGES / _CFG / _BK of the table in common.h (svit_debug_set, tools and variant-parity tests only)
-// Which ring kernel, if any.  Two sets of measurements on MI355X decide (profiles/r03_nt_ring.txt):
-// isolated loops per epilogue family (tools/bench_kernels.py ntring <epilogue>), where the ring kernels win
-// almost everywhere K % 64 == 0, and the replayed training step with every NT launch matched by position
-// (tools/nt_by_position.py), where the short-K wins do NOT survive (a launch's neighbours are other kernels,
-// not copies of itself: 128x128 / 2 stages for fc1 was +5 % there, 128x96 / 2 stages at K = 384 +11 %).
-// Kept are the two rules that win in both: *cfg stays < 0 otherwise (v2 kernels).
-static void ring_choice(const svit_gemm_args& a, int* cfg, int* stages) {
-  const long tm = (a.M + 127) / 128;
-  const long t192 = a.N % 192 == 0 ? tm * (a.N / 192) : 0, t96 = tm * ((a.N + 95) / 96);
-  // few, long tiles: every 128x96 tile has a CU to itself -> 4-deep ring (3656 x 768 x 768..3072: -30 %)
-  constexpr int k_min5 = 1024, t_max6 = 256, s6 = 4;     // (swept inside the step in round 4: profiles/r04_in_step_sweeps.txt)
-  if (t96 <= t_max6 && a.K >= 768) { *cfg = 6, *stages = (t96 > 256 ? 2 : s6); return; }   // (> 256 tiles: two workgroups per CU need the 2-stage ring)
-  // long K, narrow output, enough 128x192 tiles for most CUs (13064 x 384 x 1152..2304: -6..-10 % in the
-  // step, -15..-20 % isolated; on a par with hipBLASLt's 128x160x64 macro-tile)
-  if (t192 >= 160 && a.N <= 768 && a.K >= k_min5) { *cfg = 5, *stages = 3; return; }
-}
 
 extern "C" int svit_gemm_nt(const svit_gemm_args* args, void* stream) {
   if (!args || !args->A || !args->W) return SVIT_ERR_ARG;
@@ -400,7 +494,7 @@ extern "C" int svit_gemm_nt(const svit_gemm_args* args, void* stream) {
         a.relq_ld < 96 + a.relq_extra || a.bias)
       return SVIT_ERR_ARG;
   }
-  if (a.M <= 0 || a.N <= 0 || a.K <= 0 || a.K % 32 != 0 || a.N % 96 != 0) return SVIT_ERR_SHAPE;
+  if (int rc = nt_check_shape(a.M, a.N, a.K)) return rc;
   if (a.lda % 8 != 0 || a.ldw % 8 != 0 || a.lda < a.K || a.ldw < a.K || (!relq && a.ldo < a.N))
     return SVIT_ERR_ALIGN;
   if (((uintptr_t)a.A | (uintptr_t)a.W) & 15) return SVIT_ERR_ALIGN;
@@ -410,105 +504,26 @@ extern "C" int svit_gemm_nt(const svit_gemm_args* args, void* stream) {
   if (a.out2 && (a.ldo2 % 4 != 0 || ((uintptr_t)a.out2 & 15))) return SVIT_ERR_ALIGN;
   if ((a.epilogue == SVIT_EPI_RESID || a.epilogue == SVIT_EPI_DGELU) && !a.aux) return SVIT_ERR_ARG;
   if (a.epilogue == SVIT_EPI_RESID && a.row_scale && a.rows_per_sample <= 0) return SVIT_ERR_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  // Tile choice (measured on MI355X, tools/bench_kernels.py ntstages): 128x192 blocks (2x2 waves
-  // of 64x96) win whenever they still give >= 1 tile per CU; otherwise, and for N = 96 (mod
-  // 192), 128x96 blocks (4 waves of 32x96) double the number of workgroups.  A 256x192 / 8-wave
-  // tile (fewer LDS-fill bytes per flop) was measured too and never won.  At M = 13064 every
-  // variant lands within 10 % of the others: the bound is the per-CU LDS fill rate (~40 GB/s
-  // per CU, ~10 TB/s chip-wide for the mix of L2 and Infinity-Cache hits), not the pipeline
-  // depth, the fragment-read scheduling or the tile shape.  Also measured and rejected: a
-  // persistent form (a workgroup walks several tiles and issues the next tile's first LDS-DMA from
-  // inside the epilogue of the current one; commit "experiment: persistent NT GEMM", profiles/
-  // r02_nt_persistent_tiles.txt): -10..-17 % on the many-tile K = 384 shapes of the 56x56 stage,
-  // +5..10 % wherever the epilogue writes two outputs or fp32 rows -- the next tile's first
-  // s_waitcnt vmcnt(0) also waits for this tile's stores, which a finishing workgroup never does.
-  // Net zero over the step; not kept.
-  // register-staged form (global_load_dwordx4 -> VGPR -> ds_write_b128, K-step 64, loads a whole
-  // K-step ahead; commit "experiment: register-staged NT GEMM variant", profiles/
-  // r02_nt_tile_sweep.txt column REG): 5-10 % slower than LDS-DMA on every shape -- the bound is
-  // the CU's vector-memory path itself (SQ counters, profiles/r02_nt_pmc_13064x384x1536.txt: waves
-  // spend 51 % of their cycles stalled at instruction issue with the MFMA pipe 28 % busy; ~35
-  // cycles per 1-KiB load instruction per CU = 29 B/clk/CU = 56 GB/s/CU), not how the bytes reach
-  // LDS.  Also measured and rejected: a row-stationary form for K <= 384 (8-wave workgroups, A rows held in registers as MFMA
-  // fragments, only W streamed through a 4-deep LDS ring: 4x fewer fill bytes per flop) --
-  // 0.6-0.9x the speed of these tiles on every shape of the model: one barrier-locked workgroup
-  // per CU leaves nothing to overlap its epilogues and barriers with.
-  // force_cfg: 0 / 2 / 4 = v2 tiles, 5 / 6 / 7 = ring tiles, 8 = the v2 heuristic (no ring), -1 = heuristic
-  const int force_raw = svit_knob(SVIT_K_NT_CFG), force_stages = svit_knob(SVIT_K_NT_STAGES);
-  const bool no_ring = force_raw == 8 || svit_knob(SVIT_K_NT_BK) != 0;
-  const int force_cfg = force_raw == 8 ? -1 : force_raw;
-  // Ring kernels (loader waves + MFMA waves, K-steps of 64; tools/bench_kernels.py ntring, profiles/
-  // r03_nt_ring.txt): see ring_choice().
-  if (a.K % 64 == 0 && !relq && ((force_cfg < 0 && !no_ring) || (force_cfg >= 5 && force_cfg <= 7))) {
-    int cfg = force_cfg, rs = force_stages;
-    if (cfg < 0) ring_choice(a, &cfg, &rs);
-    if (cfg >= 5) {
-      if (!rs) rs = 3;
-#define SVIT_RING_PICK(RB, NB, WM, WN)                                         \
-  do {                                                                         \
-    if (rs == 2) return launch_ring<RB, NB, WM, WN, 4, 2>(a, st);              \
-    if (rs == 3) return launch_ring<RB, NB, WM, WN, 4, 3>(a, st);              \
-    return launch_ring<RB, NB, WM, WN, 4, 4>(a, st);                           \
-  } while (0)
-      if (cfg == 5) SVIT_RING_PICK(2, 3, 2, 2);
-      if (cfg == 6) SVIT_RING_PICK(1, 3, 4, 1);
-      SVIT_RING_PICK(2, 2, 2, 2);
-#undef SVIT_RING_PICK
-    }
-  }
-  bool big = a.N % 192 == 0 && (long)((a.M + 127) / 128) * (a.N / 192) >= 256;
-  if (force_cfg == 0 && a.N % 192 == 0) big = true;
-  if (force_cfg == 2) big = false;
-  // pipeline depth (measured, tools/bench_kernels.py ntstages): short K loops prefer 2 stages
-  // (less LDS -> more resident workgroups), K >= 2048 wants the 4-deep prefetch
-  const int stages = force_stages ? force_stages : (a.K >= 2048 ? 4 : 2);
-  // 128x128 blocks (2x2 waves of 64x64): measured ~10 % faster than 128x192 for the wide, short-K
-  // GEMMs of the 14x14 stage (M = 13064, N = 1152 / 1536, K = 384: fc1, fc2-dgrad, qkv)
-  bool sq = a.N % 128 == 0 && a.N >= 1024 && a.K <= 512 &&
-            (long)((a.M + 127) / 128) * (a.N / 128) <= 2048;
-  if (force_cfg == 4) sq = a.N % 128 == 0;
-  else if (force_cfg >= 0) sq = false;
-  // K-step of 64 (whole 128-B lines per tile row; half as many barriers): measured 5-14 % faster
-  // for the narrow-output, long-K GEMMs (fc2, proj, qkv dgrad: N <= 768, K >= 384) as 128x96
-  // blocks at depth 2, and slower elsewhere -- the 2x LDS per stage costs a resident workgroup
-  // (tools/bench_kernels.py ntstages, profiles/r02_nt_tile_sweep.txt)
-  const int force_bk = svit_knob(SVIT_K_NT_BK);
-  bool bk64 = a.K % 64 == 0 && a.N <= 768 && a.K >= 384;
-  if (force_bk) bk64 = force_bk == 64 && a.K % 64 == 0;
-  if (bk64 && force_cfg < 0 && !force_stages) return launch_v2<1, 3, 4, 1, 2, 64>(a, st);
-#define SVIT_NT_PICK(RB, NB, WM, WN)                                           \
-  do {                                                                         \
-    if (bk64) {                                                                \
-      if (stages == 2) return launch_v2<RB, NB, WM, WN, 2, 64>(a, st);         \
-      if (stages == 3) return launch_v2<RB, NB, WM, WN, 3, 64>(a, st);         \
-      return launch_v2<RB, NB, WM, WN, 4, 64>(a, st);                          \
-    }                                                                          \
-    if (stages == 2) return launch_v2<RB, NB, WM, WN, 2, 32>(a, st);           \
-    if (stages == 3) return launch_v2<RB, NB, WM, WN, 3, 32>(a, st);           \
-    return launch_v2<RB, NB, WM, WN, 4, 32>(a, st);                            \
-  } while (0)
-  // round 4: ONE-ROUND tiles for the wide short-K GEMMs of the 14x14 stage.  At M = 13064 the 128-row tiles above put
-  // 824 (128x192) or 1236 (128x128) workgroups on 512-768 slots: a second, part-filled round in which the chip mostly
-  // stores.  160x256 (1 x 4 waves of 160x64) covers 13064 x 1536 with 82 x 6 = 492 workgroups, 192x192 (2 x 2 waves of
-  // 96x96) covers 13064 x 1152 with 69 x 6 = 414: every workgroup resident at once (two per CU), more flops per LDS-fill
-  // byte (91 / 96 against 77 / 64).  force_cfg 9 / 10 force them; heuristic: only where the grid is one
-  // round and the 128-row grid is not.
-  {
-    constexpr int one_round = 1;
-    const long t160 = a.N % 256 == 0 ? (long)((a.M + 159) / 160) * (a.N / 256) : 0;
-    const long t192 = a.N % 192 == 0 ? (long)((a.M + 191) / 192) * (a.N / 192) : 0;
-    const long t128 = (long)((a.M + 127) / 128) * ((a.N + 191) / 192);
-    const bool auto_ok = force_cfg < 0 && one_round && !force_stages && !force_bk && a.K <= 512 && t128 > 512;
-    if (force_cfg == 9 || (auto_ok && t160 > 256 && t160 <= 512)) {
-      if (a.N % 256 == 0) return launch_v2<5, 2, 1, 4, 2, 32>(a, st);
-    }
-    if (force_cfg == 10 || (auto_ok && t192 > 256 && t192 <= 512)) {
-      if (a.N % 192 == 0) return launch_v2<3, 3, 2, 2, 2, 32>(a, st);
-    }
-  }
-  if (sq) SVIT_NT_PICK(2, 2, 2, 2);
-  if (big) SVIT_NT_PICK(2, 3, 2, 2);
-  SVIT_NT_PICK(1, 3, 4, 1);
-#undef SVIT_NT_PICK
+
+  const NtChoice c = nt_choose(a.M, a.N, a.K, a.epilogue, nt_knobs());
+  NtForm* f = nt_form_of(c, a.epilogue);
+  if (!f) return SVIT_ERR_ARG;
+  for (int e = 0; e < 6; ++e)       // the form's kernels for every epilogue, on its first launch per device
+    if (f->kernel[e])
+      if (int rc = svit_max_lds_once(f->once[e], (const void*)f->kernel[e], c.lds)) return rc;
+  hipLaunchKernelGGL(f->kernel[a.epilogue], dim3(c.gx, c.gy), dim3(c.block), c.lds, (hipStream_t)stream, a);
+  SVIT_LAUNCH_CHECK();
+  return SVIT_OK;
+}
+
+// Host-only plan query (include/svit_hip.h, diagnostics): nt_choose's answer as integers.
+extern "C" int svit_debug_gemm_nt_plan(int M, int N, int K, int epilogue, int32_t* out, int n_out) {
+  if (!out || n_out < 13) return SVIT_ERR_ARG;
+  if (int rc = nt_check_shape(M, N, K)) return rc;
+  const NtChoice c = nt_choose(M, N, K, epilogue, nt_knobs());
+  if (!nt_form_of(c, epilogue)) return SVIT_ERR_ARG;
+  static_assert(sizeof c.p == 8 * sizeof(int32_t), "layout");
+  memcpy(out, &c.p, sizeof c.p);       // family, RB, NB, WAVES_M, WAVES_N, loader waves, stages, K-step
+  out[8] = (int32_t)c.gx, out[9] = (int32_t)c.gy, out[10] = (int32_t)c.block, out[11] = (int32_t)c.lds, out[12] = c.rule;
+  return 13;
 }

@@ -95,6 +95,24 @@ def gemm_nt(a, w, bias=None, epilogue=hip.EPI_BF16, out=None, out2=None, aux=Non
     return (out, out2) if epilogue == hip.EPI_GELU else out
 
 
+NT_FAMILIES = ("v2", "ring")
+NT_RULES = ("forced", "ring_few_long_tiles", "ring_long_k_narrow", "bk64_narrow_long_k", "one_round_160x256",
+            "one_round_192x192", "square_128x128", "big_128x192", "default_128x96")
+_NT_PLAN_FIELDS = ("RB", "NB", "WM", "WN", "NL", "stages", "BK", "gx", "gy", "block", "lds")
+
+
+def gemm_nt_plan(M, N, K, epilogue=hip.EPI_BF16):
+    """Which kernel svit_gemm_nt would launch for this shape and epilogue under the current knobs, and how
+    (svit_debug_gemm_nt_plan: the launch path's own chooser; launches nothing, needs no device) -> dict of family, the
+    template parameters RB NB WM WN NL stages BK, grid gx gy, block, dynamic LDS bytes, and the rule that decided."""
+    out = (C.c_int32 * 13)()
+    n = hip.load().svit_debug_gemm_nt_plan(M, N, K, epilogue, out, 13)
+    hip.check(min(n, 0), "svit_debug_gemm_nt_plan")
+    plan = dict(zip(_NT_PLAN_FIELDS, out[1:12]))
+    plan.update(family=NT_FAMILIES[out[0]], rule=NT_RULES[out[12]])
+    return plan
+
+
 def gemm_tn(a, b, dw, splits=0, dbias=None):
     """dw[N,K] (f32) += a[M,N]^T @ b[M,K].  a / b may be column slices (row-strided views)."""
     _chk_rows(a, b)

@@ -205,9 +205,9 @@ SMALL_LIST = [dict(epi="f32"), dict(epi="bf16")]
 # kernel forms: name -> (cfg, stages, K-step; the svit_debug_set knobs 1, 0, 2), the N it accepts as that form (a
 # forced tile that does not divide N silently becomes another tile) and whether it needs K % 64 == 0 (so does a
 # ring kernel and a forced K-step of 64: otherwise the entry point runs another kernel); rb = 32-row blocks per wave
-# of the tile (at MAIN_SHAPE for the heuristic, which takes the 128 x 96 K-step-64 tile there).  No export tells
-# which kernel ran: that a form's knobs select the kernel named here rests on reading svit_gemm_nt's dispatch
-# (gemm_nt.hip, from `force_raw` to the last SVIT_NT_PICK) against these preconditions.
+# of the tile (at MAIN_SHAPE for the heuristic, which takes the 128 x 96 K-step-64 tile there).  That a form's
+# knobs select the kernel named here, at every shape form_shapes gives it, is checked: tests/test_gemm_nt_plan_cpu.py
+# asks svit_debug_gemm_nt_plan -- the chooser the launch itself calls -- for family, tile, stages and K-step.
 _RB = {0: 2, 2: 1, 4: 2, 5: 2, 6: 1, 7: 2, 9: 5, 10: 3}
 FORMS = {"heuristic": dict(cfg=-1, stages=0, bk=0, n_small=96, k64=False)}
 for _cfg, _n in ((0, 192), (2, 96), (4, 384)):

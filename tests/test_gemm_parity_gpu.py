@@ -25,10 +25,10 @@ the rows outside a remap window must come back untouched.
 
 Each test prints one line per (form, epilogue, stride path, output): the worst metric / bar of the launch.
 
-No export tells which kernel a launch ran.  That the knobs of a form select the kernel it is named after -- and not,
-silently, another tile because N or K does not fit -- rests on reading svit_gemm_nt's dispatch (gemm_nt.hip, from
-`force_raw` to the last SVIT_NT_PICK) against the N and K preconditions kept in gemm_reference.FORMS, which
-tests/test_gemm_reference_cpu.py asserts of every shape a form is given.
+That the knobs of a form select the kernel it is named after -- and not, silently, another tile because N or K does
+not fit -- is checked on the CPU: tests/test_gemm_nt_plan_cpu.py asks svit_debug_gemm_nt_plan (the chooser the launch
+itself calls) at every shape a form is given; tests/test_gemm_reference_cpu.py asserts the N and K preconditions kept
+in gemm_reference.FORMS.
 """
 import ctypes as C
 

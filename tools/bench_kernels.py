@@ -234,12 +234,18 @@ if __name__ == "__main__" and len(sys.argv) > 1 and sys.argv[1] == "tnsplit":
 
 
 
+def nt_tag(M, N, K, epi=hip.EPI_BF16):
+    """the kernel svit_gemm_nt runs for this shape under the knobs as they are set now (ops.gemm_nt_plan)"""
+    p = ops.gemm_nt_plan(M, N, K, epi)
+    return "%s %dx%d s%d k%d [%s]" % (p["family"], 32 * p["RB"] * p["WM"], 32 * p["NB"] * p["WN"], p["stages"], p["BK"], p["rule"])
+
+
 def bench_nt_stages():
-    """NT GEMM: pipeline depth x tile config sweep (svit_debug_set knobs)."""
+    """NT GEMM: pipeline depth x tile config sweep (svit_debug_set knobs); each timing beside the kernel that ran."""
     import ctypes as C
     lib = hip.load()
     lib.svit_debug_set.restype, lib.svit_debug_set.argtypes = C.c_int32, [C.c_int32, C.c_int32]
-    print("== gemm_nt: us for (stages, cfg) ==")
+    print("== gemm_nt: us per forced (cfg, stages, K-step) -- family tile stages K-step [rule]: us ==")
     shapes = [(13064, 1152, 384), (13064, 1536, 384), (13064, 384, 1536), (13064, 384, 384), (50696, 192, 768),
               (13064, 384, 1152), (3656, 768, 3072), (3656, 3072, 768), (3656, 2304, 768),
               (50696, 576, 192), (50696, 192, 576), (201224, 288, 96), (201224, 96, 384)]
@@ -261,11 +267,11 @@ def bench_nt_stages():
                     lib.svit_debug_set(1, cfg)
                     lib.svit_debug_set(2, bk)
                     us = timeit(lambda: ops.gemm_nt(a, w, bias, hip.EPI_BF16, out=out), iters=10)
-                    res.append("c%ds%dk%d:%.1f" % (cfg, st, bk, us))
+                    res.append("%s: %.1f" % (nt_tag(M, N, K), us))
         lib.svit_debug_set(0, 0)
         lib.svit_debug_set(1, -1)
         lib.svit_debug_set(2, 0)
-        print("M=%6d N=%4d K=%4d  " % (M, N, K), " ".join(res))
+        print("M=%6d N=%4d K=%4d  " % (M, N, K), " | ".join(res))
 
 
 if __name__ == "__main__" and len(sys.argv) > 1 and sys.argv[1] == "ntstages":
@@ -279,6 +285,7 @@ def bench_nt_ring():
     lib = hip.load()
     lib.svit_debug_set.restype, lib.svit_debug_set.argtypes = C.c_int32, [C.c_int32, C.c_int32]
     epi_name = sys.argv[2] if len(sys.argv) > 2 else "bf16"
+    epi = {"resid": hip.EPI_RESID, "f32": hip.EPI_F32, "gelu": hip.EPI_GELU, "dgelu": hip.EPI_DGELU}.get(epi_name, hip.EPI_BF16)
     print("== gemm_nt (%s epilogue): us, heuristic vs v2 heuristic vs ring(cfg, stages) vs torch.mm ==" % epi_name)
     shapes = [(13064, 384, 1536), (13064, 384, 1152), (3656, 768, 3072), (50696, 192, 768), (13064, 384, 2304),
               (50696, 192, 1152), (3656, 768, 2304), (50696, 192, 576), (201224, 96, 384), (201224, 96, 576),
@@ -305,21 +312,21 @@ def bench_nt_ring():
             run = lambda: ops.gemm_nt(a, w, bias, hip.EPI_BF16, out=out)
         res = []
         lib.svit_debug_set(0, 0), lib.svit_debug_set(1, -1), lib.svit_debug_set(2, 0)
-        res.append("auto:%.1f" % timeit(run, iters=10))
+        res.append("auto = %s: %.1f" % (nt_tag(M, N, K, epi), timeit(run, iters=10)))
         lib.svit_debug_set(1, 8)        # the pre-ring (v2) heuristic: what "auto" was before
-        res.append("v2:%.1f" % timeit(run, iters=10))
+        res.append("no ring = %s: %.1f" % (nt_tag(M, N, K, epi), timeit(run, iters=10)))
         if K % 64 == 0:
             for cfg in (5, 6, 7):
                 if (cfg == 5 and N % 192) or (cfg == 7 and N % 128):
                     continue
                 for st in (2, 3, 4):
                     lib.svit_debug_set(0, st), lib.svit_debug_set(1, cfg)
-                    res.append("r%ds%d:%.1f" % (cfg, st, timeit(run, iters=10)))
+                    res.append("%s: %.1f" % (nt_tag(M, N, K, epi), timeit(run, iters=10)))
         lib.svit_debug_set(0, 0), lib.svit_debug_set(1, -1), lib.svit_debug_set(2, 0)
         if epi_name == "bf16":
             wt = w.t()
-            res.append("lib:%.1f" % timeit(lambda: torch.mm(a, wt), iters=10))
-        print("M=%6d N=%4d K=%4d  " % (M, N, K), " ".join(res), flush=True)
+            res.append("torch.mm: %.1f" % timeit(lambda: torch.mm(a, wt), iters=10))
+        print("M=%6d N=%4d K=%4d  " % (M, N, K), " | ".join(res), flush=True)
 
 
 if __name__ == "__main__" and len(sys.argv) > 1 and sys.argv[1] == "ntring":

@@ -16,8 +16,15 @@ def last_step(d):
 
 
 def short(n):
+    """family tile stages K-step epilogue of a gemm_nt kernel name (the fields of ops.gemm_nt_plan; the rule that chose it
+    is a matter of the shape, which a trace does not hold)"""
     m = re.search(r"gemm_nt_(v2|ring)_kernel<([^>]*)>", n)
-    return ("%s<%s>" % (m.group(1), m.group(2).replace(" ", ""))) if m else None
+    if not m:
+        return None
+    t = [int(x) for x in m.group(2).split(",")]
+    RB, NB, WM, WN = t[:4]
+    st, epi, bk = (t[4], t[5], t[6]) if m.group(1) == "v2" else (t[5], t[6], 64)
+    return "%s %dx%d s%d k%d e%d" % (m.group(1), 32 * RB * WM, 32 * NB * WN, st, bk, epi)
 
 
 a, b = last_step(sys.argv[1]), last_step(sys.argv[2])
