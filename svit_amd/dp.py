@@ -33,6 +33,21 @@ def rank_role(cfg, local_rank):
                     "multi_images" if is_image else cfg.TRAIN.DATASET)
 
 
+def virtual_roles(cfg, world_size, rank):
+    """The recipe ranks one real rank runs when the cfg.NUM_GPUS-rank step is executed on `world_size` GPUs by
+    accumulated micro-steps (graph.AccumulatedTrainStep): real rank r takes the contiguous block [r*k, (r+1)*k),
+    k = cfg.NUM_GPUS // world_size, in recipe-rank order.  Every entry is `rank_role(cfg, i)` as the full job has it
+    (data_rank / replicas / batch_size / dataset unchanged: a loader shards as in the cfg.NUM_GPUS-rank job)."""
+    world_size, rank, n = int(world_size), int(rank), int(cfg.NUM_GPUS)
+    if world_size < 1 or n % world_size != 0:
+        raise ValueError("virtual_roles: the recipe has cfg.NUM_GPUS = %d ranks, which %d real ranks cannot share "
+                         "evenly -- the world size must divide it" % (n, world_size))
+    if not 0 <= rank < world_size:
+        raise ValueError("virtual_roles: rank %d is outside [0, %d)" % (rank, world_size))
+    k = n // world_size
+    return [rank_role(cfg, i) for i in range(rank * k, (rank + 1) * k)]
+
+
 class DataParallel(nn.Module):
     """Exposes the surface callers of the reference touch on a DDP-wrapped model: `.module`,
     `.device`, `train()/eval()`, `parameters()` (checkpoint.py:140,236; train_net.py:117-118)."""

@@ -39,7 +39,7 @@ from . import hip, ops
 
 class GraphedTrainStep:
     def __init__(self, model, loss_fun, inputs, labels, warmup=2, frames_pass=False, mixup=None, optimizer=None,
-                 meter=None):
+                 meter=None, accumulate=False):
         """model: SViT or its DataParallel wrapper (train mode); loss_fun(preds, extra, labels) ->
         scalar; inputs: the reference's `inputs` list ([video f32 [B,3,T,S,S]]); labels: any
         tensor (or tuple/dict of tensors) `loss_fun` takes -- copied into static buffers.  The static input may be an
@@ -73,7 +73,15 @@ class GraphedTrainStep:
         in device memory, every replay fills the next row of the ring).  `__call__` does the host half of
         `meter.update_stats` (lr -- the optimizer's, or the `lr` argument -- and mb_size = batch x ranks), so the loop
         only calls `meter.log_iter_stats`.  The warm-up runs only fix the meter's columns and the capture run executes
-        nothing: the meter is empty after construction.  None: the same segments and launches as ever."""
+        nothing: the meter is empty after construction.  None: the same segments and launches as ever.
+        accumulate: the step is a MICRO-step of an AccumulatedTrainStep (below) -- the captured body leaves out the bf16
+        weight refresh and the gradient-buffer memset, so a replay ADDS this batch's gradients to what `flat.grad` holds;
+        the owner issues both once per step, and the optimizer tail.  `optimizer=` and `meter=` are refused (the owner
+        holds them).  False: the same segments and launches as ever."""
+        self.accumulate = bool(accumulate)
+        if self.accumulate and (optimizer is not None or meter is not None):
+            raise hip.SvitHipError("GraphedTrainStep(accumulate=True) is a micro-step: the optimizer tail and the meter "
+                                   "belong to the AccumulatedTrainStep that replays it, pass optimizer= / meter= there")
         self.optimizer = optimizer
         self.meter = meter
         if meter is not None and torch.device(meter.device) != inputs[0].device:
@@ -160,8 +168,9 @@ class GraphedTrainStep:
             labels = self.loss_labels
             if torch.is_tensor(x):
                 ops.mixup_clips(x, self.mix_record)      # in place; a U8Clips / AugClips is mixed by its im2col instead
-        eng.refresh_weights()
-        flat.grad.zero_()
+        if not self.accumulate:         # (a micro-step: once per step, by the AccumulatedTrainStep)
+            eng.refresh_weights()
+            flat.grad.zero_()
         ds = core.sample_drop_scales(x.shape[0], x.device, Tx=Tx)      # (+ the head's dropout factors: one launch)
         head_keep, core._head_keep = core._head_keep, None
         with torch.no_grad():
@@ -229,6 +238,8 @@ class GraphedTrainStep:
         core = self.core
         eng = core.engine
         core._attach_grads()                      # .grad views of the flat buffer, host side only
+        if self.accumulate:                       # (what the owner's prologue does in front of every step)
+            eng.refresh_weights()
         dev = self.x.device
         cap = torch.cuda.Stream(device=dev)
         cap.wait_stream(torch.cuda.current_stream(dev))
@@ -286,9 +297,8 @@ class GraphedTrainStep:
         self._side = torch.cuda.Stream(device=dev)
 
     # ------------------------------------------------------------------------------------------
-    def __call__(self, inputs, labels, mix=None, lr=None):
-        """mix: this step's mixup.MixRecord (mixup steps only; drawn from np.random when None, as the reference's
-        MixUp call would).  lr: what the meter logs for this step when the step holds no optimizer."""
+    def check_batch(self, inputs):
+        """refuse a batch the capture does not fit (before anything is enqueued)"""
         x = inputs[0]
         if x.shape != self.x.shape:
             raise hip.SvitHipError("GraphedTrainStep was captured for input %s, got %s"
@@ -300,6 +310,13 @@ class GraphedTrainStep:
                 raise hip.SvitHipError("GraphedTrainStep was captured for a frame buffer %s, got %s: pad the batch to "
                                        "the captured size and pass the videos' extents"
                                        % (tuple(self.x.frames.shape), tuple(getattr(x, "frames", x).shape)))
+
+    def __call__(self, inputs, labels, mix=None, lr=None, exchange=True):
+        """mix: this step's mixup.MixRecord (mixup steps only; drawn from np.random when None, as the reference's
+        MixUp call would).  lr: what the meter logs for this step when the step holds no optimizer.  exchange: False
+        skips the data-parallel launch points of this replay (an AccumulatedTrainStep's micro-steps but the last)."""
+        self.check_batch(inputs)
+        x = inputs[0]
         if x.data_ptr() != self.x.data_ptr():
             self.x.copy_(x, non_blocking=True)
         _tree_copy(self.labels, labels)
@@ -334,7 +351,7 @@ class GraphedTrainStep:
                     val()
             elif kind == "join":
                 main.wait_stream(self._side)
-            else:                       # "ready": this bucket's gradients are final -> all-reduce
+            elif exchange:              # "ready": this bucket's gradients are final -> all-reduce
                 for r in val:
                     self.dp._on_ready(r)
         return self.loss, (self.preds, self.extra)
@@ -352,6 +369,125 @@ class GraphedTrainStep:
     @property
     def n_graphs(self):
         return sum(1 for k, _ in self.segments if k == "graph")
+
+
+class AccumulatedTrainStep:
+    """k recipe ranks ("virtual ranks", dp.virtual_roles) on one GPU: k captured micro-steps add their gradients into
+    the one flat buffer, then ONE exchange and ONE optimizer step -- the cfg.NUM_GPUS-rank step of the recipe on any
+    divisor of that many GPUs.
+
+        video = GraphedTrainStep(model, video_loss, [clips], labels, accumulate=True)
+        image = GraphedTrainStep(model, image_loss, [stills], meta, accumulate=True)
+        step = AccumulatedTrainStep(model, [video] * 7 + [image], optimizer, meter=train_meter)
+        losses = step(batches)            # [(inputs, labels)] * 8 in virtual-rank order
+
+    Per call: the bf16 weight refresh and the gradient-buffer memset once; every micro-step's replay (its own batch,
+    its own DropPath / dropout draws -- the draw counter advances per replay -- its own mix record, frames pass and
+    RandAugment chain); with a DataParallel wrapper the bucketed all-reduce from the launch points of the LAST
+    micro-step only (overlapping its backward; the earlier ones skip theirs), which leaves the mean over the real
+    ranks; then the guarded tail with grad_scale / k: norm, clip coefficient and update are those of the mean over all
+    k x world recipe ranks, and one non-finite micro-step drops the whole step.  Prologue and tail are eager launches
+    (about ten per step, plus a 4-byte loss copy per micro-step), the hot path is the micro-steps' graphs.
+
+    micro_steps: k GraphedTrainStep(accumulate=True) over `model`; entries of equal shape and role may be the SAME
+    object (one capture replayed for several virtual ranks).  meter: a meters.TrainMeter(virtual_ranks=k); each
+    micro-step's loss dict is pushed into its own ring behind its replay (one launch), the host half (lr, mb_size =
+    sum of the micro-batches x real ranks) once per step."""
+
+    def __init__(self, model, micro_steps, optimizer, meter=None):
+        from .optim import GuardedClipAdamW
+        self.wrapper = model
+        self.core = core = model.module if hasattr(model, "module") else model
+        self.micro_steps = list(micro_steps)
+        self.k = k = len(self.micro_steps)
+        if k == 0:
+            raise hip.SvitHipError("AccumulatedTrainStep needs at least one micro-step")
+        if core.engine is None:
+            raise hip.SvitHipError("AccumulatedTrainStep needs a finalized (on-GPU) SViT")
+        if not core.training:
+            raise RuntimeError("AccumulatedTrainStep runs the training step: call model.train() first")
+        if not isinstance(optimizer, GuardedClipAdamW):
+            raise hip.SvitHipError(
+                "AccumulatedTrainStep takes an optim.GuardedClipAdamW, got %s: its tail reads grad_scale = 1/k and every "
+                "other scalar from device memory and drops a step with a non-finite micro-step on the device"
+                % type(optimizer).__name__)
+        if optimizer.flat is not core.flat:
+            raise hip.SvitHipError("AccumulatedTrainStep: the optimizer was built over another model")
+        self.dp = model if hasattr(model, "_on_ready") and (getattr(model, "world_size", 1) > 1 or
+                                                           getattr(model, "force_collectives", False)) else None
+        for i, ms in enumerate(self.micro_steps):
+            if not isinstance(ms, GraphedTrainStep):
+                raise hip.SvitHipError("micro-step %d is a %s, not a GraphedTrainStep" % (i, type(ms).__name__))
+            if ms.core is not core:
+                raise hip.SvitHipError("micro-step %d was built over another model: its gradients land in another flat "
+                                       "buffer" % i)
+            if ms.optimizer is not None:
+                raise hip.SvitHipError("micro-step %d was built with its own optimizer=: it would step the weights "
+                                       "between the micro-steps" % i)
+            if not ms.accumulate:
+                raise hip.SvitHipError("micro-step %d was built without accumulate=True: its replay zeroes the gradient "
+                                       "buffer" % i)
+            if ms.dp is not self.dp:
+                raise hip.SvitHipError("micro-step %d and the AccumulatedTrainStep disagree about the data-parallel "
+                                       "wrapper: build both over the same DataParallel (or both over the bare model)" % i)
+        self.optimizer = optimizer
+        self.meter = meter
+        if meter is not None:
+            if getattr(meter, "virtual_ranks", None) != k:
+                raise hip.SvitHipError("AccumulatedTrainStep(meter=...) needs a TrainMeter(virtual_ranks=%d): video and "
+                                       "image micro-steps log different keys, each into its own ring" % k)
+            if torch.device(meter.device) != self.micro_steps[0].x.device:
+                raise hip.SvitHipError("AccumulatedTrainStep(meter=...): the meter lives on %s, the step on %s"
+                                       % (meter.device, self.micro_steps[0].x.device))
+        # micro-steps that share a capture share its static loss tensor: every replay's loss is copied out (4 bytes)
+        self._loss_buf = torch.zeros(k, dtype=torch.float32, device=self.micro_steps[0].x.device)
+        self.losses = list(self._loss_buf.unbind(0))
+
+    def _check(self, batches):
+        if not self.core.training:
+            raise RuntimeError("AccumulatedTrainStep runs the training step: call model.train() first")
+        if len(batches) != self.k:
+            raise hip.SvitHipError("AccumulatedTrainStep holds %d micro-steps, got %d batches" % (self.k, len(batches)))
+        for i, (ms, b) in enumerate(zip(self.micro_steps, batches)):
+            try:
+                ms.check_batch(b[0])
+            except hip.SvitHipError as e:
+                raise hip.SvitHipError("micro-step %d: %s" % (i, e)) from None
+
+    def __call__(self, batches, mixes=None, lr=None):
+        """batches: k (inputs, labels) in virtual-rank order; mixes: per micro-step its mixup.MixRecord or None (mixup
+        micro-steps draw their own when None).  -> the k loss tensors (0-d views of one static buffer, overwritten by the
+        next call)."""
+        self._check(batches)            # (nothing is enqueued for a step that is refused)
+        core, opt, k = self.core, self.optimizer, self.k
+        with torch.no_grad():
+            core.engine.refresh_weights()
+            core.flat.grad.zero_()
+        if self.meter is not None:
+            world = getattr(self.wrapper, "world_size", 1)
+            self.meter.host_update(opt.param_groups[0]["lr"] if lr is None else lr,
+                                   sum(ms.x.shape[0] for ms in self.micro_steps) * world)
+        for i, (ms, (inputs, labels)) in enumerate(zip(self.micro_steps, batches)):
+            ms(inputs, labels, mix=mixes[i] if mixes is not None else None, exchange=i == k - 1)
+            self.losses[i].copy_(ms.loss)
+            if self.meter is not None:
+                self.meter.push(ms.loss_dict, vrank=i)
+        # the tail of the mean over the k virtual ranks: this step's record carries grad_scale / k, the optimizer keeps its own
+        scale = opt.grad_scale
+        opt.grad_scale = scale * (1.0 / k)
+        try:
+            opt.upload()
+        finally:
+            opt.grad_scale = scale
+        with torch.no_grad():
+            opt.enqueue()
+        return self.losses
+
+    step = __call__
+
+    @property
+    def x(self):
+        return self.micro_steps[0].x
 
 
 def _tree_map(fn, obj):

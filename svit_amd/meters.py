@@ -136,6 +136,7 @@ class _DeviceMeter:
     """What TrainMeter and ValMeter share: the ring, the push, the one read per period, the data-parallel gather."""
     topk = False
     nan_key = None
+    _label = ""                        # (a virtual rank's ring names itself in the NaN message)
 
     def __init__(self, cfg, device=None, force_collectives=False):
         if device is None:
@@ -241,45 +242,63 @@ class _DeviceMeter:
             return False
         return dist.get_world_size() > 1 or self.force_collectives
 
-    def _drain(self):
+    def _on_device(self):
+        return self.device.type == "cuda" and "nccl" in str(dist.get_backend())
+
+    def _payload(self, kmax):
+        """what a rank sends at the period: state | the batch sizes of the rows (host knowledge the other ranks lack) |
+        ring padded to kmax columns (host copies under gloo: the one synchronisation)"""
+        w, k = self.ring.shape
+        ns = [int(h[-1]) for h in self._host] if self.topk else []
+        src = self.buf if self._on_device() else self.buf.cpu()
+        payload = torch.zeros(4 + w + w * kmax, dtype=torch.int32, device=src.device)
+        payload[:4] = src[:4]
+        if ns:
+            rows = [(self._read + i) % w for i in range(min(len(ns), w))]
+            size = torch.zeros(w, dtype=torch.int32)
+            size[rows] = torch.tensor(ns[:w], dtype=torch.int32)
+            payload[4:4 + w] = size.to(src.device, non_blocking=True)
+        payload[4 + w:].view(w, kmax)[:, :k] = src[4:].view(w, k)
+        return payload
+
+    def _all_gather(self, payload):
+        """ONE all_gather -> the ranks' payloads on the host"""
+        world = dist.get_world_size()
+        if self._on_device():
+            out = torch.empty(world * payload.numel(), dtype=torch.int32, device=payload.device)
+            dist.all_gather_into_tensor(out, payload)
+            return list(out.cpu().view(world, -1))                  # the one synchronisation
+        parts = [torch.empty_like(payload) for _ in range(world)]
+        dist.all_gather(parts, payload)
+        return parts
+
+    def _parse(self, names, p, kmax):
+        """a rank's payload -> (its column names, its state + ring as it holds them, the batch sizes of its rows)"""
+        w = self.window
+        kr = len(names) + (2 if self.topk else 0)
+        own = torch.cat((p[:4], p[4 + w:].view(w, kmax)[:, :kr].reshape(-1)))
+        return names, own, p[4:4 + w]
+
+    def _drain(self, ranks=None):
         """-> [(host record, [row of rank 0, row of rank 1, ...])] of the pushes since the last read, in push order; a
-        rank's row is {name: python float} (+ "_hits": (fp32 count, fp32 count), "_n": rows of its batch)"""
+        rank's row is {name: python float} (+ "_hits": (fp32 count, fp32 count), "_n": rows of its batch).  ranks: what
+        `_parse` gave for every rank, when the owner of several rings gathered them together"""
         if self.buf is None:
             return []
         w, k = self.ring.shape
         ns = [int(h[-1]) for h in self._host] if self.topk else []
-        if not self._collective():
+        if ranks is not None:
+            pass
+        elif not self._collective():
             ranks = [(self.names, self.buf.cpu(), None)]            # the one synchronisation of the period
         else:
-            world = dist.get_world_size()
             if self._rank_names is None:                            # once
-                got = [None] * world
+                got = [None] * dist.get_world_size()
                 dist.all_gather_object(got, self.names)
                 self._rank_names = got
             kmax = max(len(n) for n in self._rank_names) + (2 if self.topk else 0)
-            on_device = self.device.type == "cuda" and "nccl" in str(dist.get_backend())
-            src = self.buf if on_device else self.buf.cpu()         # (host copies under gloo: the one synchronisation)
-            # payload: state | the batch sizes of the rows (host knowledge the other ranks lack) | ring padded to kmax
-            payload = torch.zeros(4 + w + w * kmax, dtype=torch.int32, device=src.device)
-            payload[:4] = src[:4]
-            if ns:
-                rows = [(self._read + i) % w for i in range(min(len(ns), w))]
-                size = torch.zeros(w, dtype=torch.int32)
-                size[rows] = torch.tensor(ns[:w], dtype=torch.int32)
-                payload[4:4 + w] = size.to(src.device, non_blocking=True)
-            payload[4 + w:].view(w, kmax)[:, :k] = src[4:].view(w, k)
-            if on_device:
-                out = torch.empty(world * payload.numel(), dtype=torch.int32, device=src.device)
-                dist.all_gather_into_tensor(out, payload)
-                parts = list(out.cpu().view(world, -1))             # the one synchronisation
-            else:
-                parts = [torch.empty_like(payload) for _ in range(world)]
-                dist.all_gather(parts, payload)
-            ranks = []
-            for names, p in zip(self._rank_names, parts):
-                kr = len(names) + (2 if self.topk else 0)
-                own = torch.cat((p[:4], p[4 + w:].view(w, kmax)[:, :kr].reshape(-1)))
-                ranks.append((names, own, p[4:4 + w]))
+            parts = self._all_gather(self._payload(kmax))
+            ranks = [self._parse(names, p, kmax) for names, p in zip(self._rank_names, parts)]
         out = None
         for rank, (names, host, sizes) in enumerate(ranks):
             pushes, bad = (int(v) for v in host[:4].view(torch.int64))
@@ -301,7 +320,7 @@ class _DeviceMeter:
                 row = dict(zip(names, vals))
                 if self.nan_key in row:
                     misc.check_nan_losses(row[self.nan_key], extra_msg="first at iteration %d of the epoch%s, %s" % (
-                        self._read + i, "" if len(ranks) == 1 else " (rank %d)" % rank, row))
+                        self._read + i, ("" if len(ranks) == 1 else " (rank %d)" % rank) + self._label, row))
                 if self.topk:
                     row["_hits"] = (vals[len(names)], vals[len(names) + 1])
                     row["_n"] = int(sizes[r]) if sizes is not None else ns[i]
@@ -326,26 +345,108 @@ class _DeviceMeter:
         pass
 
 
-class TrainMeter(_DeviceMeter):
-    """slowfast/utils/meters.py:454-560 with the loss dict left on the device."""
+class _Ring(_DeviceMeter):
+    """the ring of ONE virtual rank of a TrainMeter(virtual_ranks=k): its own column names, buffer and counter"""
     nan_key = "loss"
 
-    def __init__(self, epoch_iters, cfg, device=None, force_collectives=False):
+    def __init__(self, cfg, device, force_collectives, vrank):
+        super().__init__(cfg, device, force_collectives)
+        self._label = " (virtual rank %d)" % vrank
+
+
+class TrainMeter(_DeviceMeter):
+    """slowfast/utils/meters.py:454-560 with the loss dict left on the device.
+
+    virtual_ranks=k (graph.AccumulatedTrainStep, train.accumulate_step): one real rank runs k recipe ranks per
+    iteration, whose key sets differ (video and image ranks) -- the meter then keeps ONE RING PER VIRTUAL RANK, each with
+    its own column names and push counter (`push(scalars, vrank=i)`; `svit_meter_push` as it is), and one host record
+    per iteration.  At the period every ring is read as a plain meter's is (across real ranks: the ONE all_gather
+    carries the k rings), and the rows of an iteration are merged in recipe-rank order -- real rank r, virtual rank i is recipe rank r*k + i --
+    by the same `sum(v) / len(v)` over the recipe ranks that logged the key: what the k x world-rank job logs.  None:
+    the one ring, buffer layout, payload and numbers of a plain meter."""
+    nan_key = "loss"
+
+    def __init__(self, epoch_iters, cfg, device=None, force_collectives=False, virtual_ranks=None):
         super().__init__(cfg, device, force_collectives)
         self.epoch_iters = epoch_iters
         self.multi_loss = MultiLossMeter(cfg.LOG_PERIOD)
         self.MAX_EPOCH = cfg.SOLVER.MAX_EPOCH * epoch_iters
         self.lr = None
         self.num_samples = 0
+        self.virtual_ranks = None if virtual_ranks is None else int(virtual_ranks)
+        self._rings = None
+        if self.virtual_ranks is not None:
+            if self.virtual_ranks < 1:
+                raise ValueError("virtual_ranks must be positive, got %r" % (virtual_ranks,))
+            self._rings = [_Ring(cfg, self.device, force_collectives, i) for i in range(self.virtual_ranks)]
 
     def reset(self):
         self.multi_loss.reset()
         self.lr = None
         self.num_samples = 0
         self._reset_device()
+        for ring in self._rings or ():
+            ring._reset_device()
+
+    # ---- virtual ranks: the device half goes to the rank's ring, the host half to all of them -----------------------
+    def _ring(self, vrank):
+        if self._rings is None:
+            if vrank is not None:
+                raise ValueError("push(vrank=%r) on a TrainMeter built without virtual_ranks" % (vrank,))
+            return None
+        if vrank is None or not 0 <= int(vrank) < len(self._rings):
+            raise ValueError("a TrainMeter(virtual_ranks=%d) takes push(scalars, vrank=i) with i in [0, %d), got %r"
+                             % (len(self._rings), len(self._rings), vrank))
+        return self._rings[int(vrank)]
+
+    def bind(self, scalars, vrank=None):
+        ring = self._ring(vrank)
+        return super().bind(scalars) if ring is None else ring.bind(scalars)
+
+    def push(self, scalars, vrank=None, **kw):
+        ring = self._ring(vrank)
+        return super().push(scalars, **kw) if ring is None else ring.push(scalars)
+
+    def host_update(self, *record):
+        super().host_update(*record)
+        for ring in self._rings or ():
+            ring.host_update(*record)
+
+    def _drain(self):
+        if self._rings is None:
+            return super()._drain()
+        host, self._host = self._host, []
+        rings = self._rings
+        if self._collective() and all(r.buf is not None for r in rings):
+            # the one all_gather of a plain meter carries the k rings, every one padded to the widest of all ranks
+            if self._rank_names is None:                            # once: per real rank, the k lists of column names
+                got = [None] * dist.get_world_size()
+                dist.all_gather_object(got, [r.names for r in rings])
+                self._rank_names = got
+            kmax = max(len(n) for names in self._rank_names for n in names)
+            parts = self._all_gather(torch.cat([r._payload(kmax) for r in rings]))
+            per = [ring._drain(ranks=[ring._parse(names[v], p.view(len(rings), -1)[v], kmax)
+                                      for names, p in zip(self._rank_names, parts)])
+                   for v, ring in enumerate(rings)]
+        else:
+            per = [ring._drain() for ring in rings]             # per ring: [(host record, [row of real rank 0, 1, ...])]
+        for i, got in enumerate(per):
+            if len(got) != len(host):
+                raise RuntimeError("virtual rank %d pushed %d iterations since the last read, the host half of "
+                                   "update_stats ran %d times" % (i, len(got), len(host)))
+        out = []
+        for it, h in enumerate(host):
+            by_ring = [got[it][1] for got in per]
+            world = len(by_ring[0])
+            out.append((h, [by_ring[v][r] for r in range(world) for v in range(len(per))]))     # recipe-rank order
+        self.time_diff = self._rings[0].time_diff
+        return out
 
     def update_stats(self, lr, mb_size, dloss=None, is_video=True):
         """dloss: {name: 0-d device tensor}; nothing is read back here"""
+        if self._rings is not None:
+            raise ValueError("a TrainMeter(virtual_ranks=...) is fed by push(scalars, vrank=i) per micro-step and one "
+                             "host_update(lr, mb_size) per iteration")
         if not isinstance(dloss, dict):
             dloss = {"loss": dloss}
         self.push(dloss)

@@ -12,7 +12,7 @@ import torch
 import torch.distributed as dist
 
 from . import losses, optim
-from .graph import GraphedTrainStep
+from .graph import AccumulatedTrainStep, GraphedTrainStep
 
 
 def _min_length(n):
@@ -29,11 +29,96 @@ def _lr_value(lr):
     return lr["lr"] if isinstance(lr, dict) else lr
 
 
+def accumulate_step(model, loss_funs, batches, optimizer, meter=None, lr=None):
+    """The eager twin of graph.AccumulatedTrainStep: k recipe ranks (dp.virtual_roles) one after another on this GPU,
+    ONE optimizer step.  `zero_grad` once, then per micro-step i the eager forward of batches[i] = (inputs, labels),
+    loss_funs[i](preds, extra, labels) (a scalar, or a dict whose "loss" entry is differentiated) and its backward --
+    every gradient producer ADDS into the flat buffer, nothing is zeroed in between and the weights do not move -- with
+    a DataParallel wrapper the exchange from the last micro-step's backward only, then `optimizer.step()` with
+    grad_scale / k: the step of the mean over the k (x world) recipe ranks.  meter: a TrainMeter(virtual_ranks=k).
+    -> the k loss tensors."""
+    k = len(batches)
+    if k == 0 or len(loss_funs) != k:
+        raise ValueError("accumulate_step: %d loss functions for %d batches" % (len(loss_funs), k))
+    if not hasattr(optimizer, "grad_scale"):
+        raise ValueError("accumulate_step needs an optimizer with a grad_scale (optim.FusedClipAdamW / GuardedClipAdamW), "
+                         "got %s" % type(optimizer).__name__)
+    core = model.module if hasattr(model, "module") else model
+    if not core.training:
+        raise RuntimeError("accumulate_step runs the training step: call model.train() first")
+    if meter is not None and getattr(meter, "virtual_ranks", None) != k:
+        raise ValueError("accumulate_step(meter=...) needs a TrainMeter(virtual_ranks=%d)" % k)
+    optimizer.zero_grad()
+    hook, out = core._grad_ready_hook, []
+    try:
+        for i, ((inputs, labels), loss_fun) in enumerate(zip(batches, loss_funs)):
+            core._grad_ready_hook = hook if i == k - 1 else None      # the exchange rides on the last backward only
+            preds, extra = model(inputs, {})
+            got = loss_fun(preds, extra, labels)
+            logged = got if isinstance(got, dict) else {"loss": got}
+            logged["loss"].backward()
+            out.append(logged["loss"].detach())
+            if meter is not None:
+                meter.push(logged, vrank=i)
+    finally:
+        core._grad_ready_hook = hook
+    if meter is not None:
+        world = getattr(model, "world_size", 1)
+        meter.host_update(optimizer.param_groups[0]["lr"] if lr is None else lr,
+                          sum(b[0][0].shape[0] for b in batches) * world)
+    scale = optimizer.grad_scale
+    optimizer.grad_scale = scale * (1.0 / k)
+    try:
+        optimizer.step()
+    finally:
+        optimizer.grad_scale = scale
+    return out
+
+
+def _train_epoch_accumulated(train_loader, step, optimizer, train_meter, cur_epoch, cfg):
+    """train_epoch over an AccumulatedTrainStep: per iteration the loader yields k (inputs, labels, video_idx, meta) in
+    virtual-rank order; a micro-step whose static labels are a dict (an image rank: the HAOG targets) takes `meta`"""
+    if step.meter is not train_meter or step.optimizer is not optimizer:
+        raise ValueError("train_epoch: the AccumulatedTrainStep must be built with the optimizer and meter= the ones "
+                         "passed here (it ends with the optimizer's launches and pushes into the meter)")
+    dev = step.x.device
+
+    def to_dev(t):
+        if isinstance(t, dict):
+            return {k: to_dev(v) for k, v in t.items()}
+        return t.to(dev, non_blocking=True) if torch.is_tensor(t) else t
+    train_meter.iter_tic()
+    data_size = len(train_loader)
+    min_length = _min_length(data_size)
+    for cur_iter, micro in enumerate(train_loader):
+        if cur_iter >= min_length:
+            break
+        if len(micro) != len(step.micro_steps):
+            raise ValueError("train_epoch: the loader yielded %d micro-batches, the step holds %d micro-steps"
+                             % (len(micro), len(step.micro_steps)))
+        batches = [([x.to(dev, non_blocking=True) for x in inputs],
+                    to_dev(meta if isinstance(ms.static_labels, dict) else labels))
+                   for ms, (inputs, labels, _vid_idx, meta) in zip(step.micro_steps, micro)]
+        lr = _lr_value(optim.get_lr_at_epoch(cfg, cur_epoch + float(cur_iter) / data_size))
+        optim.set_lr(optimizer, lr)
+        train_meter.data_toc()
+        step(batches)                                # (host half of update_stats included)
+        train_meter.iter_toc()
+        train_meter.log_iter_stats(cur_epoch, cur_iter)
+        train_meter.iter_tic()
+    stats = train_meter.log_epoch_stats(cur_epoch)
+    train_meter.reset()
+    return stats
+
+
 def train_epoch(train_loader, step_or_model, optimizer, train_meter, cur_epoch, cfg):
     """tools/train_net.py:33-178.  step_or_model: a GraphedTrainStep built with `optimizer=` and `meter=train_meter`
     (the whole iteration is one replay; nothing here touches the device but the input copy) or the model itself (the
     eager step: forward, video_image_loss, backward, optimizer.step(), one meter push).  The loader yields
-    (inputs, labels, video_idx, meta) like the reference's."""
+    (inputs, labels, video_idx, meta) like the reference's.  An AccumulatedTrainStep (k virtual ranks per iteration,
+    graph.py) takes a loader that yields a list of k such tuples in virtual-rank order."""
+    if isinstance(step_or_model, AccumulatedTrainStep):
+        return _train_epoch_accumulated(train_loader, step_or_model, optimizer, train_meter, cur_epoch, cfg)
     graphed = isinstance(step_or_model, GraphedTrainStep)
     if graphed:
         if step_or_model.meter is not train_meter or step_or_model.optimizer is not optimizer:
