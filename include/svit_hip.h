@@ -292,6 +292,41 @@ int svit_randaug_stats_ext(const uint8_t* frames, const void* records, const int
                            int V, int T, int Hs, int Ws, int N, void* stream);
 int svit_randaug_apply_ext(const uint8_t* src, uint8_t* dst, const void* records, const int32_t* extents, int layer,
                            const void* workspace, int V, int T, int Hs, int Ws, int N, void* stream);
+/* THE BATCH FEEDER's device half (svit_amd/feeder.py, csrc/feed.hip): one uploaded slot -> the buffers a captured step reads,
+ * in ONE launch.  The host packs a batch TIGHTLY into a slot -- video v as its own u8 [T,h_v,w_v,3], no padding rows, no
+ * zero fill, the small tables behind the videos -- and uploads it with one copy; this launch writes the padded buffer
+ * `frames` u8 [V,T,Hs,Ws,3] (the layout of the PER-VIDEO EXTENTS above) and copies up to eight segments.
+ *   slot, slot_bytes  the uploaded bytes, DEVICE memory, 16-byte aligned, slot_bytes a positive multiple of 16
+ *   offsets           DEVICE int64 [V] (8-byte aligned): byte offset of video v inside the slot; NULL: v*T*Hs*Ws*3
+ *   extents           DEVICE int32 [V,2] = (h_v, w_v) (4-byte aligned); NULL: every video is Hs x Ws
+ *   frames            DEVICE u8 [V,T,Hs,Ws,3], 16-byte aligned; T*Hs*Ws*3 below 2^31
+ *   fill 0..255, swap_rb (any non-zero value is 1), n_seg 0..8
+ * The frames.  Both tables are read on the device at run time.  Per video (h, w) is the extent clamped into [1,Hs] x [1,Ws]
+ * and n_v = T*h*w*3 (int64).  offsets[v] < 0 or offsets[v] > slot_bytes - n_v: the video is ABSENT and its whole T x Hs x Ws
+ * x 3 block becomes `fill`.  Otherwise frames[v,t,y,x,c] = slot[offsets[v] + ((t*h + y)*w + x)*3 + (swap_rb ? 2-c : c)] for
+ * y < h, x < w, and `fill` elsewhere (swap_rb: a decoder that yields RGB feeds weights trained on the reference's BGR,
+ * slowfast/datasets/utils.py:37).  Every byte of `frames` is written exactly once per launch; an offset may be any byte
+ * address (rows of 33 or 57 bytes, videos of 54), the row pitch Ws*3 need not be a multiple of anything.  NOTHING outside
+ * [slot, slot + slot_bytes) is ever read, whatever the tables hold: the kernel loads aligned dwords that hold at least one
+ * byte of a video lying inside the slot, which is what the alignment rule is for.
+ * The segments.  seg[s], s < n_seg: `bytes` bytes from slot + src_off to dst (records, extents, RandAugment table, labels),
+ * by extra blocks of the same launch.  src_off is a multiple of 16, dst is 4-byte aligned, bytes >= 0 and need not be a
+ * multiple of anything (exactly `bytes` bytes of dst are written), src_off + bytes <= slot_bytes.  A segment must not
+ * overlap `frames`, another segment's dst or the slot.
+ * Checked on the host before the launch: SVIT_ERR_ARG for a null args / slot / frames / segment dst, fill outside 0..255,
+ * n_seg outside 0..8, a segment with negative bytes or src_off or one that leaves the slot; SVIT_ERR_ALIGN for a
+ * misaligned slot / frames / offsets / extents / segment dst, slot_bytes or a src_off not a multiple of 16; SVIT_ERR_SHAPE
+ * for V, T, Hs or Ws below 1, slot_bytes below 16 or T*Hs*Ws*3 of 2^31 or more.  Stream-ordered, no host synchronisation. */
+typedef struct { int64_t src_off; void* dst; int64_t bytes; } svit_feed_seg;
+typedef struct {
+  const uint8_t* slot; int64_t slot_bytes;
+  const int64_t* offsets;
+  const int32_t* extents;
+  uint8_t* frames;
+  int V, T, Hs, Ws, fill, swap_rb, n_seg;
+  svit_feed_seg seg[8];
+} svit_feed_args;
+int svit_feed_unpack(const svit_feed_args* a, void* stream);
 /* cls / object token rows of the block-0 input (video_model_builder.py:326-363). */
 int svit_fill_special_tokens(float* x, const float* cls, const float* objq, const float* pos_t,
                              int B, int N, int L, int Tx, int O, int C, int add_pos, void* stream);

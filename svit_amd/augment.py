@@ -67,7 +67,8 @@ S, clip to [0, 1], cxcywh, rows no larger than 0.05 zeroed).  `draw_still` does 
 One captured step serves every draw: a replay uploads stills, records, tables and extents through `AugClips.copy_` and
 the targets / contact states through the label tree.  The Shear boxes are geometric, not the reference's (randaug.py).
 
-Out of scope: tightly packed storage with per-video offsets, per-frame sizes inside one video, colour jitter
+Out of scope: tightly packed storage with per-video offsets on the device (feeder.py packs tightly for the upload and
+unpacks into this padded layout), per-frame sizes inside one video, colour jitter
 (AUG.COLOR_JITTER, which the reference's loader never reads), DATA.TRAIN_JITTER_MOTION_SHIFT, the dataset class of the
 image ranks (JSON parsing, `match_haog`, JPEG decoding), mixup on image ranks, AUG.RE_COUNT > 1 and bicubic
 resampling.  The reference's frames pass reads the same frames and

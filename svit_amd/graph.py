@@ -449,13 +449,19 @@ class AccumulatedTrainStep:
         if len(batches) != self.k:
             raise hip.SvitHipError("AccumulatedTrainStep holds %d micro-steps, got %d batches" % (self.k, len(batches)))
         for i, (ms, b) in enumerate(zip(self.micro_steps, batches)):
+            if _is_feeder(b):
+                if b.target is not ms.x:
+                    raise hip.SvitHipError("micro-step %d: the feeder was built over another step's static input" % i)
+                continue
             try:
                 ms.check_batch(b[0])
             except hip.SvitHipError as e:
                 raise hip.SvitHipError("micro-step %d: %s" % (i, e)) from None
 
     def __call__(self, batches, mixes=None, lr=None):
-        """batches: k (inputs, labels) in virtual-rank order; mixes: per micro-step its mixup.MixRecord or None (mixup
+        """batches: k (inputs, labels) in virtual-rank order -- an entry may instead be the feeder.ClipFeeder of its
+        micro-step's capture (one feeder may stand at several entries): its `next()` is called immediately before that
+        micro-step's replay and `pump()` once behind the last one; mixes: per micro-step its mixup.MixRecord or None (mixup
         micro-steps draw their own when None).  -> the k loss tensors (0-d views of one static buffer, overwritten by the
         next call)."""
         self._check(batches)            # (nothing is enqueued for a step that is refused)
@@ -467,11 +473,19 @@ class AccumulatedTrainStep:
             world = getattr(self.wrapper, "world_size", 1)
             self.meter.host_update(opt.param_groups[0]["lr"] if lr is None else lr,
                                    sum(ms.x.shape[0] for ms in self.micro_steps) * world)
-        for i, (ms, (inputs, labels)) in enumerate(zip(self.micro_steps, batches)):
+        for i, (ms, b) in enumerate(zip(self.micro_steps, batches)):
+            # a feeder: micro-steps that share a capture share its static buffer, so the batch is unpacked into it
+            # immediately before its own replay
+            inputs, labels = b.next() if _is_feeder(b) else b
             ms(inputs, labels, mix=mixes[i] if mixes is not None else None, exchange=i == k - 1)
             self.losses[i].copy_(ms.loss)
             if self.meter is not None:
                 self.meter.push(ms.loss_dict, vrank=i)
+        fed = []
+        for b in batches:                # the next step's uploads run beside this step's tail
+            if _is_feeder(b) and not any(b is f for f in fed):
+                fed.append(b)
+                b.pump()
         # the tail of the mean over the k virtual ranks: this step's record carries grad_scale / k, the optimizer keeps its own
         scale = opt.grad_scale
         opt.grad_scale = scale * (1.0 / k)
@@ -488,6 +502,11 @@ class AccumulatedTrainStep:
     @property
     def x(self):
         return self.micro_steps[0].x
+
+
+def _is_feeder(batch):
+    from .feeder import ClipFeeder
+    return isinstance(batch, ClipFeeder)
 
 
 def _tree_map(fn, obj):

@@ -119,6 +119,17 @@ class HeadBwdArgs(C.Structure):
                 ("gw_con", vp), ("gb_con", vp), ("ordered", i32)]
 
 
+class FeedSeg(C.Structure):
+    _fields_ = [("src_off", i64), ("dst", vp), ("bytes", i64)]
+
+
+class FeedArgs(C.Structure):
+    """svit_feed_args: one uploaded slot -> the padded frame buffer + up to eight small segments"""
+    _fields_ = [("slot", vp), ("slot_bytes", i64), ("offsets", vp), ("extents", vp), ("frames", vp),
+                ("V", i32), ("T", i32), ("Hs", i32), ("Ws", i32), ("fill", i32), ("swap_rb", i32), ("n_seg", i32),
+                ("seg", FeedSeg * 8)]
+
+
 class StepHost(C.Structure):
     """svit_step_host: the part of the guarded optimiser's step record the host uploads before every step"""
     _fields_ = [("lr", f32 * 2), ("weight_decay", f32 * 2), ("max_norm", f32), ("clip_value", f32),
@@ -169,6 +180,7 @@ _SIGS = {
     "svit_randaug_apply": (i32, [vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, vp]),
     "svit_randaug_stats_ext": (i32, [vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, vp]),
     "svit_randaug_apply_ext": (i32, [vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, vp]),
+    "svit_feed_unpack": (i32, [C.POINTER(FeedArgs), vp]),
     "svit_fill_special_tokens": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
     "svit_special_token_grads": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
     "svit_pool_ln_fwd": (i32, [C.POINTER(PoolArgs), vp]),

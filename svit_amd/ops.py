@@ -443,6 +443,48 @@ def u8_clips_render(clips):
     return out
 
 
+def feed_args(slot, frames, offsets=None, extents=None, fill=0, swap_rb=False, segments=(), slot_bytes=None):
+    """The svit_feed_args of one launch (checked here for what the C side cannot see: devices, dtypes, shapes).
+    slot: contiguous u8 device tensor (its first `slot_bytes` bytes are the slot; default: all of it); frames: u8
+    [V,T,Hs,Ws,3]; offsets int64 [V] / extents int32 [V,2] on the device, or None; segments: up to eight
+    (src_off, dst tensor[, bytes]) -- bytes defaults to the whole dst.  The struct holds raw pointers: keep the tensors."""
+    _chk_dev(slot, frames, offsets, extents)
+    if slot.dtype != torch.uint8 or frames.dtype != torch.uint8 or frames.dim() != 5 or frames.shape[-1] != 3:
+        raise hip.SvitHipError("feed_unpack takes a uint8 slot and uint8 [V,T,Hs,Ws,3] frames, got %s and %s %s"
+                               % (slot.dtype, frames.dtype, tuple(frames.shape)))
+    V, T, Hs, Ws, _ = frames.shape
+    if offsets is not None and (offsets.dtype != torch.int64 or tuple(offsets.shape) != (V,) or offsets.device != frames.device):
+        raise hip.SvitHipError("the offsets must be int64 [%d] on %s" % (V, frames.device))
+    if extents is not None:
+        _chk_extents(extents, frames)
+    a = hip.FeedArgs()
+    a.slot, a.slot_bytes = ptr(slot), slot.numel() if slot_bytes is None else int(slot_bytes)
+    if a.slot_bytes > slot.numel():
+        raise hip.SvitHipError("slot_bytes %d exceeds the slot tensor's %d bytes" % (a.slot_bytes, slot.numel()))
+    a.offsets, a.extents, a.frames = ptr(offsets), ptr(extents), ptr(frames)
+    a.V, a.T, a.Hs, a.Ws, a.fill, a.swap_rb = V, T, Hs, Ws, int(fill), int(bool(swap_rb))
+    if len(segments) > 8:
+        raise hip.SvitHipError("feed_unpack carries at most 8 segments, got %d" % len(segments))
+    a.n_seg = len(segments)
+    for s, sg in enumerate(segments):
+        dst = sg[1]
+        _chk_dev(dst)
+        if dst.device != frames.device:
+            raise hip.SvitHipError("segment %d lives on %s, the frames on %s" % (s, dst.device, frames.device))
+        full = dst.numel() * dst.element_size()
+        nbytes = full if len(sg) < 3 else int(sg[2])
+        if nbytes > full:
+            raise hip.SvitHipError("segment %d: %d bytes into a tensor of %d" % (s, nbytes, full))
+        a.seg[s].src_off, a.seg[s].dst, a.seg[s].bytes = int(sg[0]), ptr(dst), nbytes
+    return a
+
+
+def feed_unpack(args):
+    """svit_feed_unpack on the current stream: one uploaded slot -> the padded frame buffer + the small segments
+    (`feed_args`; svit_amd/feeder.py)."""
+    hip.call("svit_feed_unpack", C.byref(args))
+
+
 def _chk_mix(mix, device):
     """the 32-byte mix record (include/svit_hip.h, svit_mixup_clips): int32 [8] on the device of the data"""
     _chk_dev(mix)

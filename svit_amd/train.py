@@ -111,12 +111,63 @@ def _train_epoch_accumulated(train_loader, step, optimizer, train_meter, cur_epo
     return stats
 
 
-def train_epoch(train_loader, step_or_model, optimizer, train_meter, cur_epoch, cfg):
+def _train_epoch_fed(train_loader, step, optimizer, train_meter, cur_epoch, cfg, feeder):
+    """train_epoch over a GraphedTrainStep and its feeder.ClipFeeder: the loader yields HOST batches
+    (videos, records, labels, video_idx, meta[, randaug]); a step whose static labels are a dict (an image rank) takes
+    `meta`.  One producer thread packs them into the feeder's pinned slots; per iteration `feeder.next()` (upload if not
+    yet under way + one unpack launch into the step's static buffers), the replay, `feeder.pump()` -- batch n + 1
+    uploads while step n runs."""
+    from .feeder import Producer
+    if not isinstance(step, GraphedTrainStep):
+        raise ValueError("train_epoch(feeder=...) needs a GraphedTrainStep: the feeder writes its static buffers")
+    if step.meter is not train_meter or step.optimizer is not optimizer:
+        raise ValueError("train_epoch: the GraphedTrainStep must be built with optimizer= and meter= the ones passed "
+                         "here (its replay ends with the optimizer's launches and holds the meter's push)")
+    if feeder.target is not step.static_inputs[0]:
+        raise ValueError("train_epoch: the feeder was built over another step's static input (ClipFeeder.for_step(step))")
+    train_meter.iter_tic()
+    data_size = len(train_loader)
+    min_length = _min_length(data_size)
+    from_meta = isinstance(step.static_labels, dict)
+
+    def host_batches():
+        for cur_iter, batch in enumerate(train_loader):
+            if cur_iter >= min_length:
+                break
+            videos, records, labels, _vid_idx, meta = batch[:5]
+            yield (videos, records, meta if from_meta else labels) + tuple(batch[5:6])
+    producer = Producer(feeder, host_batches())
+    producer.start()
+    try:
+        for cur_iter in range(min(min_length, data_size)):
+            producer.wait_ready()
+            inputs, labels = feeder.next()
+            lr = _lr_value(optim.get_lr_at_epoch(cfg, cur_epoch + float(cur_iter) / data_size))
+            optim.set_lr(optimizer, lr)
+            train_meter.data_toc()
+            step(inputs, labels)                     # (host half of update_stats included)
+            feeder.pump()
+            train_meter.iter_toc()
+            train_meter.log_iter_stats(cur_epoch, cur_iter)
+            train_meter.iter_tic()
+    finally:
+        producer.stop()
+    stats = train_meter.log_epoch_stats(cur_epoch)
+    train_meter.reset()
+    return stats
+
+
+def train_epoch(train_loader, step_or_model, optimizer, train_meter, cur_epoch, cfg, feeder=None):
     """tools/train_net.py:33-178.  step_or_model: a GraphedTrainStep built with `optimizer=` and `meter=train_meter`
     (the whole iteration is one replay; nothing here touches the device but the input copy) or the model itself (the
     eager step: forward, video_image_loss, backward, optimizer.step(), one meter push).  The loader yields
     (inputs, labels, video_idx, meta) like the reference's.  An AccumulatedTrainStep (k virtual ranks per iteration,
-    graph.py) takes a loader that yields a list of k such tuples in virtual-rank order."""
+    graph.py) takes a loader that yields a list of k such tuples in virtual-rank order.
+    feeder: a feeder.ClipFeeder over the GraphedTrainStep's static AugClips -- the loader then yields host batches
+    (videos, records, labels, video_idx, meta[, randaug]) and uploads overlap the step (`_train_epoch_fed`).  None: the
+    loop below."""
+    if feeder is not None:
+        return _train_epoch_fed(train_loader, step_or_model, optimizer, train_meter, cur_epoch, cfg, feeder)
     if isinstance(step_or_model, AccumulatedTrainStep):
         return _train_epoch_accumulated(train_loader, step_or_model, optimizer, train_meter, cur_epoch, cfg)
     graphed = isinstance(step_or_model, GraphedTrainStep)
