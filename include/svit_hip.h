@@ -654,6 +654,19 @@ typedef struct {
                         chunk in row order (no atomics: bit-reproducible when B*T*O exceeds one 32-row chunk); 0: a block per row chunk */
 } svit_head_bwd_args;
 int svit_head_bwd(const svit_head_bwd_args* g, void* stream);
+/* The head in EVAL mode, one launch (csrc/head_eval.hip; what SViTHead.forward returns when `not self.training`).  Same
+ * argument block; `tokens` is the final norm's output as it lies (row 0 = cls, the last T*O rows = objects: no
+ * concatenation in front), `keep` must be NULL.  Outputs: logits [B,n_cls] holds PROBABILITIES -- act 0: softmax over
+ * the classes, act 1: sigmoid per class (exponentials, sums and divisions in fp64, rounded to fp32 once; every
+ * exponential has an argument <= 0 and every divisor lies in [1, n_cls], so no logit, however large, overflows: a
+ * sigmoid of -800 is 0, not NaN); boxes [B,T,O,5]:
+ * column 0 the SIGMOID of the objectness logit, 1..4 the sigmoid boxes; contact [B,T,2,5]: softmax over the last axis;
+ * xobj [B,T*O,C] (optional, may be NULL): the object rows.  Workgroups [0,B) own one cls row each and run the softmax
+ * in LDS; the others take eight object rows each.  Plain vector stores only; no atomics, so one build gives equal bits
+ * for equal inputs.  Refused before any launch: SVIT_ERR_ARG -- keep != NULL, or NULL tokens / weights / biases /
+ * logits / boxes / contact; SVIT_ERR_SHAPE -- C % 4 != 0, n_cls < 1, n_cls > 1024 (the LDS row), N < 1 + T*O, O < 2,
+ * B or T < 1, act outside {0, 1}; SVIT_ERR_ALIGN -- tokens, a weight matrix or xobj not 16-byte aligned. */
+int svit_head_eval(const svit_head_args* a, int act, void* stream);
 
 /* ------------------------------------------------ image-rank HAOG losses ---- */
 /* boxes_loss_ + contact-state CE of VideoImageLoss._haog_loss (slowfast/models/losses.py:50-93,

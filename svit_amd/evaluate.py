@@ -14,6 +14,11 @@ changes that matter on an MI355X:
 * in test mode the dataset's NUM_ENSEMBLE_VIEWS temporal views are identical frames (segment
   midpoints, ssv2.py:225-230): only the NUM_SPATIAL_CROPS unique views are computed and each is
   folded NUM_ENSEMBLE_VIEWS times (`unique_views`), 10x less forward work for the same scores.
+
+On the uint8 route the views of a video are records over ONE uploaded copy of its frames (`test_views` ->
+`augment.AugClips`), an iteration is one replay of a `graph.GraphedEvalStep` with the fold inside the graph, and host
+batches arrive through `feeder.ClipFeeder` (`perform_test(..., feeder=)`, `run_eval_step`).  `head_eval_host` restates
+the step's one new kernel, `svit_head_eval`, in NumPy.
 """
 import math
 
@@ -150,15 +155,167 @@ def spatial_crops(video, size, num_crops=3):
     return out.flatten(0, 1)
 
 
+def test_views(sampler, sizes, first_video, num_crops):
+    """The test-time views of a batch of videos as augmentation records over their shared uint8 frames (host only).
+    sampler: `augment.build_sampler(cfg, "test")`; sizes: (h, w) of video v of the batch; first_video: the dataset index
+    of video 0.  -> (records, clip_ids): video-major, for video v the records `sampler.draw(h, w, video=v,
+    spatial_idx=s)` for s in range(num_crops), or the centre [1] when num_crops == 1 (ssv2.py:279-285; `spatial_crops`),
+    and clip_ids int64 = (first_video + v) * num_crops + j."""
+    idx = [1] if num_crops == 1 else list(range(num_crops))
+    records, ids = [], []
+    for v, (h, w) in enumerate(sizes):
+        for j, s in enumerate(idx):
+            records.append(sampler.draw(int(h), int(w), video=v, spatial_idx=s))
+            ids.append((int(first_video) + v) * num_crops + j)
+    return records, torch.tensor(ids, dtype=torch.int64)
+
+
+test_views.__test__ = False          # (a library function: pytest must not collect it where a test imports it)
+
+
+def head_eval_host(tokens, params, T, O, act, dtype=None):
+    """NumPy restatement of svit_head_eval (include/svit_hip.h), float64 unless `dtype` says otherwise: the kernel's
+    yardstick.  tokens [B,N,C] (row 0 = cls, the last T*O rows = objects); params = ((w, b) of the class projection, the
+    box MLP, the objectness Linear, the contact MLP); act 0 softmax, 1 sigmoid.  -> (probabilities [B,n_cls], boxes
+    [B,T,O,5], contact [B,T,2,5], obj_desc [B,T,O,C])."""
+    import numpy as np
+    dt = np.float64 if dtype is None else dtype
+
+    def arr(t):
+        return np.asarray(t.detach().cpu().numpy() if torch.is_tensor(t) else t).astype(dt)
+
+    def sigmoid(z):
+        with np.errstate(over="ignore"):
+            return (1 / (1 + np.exp(-z))).astype(dt)
+
+    def softmax(z):
+        e = np.exp(z - z.max(axis=-1, keepdims=True))
+        return (e / e.sum(axis=-1, keepdims=True)).astype(dt)
+    if act not in (0, 1):
+        raise ValueError("act is 0 (softmax) or 1 (sigmoid)")
+    x = arr(tokens)
+    (wp, bp), (wb, bb), (we, be), (wc, bc) = [(arr(w), arr(b)) for w, b in params]
+    B, N, C_ = x.shape
+    if N < 1 + T * O:
+        raise ValueError("N = %d rows cannot hold a cls row and %d x %d objects" % (N, T, O))
+    z = x[:, 0] @ wp.T + bp
+    probs = softmax(z) if act == 0 else sigmoid(z)
+    xobj = x[:, N - T * O:].reshape(B, T, O, C_)
+    boxes = np.concatenate((sigmoid(xobj @ we.T + be), sigmoid(xobj @ wb.T + bb)), axis=-1)
+    contact = softmax(xobj[:, :, :2] @ wc.T + bc)
+    return probs, boxes, contact, xobj
+
+
+def _to_device(tree, dev):
+    if isinstance(tree, dict):
+        return {k: _to_device(v, dev) for k, v in tree.items()}
+    return tree.to(dev, non_blocking=True) if torch.is_tensor(tree) else tree
+
+
+def run_eval_step(loader, step, feeder=None, after=None):
+    """What `perform_test` and `train.eval_epoch` share when they drive a graph.GraphedEvalStep: `step.refresh()` once,
+    then every batch of `loader` through the replay (a full batch) or `step.eager` (a batch with fewer clips: the short
+    last batch of an epoch), `after(cur_iter)` behind each.
+    feeder None: the loader yields device-side (inputs, labels, ...) -- `labels` whatever the step's static labels hold.
+    feeder (a feeder.ClipFeeder over the step's static AugClips): the loader yields HOST batches (videos, records,
+    labels, ...); one feeder.Producer thread packs the full ones into the pinned slots and the loop is `next()` /
+    replay / `pump()` as train._train_epoch_fed's.  A batch with fewer than V videos is not fed: it is reached in order,
+    i.e. with every earlier batch consumed, and goes through `pack_videos(videos, Hs, Ws)`, a temporary AugClips with
+    extents and `step.eager`."""
+    import queue
+    from .augment import AugClips, pack_videos
+    from .graph import GraphedEvalStep
+    if not isinstance(step, GraphedEvalStep):
+        raise ValueError("expected a graph.GraphedEvalStep, got %s" % type(step).__name__)
+    step.refresh()
+    x = step.static_inputs[0]
+    dev = x.device
+    if feeder is None:
+        for cur_iter, batch in enumerate(loader):
+            inputs, labels = batch[0], batch[1]
+            if inputs[0].shape[0] < x.shape[0]:
+                step.eager(inputs, labels)
+            else:
+                step(inputs, labels)
+            if after is not None:
+                after(cur_iter)
+        return
+    from .feeder import Producer
+    if feeder.target is not x:
+        raise ValueError("the feeder was built over another step's static input (ClipFeeder.for_step(step))")
+    if not isinstance(x, AugClips) or x.raw is not None:
+        raise ValueError("a fed evaluation step runs over an AugClips without RandAugment")
+    V, _, Hs, Ws, _ = x.frames.shape
+    order = queue.Queue()           # per batch, in loader order: None (fed) or the short batch itself; _END last
+
+    def host_batches():
+        try:
+            for batch in loader:
+                videos, records, labels = batch[:3]
+                if len(videos) == V:
+                    order.put(None)
+                    yield videos, records, labels
+                else:
+                    order.put((videos, records, labels))
+        finally:                    # also when the loader raises: the loop ends and `producer.stop()` re-raises it
+            order.put(_END)
+    producer = Producer(feeder, host_batches())
+    producer.start()
+    try:
+        cur_iter = 0
+        while True:
+            item = order.get()
+            if item is _END:
+                break
+            if item is None:
+                producer.wait_ready()       # (re-raises what `put` raised for this batch)
+                inputs, labels = feeder.next()
+                step(inputs, labels)
+                feeder.pump()
+            else:
+                videos, records, labels = item
+                frames, ext = pack_videos(list(videos), Hs, Ws)
+                clips = AugClips(frames.to(dev, non_blocking=True), x.size, records, x.mean, x.std, lut_f32=x.lut_f32,
+                                 extents=ext)
+                step.eager([clips], _to_device(labels, dev))
+            if after is not None:
+                after(cur_iter)
+            cur_iter += 1
+    finally:
+        producer.stop()
+
+
+_END = object()
+
+
 @torch.no_grad()
-def perform_test(test_loader, model, test_meter, cfg, dedupe=True, force_collectives=False):
+def perform_test(test_loader, model, test_meter, cfg, dedupe=True, force_collectives=False, feeder=None):
     """tools/test_net.py:25-170, classification branch.  `test_loader` yields
     (inputs, labels, video_idx, meta) like the reference's loader; with `dedupe` it is expected to
     yield only the unique views (clip index = video * NUM_SPATIAL_CROPS + crop) and the meter is
-    built with num_clips = NUM_SPATIAL_CROPS."""
-    model.eval()
+    built with num_clips = NUM_SPATIAL_CROPS.
+    model: the model, or a graph.GraphedEvalStep built with `test_meter=` this meter and `repeat=` the fold count used
+    here -- the loader then yields device-side (inputs, {"labels", "clip_ids"}, ...) and an iteration is one replay
+    (`run_eval_step`); with `feeder` (a feeder.ClipFeeder over the step) it yields HOST batches (videos, records,
+    {"labels", "clip_ids"}, video_idx, meta) and uploads overlap the step."""
     repeat = unique_views(cfg)[1] if dedupe else 1
     ks = (1, 5) if cfg.MODEL.NUM_CLASSES > 5 else (1, 1)
+    from .graph import GraphedEvalStep
+    if isinstance(model, GraphedEvalStep):
+        step = model
+        if step.test_meter is not test_meter:
+            raise ValueError("perform_test: the GraphedEvalStep must be built with test_meter= the meter passed here (its "
+                             "replay holds the ensemble's fold)")
+        if step.repeat != repeat:
+            raise ValueError("perform_test folds every view %d times, the GraphedEvalStep was built with repeat=%d"
+                             % (repeat, step.repeat))
+        run_eval_step(test_loader, step, feeder)
+        test_meter.all_reduce(force=force_collectives)
+        test_meter.finalize_metrics(ks=ks)
+        return test_meter
+    if feeder is not None:
+        raise ValueError("perform_test(feeder=...) needs a GraphedEvalStep: the feeder writes its static buffers")
+    model.eval()
     for cur_iter, (inputs, labels, video_idx, meta) in enumerate(test_loader):
         preds = model(inputs, meta)
         if isinstance(preds, tuple):

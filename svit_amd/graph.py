@@ -28,6 +28,10 @@ than serial on ROCm 7.2; (b) data parallel: after the segment that finalises a g
 the wrapper's `_on_ready` hook launches that bucket's all-reduce on RCCL's stream, overlapping
 the next segment exactly like in the eager path (svit_amd/dp.py) -- no collective lives inside a
 graph.
+
+`GraphedEvalStep` (below) is the evaluation counterpart: one iteration of `train.eval_epoch` or `evaluate.perform_test` -- forward,
+the eval-mode head as one launch, the frames pass, the meter's push or the ensemble's fold -- as ONE graph, a single chain on
+one stream (nothing leaves the main chain without a backward).
 """
 import gc
 import warnings
@@ -502,6 +506,187 @@ class AccumulatedTrainStep:
     @property
     def x(self):
         return self.micro_steps[0].x
+
+
+class GraphedEvalStep:
+    """HIP-graph replay of one evaluation iteration (tools/train_net.py:181-368 per `TRAIN.EVAL_PERIOD`, tools/test_net.py:
+    25-170 at the end): backbone forward, the eval-mode head as one launch (`SViT.head_eval`, csrc/head_eval.hip), the
+    frames pass, the validation losses + meter push or the test ensemble's fold -- ONE graph, a single chain of kernel
+    nodes on one stream.  The bf16 weight refresh is NOT in the captured body: weights do not move during an
+    evaluation, so `refresh()` issues it eagerly -- the constructor calls it once, `train.eval_epoch` and
+    `evaluate.perform_test` once before their first batch, and a caller that replays the step by hand after the weights
+    changed calls it itself.
+
+        model.eval()
+        step = GraphedEvalStep(model, [clips], {"labels": y, "clip_ids": ids}, test_meter=meter, repeat=10)
+        feeder = ClipFeeder.for_step(step)                  # static_inputs / static_labels: GraphedTrainStep's contract
+        evaluate.perform_test(loader, step, meter, cfg, feeder=feeder)
+
+    model: an SViT or its DataParallel wrapper in eval mode (a model in training mode is refused).  inputs: [AugClips],
+    [U8Clips] or [fp32 tensor], the shapes a replay will see.  labels: int64 [B], or the tree {"labels": int64 [B],
+    "clip_ids": int64 [B]} of a test batch; copied into static buffers (`static_labels`).
+    frames_pass: "u8" (U8Clips / AugClips: `input.FramesView(x, fresh=True)`) or True (fp32) -- with more than one frame
+    the single-frame forward of tools/train_net.py:243-248 runs too and arrives as extra["frames_output"].
+    val_meter (needs cfg): `train.eval_extra_metrics` and the meter's push are part of the body and `__call__` / `eager`
+    do the host half, so the loop only calls `log_iter_stats`.  test_meter: `update_stats(preds, labels, clip_ids,
+    repeat=repeat)` is part of the body; the warm-up runs leave it out, so the meter is empty after construction.
+    The step draws nothing (`sample_drop_scales` is never called) and writes neither weights, gradients nor optimizer
+    state."""
+
+    def __init__(self, model, inputs, labels, *, cfg=None, frames_pass=False, val_meter=None, test_meter=None, repeat=1,
+                 warmup=2):
+        from .augment import AugClips
+        from .input import U8Clips
+        self.wrapper = model
+        self.core = core = model.module if hasattr(model, "module") else model
+        if core.engine is None:
+            raise hip.SvitHipError("GraphedEvalStep needs a finalized (on-GPU) SViT")
+        if core.training:
+            raise hip.SvitHipError("GraphedEvalStep captures the evaluation step: call model.eval() first (the training "
+                                   "step is graph.GraphedTrainStep)")
+        if val_meter is not None and cfg is None:
+            raise hip.SvitHipError("GraphedEvalStep(val_meter=...) needs cfg=: the validation losses are built from it")
+        dev = inputs[0].device
+        for name, m in (("val_meter", val_meter), ("test_meter", test_meter)):
+            if m is not None and torch.device(m.device) != dev:
+                raise hip.SvitHipError("GraphedEvalStep(%s=...): the meter lives on %s, the step on %s" % (name, m.device, dev))
+        self.cfg, self.val_meter, self.test_meter, self.repeat = cfg, val_meter, test_meter, int(repeat)
+        self.frames_pass = frames_pass
+        self.x = inputs[0].detach().clone().contiguous()
+        if isinstance(frames_pass, str):
+            if frames_pass != "u8":
+                raise hip.SvitHipError("frames_pass is False, True or \"u8\", got %r" % (frames_pass,))
+            if not isinstance(self.x, (U8Clips, AugClips)):
+                raise hip.SvitHipError("frames_pass=\"u8\" reads the frames of a U8Clips or an AugClips; for the fp32 "
+                                       "clip tensor pass frames_pass=True")
+        elif frames_pass and isinstance(self.x, AugClips):
+            raise hip.SvitHipError("frames_pass=True is the fp32 route and does not take an AugClips: pass "
+                                   "frames_pass=\"u8\" (or feed clips.render())")
+        if not torch.is_tensor(self.x):
+            self.x.lut_f32                    # (U8Clips: the fp32 table is built here, outside the capture)
+        self.labels = _tree_map(lambda t: t.detach().clone().contiguous(), labels)
+        self._split(self.labels)              # (refuses a tree the meters cannot be fed from)
+        self.graph = self.preds = self.extra = None
+        self.refresh()
+        self._capture(warmup)
+
+    # ------------------------------------------------------------------------------------------
+    def _split(self, labels):
+        """-> (labels int64 [B], clip_ids or None) of a label tree"""
+        if isinstance(labels, dict):
+            if "labels" not in labels:
+                raise hip.SvitHipError("the label tree of an evaluation step holds \"labels\" (and \"clip_ids\" for the "
+                                       "test ensemble), got %s" % sorted(labels))
+            lab, ids = labels["labels"], labels.get("clip_ids")
+        else:
+            lab, ids = labels, None
+        if self.test_meter is not None and ids is None:
+            raise hip.SvitHipError("GraphedEvalStep(test_meter=...) needs the label tree {\"labels\", \"clip_ids\"}")
+        if (self.val_meter is not None or self.test_meter is not None) and not torch.is_tensor(lab):
+            raise hip.SvitHipError("the meters need the labels as an int64 [B] tensor")
+        return lab, ids
+
+    def refresh(self):
+        """the bf16 copies of the weights, eagerly on the current stream (class docstring)"""
+        with torch.no_grad():
+            self.core.engine.refresh_weights()
+
+    def _body(self, x, labels, mode):
+        """mode "warm": the meters only fix their columns; "run": the captured body, and `eager`'s"""
+        core = self.core
+        eng = core.engine
+        Tx = x.shape[2] if x.dim() == 5 else 1
+        lab, ids = self._split(labels)
+        y, _ = eng.forward(x, None, save=False)
+        preds, extra = core.head_eval(y, Tx)
+        if self.frames_pass and Tx > 1:       # B*T single frames through the same kernels (T' = 1)
+            if self.frames_pass == "u8":      # (the clip forward above has run the RandAugment chain, if any)
+                from .input import FramesView
+                xf = FramesView(x, fresh=True)
+            else:
+                xf = x.transpose(1, 2).flatten(0, 1).unsqueeze(2)
+            fy, _ = eng.forward(xf, None, save=False)
+            fp, fe = core.head_eval(fy, 1)
+            extra["frames_output"] = {"preds": fp, "extra_preds": fe}
+        if self.val_meter is not None:
+            from .train import eval_extra_metrics
+            metrics = dict(eval_extra_metrics(self.cfg, preds, extra, lab, {}))
+            if mode == "warm":
+                self.val_meter.bind(metrics)
+            else:
+                self.val_meter.push(metrics, preds, lab, self.val_meter.ks)
+        if self.test_meter is not None and mode != "warm":
+            self.test_meter.update_stats(preds, lab, ids, repeat=self.repeat)
+        return preds, extra
+
+    def _capture(self, warmup):
+        dev = self.x.device
+        cap = torch.cuda.Stream(device=dev)
+        cap.wait_stream(torch.cuda.current_stream(dev))
+        with torch.no_grad():
+            with torch.cuda.stream(cap):
+                for _ in range(max(1, warmup)):       # lazy tables / library workspaces materialise here
+                    self._body(self.x, self.labels, "warm")
+            cap.synchronize()
+            self.graph = torch.cuda.CUDAGraph()
+            # "thread_local": the process group's watchdog thread may query events while we capture
+            with torch.cuda.graph(self.graph, stream=cap, capture_error_mode="thread_local"):
+                self.preds, self.extra = self._body(self.x, self.labels, "run")
+        torch.cuda.current_stream(dev).wait_stream(cap)
+        torch.cuda.synchronize(dev)
+
+    # ------------------------------------------------------------------------------------------
+    def check_batch(self, inputs):
+        """refuse a batch the capture does not fit (before anything is enqueued)"""
+        x = inputs[0]
+        if x.shape != self.x.shape:
+            raise hip.SvitHipError("GraphedEvalStep was captured for input %s, got %s"
+                                   % (tuple(self.x.shape), tuple(x.shape)))
+        if torch.is_tensor(self.x) != torch.is_tensor(x) or (not torch.is_tensor(x) and type(x) is not type(self.x)):
+            raise hip.SvitHipError("GraphedEvalStep was captured for a %s, got a %s"
+                                   % (type(self.x).__name__, type(x).__name__))
+        if not torch.is_tensor(x) and x.frames.shape != self.x.frames.shape:
+            raise hip.SvitHipError("GraphedEvalStep was captured for a frame buffer %s, got %s: pad the batch to the "
+                                   "captured size and pass the videos' extents"
+                                   % (tuple(self.x.frames.shape), tuple(x.frames.shape)))
+
+    def _host_half(self, n):
+        if self.val_meter is not None:
+            self.val_meter.host_update(n * getattr(self.wrapper, "world_size", 1), n)
+
+    def _check_eval(self):
+        if self.core.training:
+            raise hip.SvitHipError("GraphedEvalStep runs the evaluation step: call model.eval() first")
+
+    def __call__(self, inputs, labels):
+        """-> (preds, extra): static tensors, overwritten by every replay"""
+        self._check_eval()
+        self.check_batch(inputs)
+        x = inputs[0]
+        if x.data_ptr() != self.x.data_ptr():
+            self.x.copy_(x, non_blocking=True)        # (an AugClips: frames, records, extents)
+        _tree_copy(self.labels, labels)
+        self._host_half(self.x.shape[0])
+        self.graph.replay()
+        return self.preds, self.extra
+
+    @torch.no_grad()
+    def eager(self, inputs, labels):
+        """the same body, uncaptured, on the given objects (any batch size: the short last batch of an epoch; the
+        tests' twin) -> (preds, extra), fresh tensors"""
+        self._check_eval()
+        x = inputs[0]
+        out = self._body(x, labels, "run")
+        self._host_half(x.shape[0])
+        return out
+
+    @property
+    def static_inputs(self):
+        return [self.x]
+
+    @property
+    def static_labels(self):
+        return self.labels
 
 
 def _is_feeder(batch):

@@ -208,6 +208,7 @@ _SIGS = {
     "svit_adamw_step_guarded": (i32, [vp, vp, vp, vp, i64, i64, vp, vp, f32, f32, f32, vp]),
     "svit_head_fwd": (i32, [C.POINTER(HeadArgs), vp]),
     "svit_head_bwd": (i32, [C.POINTER(HeadBwdArgs), vp]),
+    "svit_head_eval": (i32, [C.POINTER(HeadArgs), i32, vp]),
     "svit_haog_loss": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp]),
     "svit_haog_loss_bwd": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, vp]),
     "svit_ce_loss": (i32, [vp, vp, i32, i32, vp, vp, vp]),

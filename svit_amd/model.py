@@ -338,6 +338,18 @@ class SViT(nn.Module):
         logits, boxes, contact, xobj = _HeadFn.apply(self, tokens, Tx, self.O, keep)
         return logits, {"obj_desc": xobj, "pred_bboxes": boxes, "pred_contact_state": contact}
 
+    @torch.no_grad()
+    def head_eval(self, tokens, Tx):
+        """Eval-mode head on the final norm's output tokens f32 [B,N,C] as ONE launch (csrc/head_eval.hip): what
+        `self.head` returns when `not self.training` -- class probabilities, sigmoid objectness, softmaxed contact
+        states -- with the keys of SViTHead.forward.  `forward` in eval mode keeps the ATen head; this is what
+        graph.GraphedEvalStep calls."""
+        head = self.head
+        probs, boxes, contact, xobj = ops.head_eval(tokens.contiguous(), Tx, self.O,
+                                                    [(w.data, b.data) for w, b in head.param_pairs()],
+                                                    act=0 if head.act_func == "softmax" else 1)
+        return probs, {"obj_desc": xobj, "pred_bboxes": boxes, "pred_contact_state": contact}
+
     def forward(self, x, metadata=None, bboxes=None, drop_scales=None, dropout_keep=None):
         if self.engine is None:
             raise hip.SvitHipError("SViT (svit_amd) has no CPU path: build it with "

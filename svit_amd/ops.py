@@ -915,6 +915,22 @@ def head_fwd(tokens, T, O, keep, head_params):
     return outs
 
 
+def head_eval(tokens, T, O, head_params, act=0):
+    """The eval-mode head in one launch (svit_head_eval): tokens f32 [B,N,C] as Engine.forward returns them -> class
+    PROBABILITIES [B,n_cls] (act 0 softmax, 1 sigmoid), pred_bboxes [B,T,O,5] (column 0 the sigmoid of the objectness
+    logit), contact [B,T,2,5] softmaxed over its last axis, obj_desc [B,T,O,C]."""
+    if not tokens.is_contiguous() or tokens.dtype != F32 or tokens.dim() != 3:
+        raise hip.SvitHipError("head_eval takes contiguous f32 [B,N,C] tokens, got %s %s" % (tokens.dtype, tuple(tokens.shape)))
+    _chk_dev(tokens, *[t for wb in head_params for t in wb])
+    B, N, C_ = tokens.shape
+    dev = tokens.device
+    outs = (torch.empty((B, head_params[0][0].shape[0]), device=dev), torch.empty((B, T, O, 5), device=dev),
+            torch.empty((B, T, 2, 5), device=dev), torch.empty((B, T, O, C_), device=dev))
+    a = _head_args(tokens, T, O, None, head_params, outs)
+    hip.call("svit_head_eval", C.byref(a), int(act))
+    return outs
+
+
 def head_bwd(tokens, T, O, keep, head_params, boxes, grads_out, param_grads, ordered=False):
     """-> d(tokens) f32 [B,N,C] (zero rows for the patch tokens); the parameter gradients are ADDED into
     param_grads (same nesting as head_params).  grads_out = (dlogits, dboxes, dcontact, dxobj), None allowed.

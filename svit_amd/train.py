@@ -12,7 +12,7 @@ import torch
 import torch.distributed as dist
 
 from . import losses, optim
-from .graph import AccumulatedTrainStep, GraphedTrainStep
+from .graph import AccumulatedTrainStep, GraphedEvalStep, GraphedTrainStep
 
 
 def _min_length(n):
@@ -223,10 +223,43 @@ def eval_extra_metrics(cfg, preds, extra_preds, labels, metadata):
     return loss_dict
 
 
+def _eval_epoch_step(val_loader, step, val_meter, cur_epoch, cfg, feeder):
+    """eval_epoch over a graph.GraphedEvalStep: an iteration is one replay (forward, frames pass, validation losses and
+    the meter's push, its host half included), a short last batch the same body eagerly (`evaluate.run_eval_step`).
+    `val_meter.data_toc()` is not called: the upload runs beside the previous replay (feeder) or lies with the loader, so
+    the loop has no point at which the data of an iteration has arrived and its compute has not begun (the device
+    meters' timers are no-ops and `time_diff` is wall time per read: meters.py)."""
+    from .evaluate import run_eval_step
+    if step.val_meter is not val_meter:
+        raise ValueError("eval_epoch: the GraphedEvalStep must be built with val_meter= the meter passed here (its "
+                         "replay holds the meter's push)")
+    if bool(cfg.TRAIN.FORWARD_VIDEO_FRAMES) != bool(step.frames_pass) and step.x.shape[2] > 1:
+        raise ValueError("eval_epoch: cfg.TRAIN.FORWARD_VIDEO_FRAMES is %s, the GraphedEvalStep was built with "
+                         "frames_pass=%r" % (cfg.TRAIN.FORWARD_VIDEO_FRAMES, step.frames_pass))
+    val_meter.iter_tic()
+
+    def after(cur_iter):
+        val_meter.iter_toc()
+        val_meter.log_iter_stats(cur_epoch, cur_iter)
+        val_meter.iter_tic()
+    run_eval_step(val_loader, step, feeder, after)
+    stats = val_meter.log_epoch_stats(cur_epoch)
+    val_meter.reset()
+    return stats
+
+
 @torch.no_grad()
-def eval_epoch(val_loader, model, val_meter, cur_epoch, cfg):
+def eval_epoch(val_loader, model, val_meter, cur_epoch, cfg, feeder=None):
     """tools/train_net.py:181-368, classification branch: per iteration one forward and one meter push (top-k hits and
-    the extra losses), no host read between periods."""
+    the extra losses), no host read between periods.
+    model: the model, or a graph.GraphedEvalStep built with `cfg=`, `val_meter=` this meter and the frames pass
+    cfg.TRAIN.FORWARD_VIDEO_FRAMES asks for -- the loader then yields device-side (inputs, labels, ...); with `feeder` (a
+    feeder.ClipFeeder over the step's static AugClips) it yields HOST batches (videos, records, labels, video_idx,
+    meta) and uploads overlap the step."""
+    if isinstance(model, GraphedEvalStep):
+        return _eval_epoch_step(val_loader, model, val_meter, cur_epoch, cfg, feeder)
+    if feeder is not None:
+        raise ValueError("eval_epoch(feeder=...) needs a GraphedEvalStep: the feeder writes its static buffers")
     model.eval()
     val_meter.iter_tic()
     dev = val_meter.device
