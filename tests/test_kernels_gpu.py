@@ -2,7 +2,8 @@
 inputs (the CPU oracle's functions where the op is SViT-specific).  Needs a real MI355X.
 The NT GEMM's epilogues are also judged element by element against float64, on every store path and kernel form, in
 tests/test_gemm_parity_gpu.py (bars and mutants: tests/gemm_reference.py); the GEMM tests here keep their whole-tensor
-measure."""
+measure.  Likewise the pooled q/k/v path: every forward path and the fused backward are judged per element, stage by
+stage, in tests/test_pool_parity_gpu.py (bars and mutants: tests/pool_reference.py); the pooling tests here stay as they are."""
 import math
 
 import numpy as np
