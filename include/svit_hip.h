@@ -769,6 +769,22 @@ int svit_debug_gemm_nt_plan(int M, int N, int K, int epilogue, int32_t* out, int
  * K % 192 == 0). */
 int svit_debug_set_tn(int step_us_x100, int atomic_tbs_x100);
 int svit_debug_set_tn_tile(int mode);
+/* What a TN GEMM call would launch under the current values of the knobs above -- the launch path's own argument check,
+ * planners and walk over the problem list (csrc/gemm_tn.hip: tn_check, tn_plan / tn_single_plan, tn_chunks).  Launches
+ * nothing, makes no HIP call and needs no device; the pointers of `probs` are only checked (non-NULL, alignment), never
+ * followed.  form: 0 svit_gemm_tn_grouped, 1 svit_gemm_tn_grouped_ex with ordered = 1, 2 svit_gemm_tn_grouped_slab,
+ * 3 the stand-alone svit_gemm_tn of probs[0] (count must be 1; arg = its `splits`; arg is ignored by the other forms).
+ * Returns the number of values written to out, or an error: the entry point's own code for what it refuses in `probs` /
+ * `count`, SVIT_ERR_ARG for a form outside 0..3, form 3 with count != 1, a NULL out or an n_out below
+ * 2 + 3 groups + 10 count.  Layout of out:
+ *   [0] launch groups (ceil(count / SVIT_TN_GROUP_MAX); 1 for form 3)   [1] floats of slab workspace (form 2, else 0:
+ *   what svit_gemm_tn_grouped_workspace answers), then per group
+ *     problems in the group; grid of the GEMM launch (workgroups); grid of the reduce launch (form 2, else 0), and per problem
+ *       tile kind (0 = 128x96, 1 = 128x192); tiles along N; tiles along K; rows_per_split; splits; first_block (the
+ *       problem's first logical workgroup: its workgroups are first_block + split * tiles + tile); and, form 2 (else 0):
+ *       slab columns w; tile_off; bias_off (float offsets into the workspace); red_first (its first reduce block).
+ *   Form 3: the grid is tiles along N x tiles along K x splits, tile kind 0, first_block 0. */
+int svit_debug_gemm_tn_plan(const svit_tn_problem* probs, int count, int form, int arg, int64_t* out, int n_out);
 /* pooling (csrc/pool.hip): key 0 = forward path of the small planes: 0 streaming kernels, 1 VALU slab conv, 2 (default)
  * MFMA conv where it is ahead (blocks 4-13 of 16x224^2) and the slab elsewhere, 3 MFMA conv wherever its geometry holds;
  * key 1 = conv backward: 1 (default) the fused plane-walk kernel (conv dgrad + conv wgrad in one launch),

@@ -3,9 +3,11 @@
 //                  through ds_read_b64_tr_b16 transposed LDS reads; fused bias gradient)
 //   svit_gemm_tn_grouped_slab : the grouped form with the row splits stored to slabs and summed in split order by a
 //                  second launch instead of meeting in fp32 atomics (bit-reproducible weight gradients)
+//   svit_debug_gemm_tn_plan : what any of these calls would launch, from the launch path's own check and planners
 // (the forward / dgrad kernel svit_gemm_nt lives in gemm_nt.hip)
 #include <algorithm>
 #include <type_traits>
+#include <vector>
 #include "common.h"
 #include "../../include/svit_hip.h"
 
@@ -20,25 +22,14 @@ __device__ __forceinline__ void tn_static_for(F&& f) {
 }
 
 // ---------------------------------------------------------------------------------------
-// TN kernel.  Both operands are [rows=m][cols] in LDS and read transposed (ds_read_b64_tr_b16).
-//   TnCfg<1, 4, 1, 64>: out tile 128(n) x 96(k), 4 waves of 32 x 96, 64 reduction rows per step.
-//   TnCfg<2, 2, 2, 32> (round 2): out tile 128 x 192, 2 x 2 waves of 64 x 96, 32 rows per step --
+// TN kernel.  Both operands are [rows=m][cols] in LDS and read transposed (ds_read_b64_tr_b16).  Two tile shapes,
+// TnSmallD / TnBigD = TnDma<RB, WN, WK, BM, NS> below -- the one description the kernels and the host planners read:
+//   TnSmallD <1, 4, 1, 64>: out tile 128(n) x 96(k), 4 waves of 32 x 96, 64 reduction rows per step.
+//   TnBigD <2, 2, 2, 32> (round 2): out tile 128 x 192, 2 x 2 waves of 64 x 96, 32 rows per step --
 //     the same 12 MFMAs per wave and step from 20 KB of staged operands instead of 28 KB
 //     (rocprofv3 round 2: the grouped launch fetched 687 MB against ~320 MB of operands and the
 //     CU's vector-memory path, not the matrix pipe, sets the pace), and 10 transposed LDS reads
 //     per 6 MFMAs instead of 8 per 3.
-// ---------------------------------------------------------------------------------------
-template <int RB_, int WN_, int WK_, int BM_>
-struct TnCfg {
-  static constexpr int RB = RB_, WN = WN_, WK = WK_, BM = BM_;
-  static constexpr int TN = 32 * RB * WN, TK = 96 * WK;
-  static constexpr int ROWA = TN * 2 + 64;                      // 320 B: the 4 rows of a tr block hit disjoint banks
-  static constexpr int ROWB = TK * 2 + ((TK * 2) % 256 == 128 ? 64 : 0);   // 192 B as is; 384 -> 448
-  static constexpr int STAGE = BM * (ROWA + ROWB);
-};
-using TnSmall = TnCfg<1, 4, 1, 64>;
-using TnBig = TnCfg<2, 2, 2, 32>;
-
 // ---------------------------------------------------------------------------------------
 // One workgroup's share: rows [m_begin, m_end) of the reduction for the TN x TK tile at (n0, k0).
 // Round 3: through an LDS-DMA ring.  The round-2 body (git history) staged both operands
@@ -292,8 +283,7 @@ __device__ __forceinline__ void tn_tile_dma(unsigned char* lds, const bf16_t* __
 }
 
 
-constexpr int TN_BM = TnSmall::BM, TN_TN = TnSmall::TN, TN_TK = TnSmall::TK;   // the single-GEMM entry point
-
+// the single-GEMM entry point: 128 x 96 tiles, grid (n tile, k tile, row split)
 __global__ __launch_bounds__(256) void gemm_tn_kernel(const bf16_t* __restrict__ A, int lda,
                                                       const bf16_t* __restrict__ B, int ldb,
                                                       float* __restrict__ dW, int lddw, int M,
@@ -301,8 +291,8 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(const bf16_t* __restrict__
                                                       float* __restrict__ dbias) {
   __shared__ __attribute__((aligned(16))) unsigned char lds[TN_DMA_LDS];
   const int m_begin = blockIdx.z * rows_per_split;
-  tn_tile_dma<TnSmallD, false>(lds, A, lda, B, ldb, dW, lddw, M, N, K, blockIdx.x * TN_TN, blockIdx.y * TN_TK, m_begin,
-                        min(M, m_begin + rows_per_split), dbias, blockIdx.y == 0);
+  tn_tile_dma<TnSmallD, false>(lds, A, lda, B, ldb, dW, lddw, M, N, K, blockIdx.x * TnSmallD::TN, blockIdx.y * TnSmallD::TK,
+                               m_begin, min(M, m_begin + rows_per_split), dbias, blockIdx.y == 0);
 }
 
 // Grouped launch: up to SVIT_TN_GROUP_MAX independent weight-gradient GEMMs share one grid, so
@@ -315,15 +305,31 @@ struct TnGroup {
   int tiles_n[SVIT_TN_GROUP_MAX];
   int tiles[SVIT_TN_GROUP_MAX];
   int rows_per_split[SVIT_TN_GROUP_MAX];
-  int big[SVIT_TN_GROUP_MAX];          // 1: 128 x 192 tiles (TnBig), 0: 128 x 96 (TnSmall)
+  int big[SVIT_TN_GROUP_MAX];          // 1: 128 x 192 tiles (TnBigD), 0: 128 x 96 (TnSmallD)
   int count;
 };
 
-#ifndef SVIT_TN_WPE         // waves per SIMD the grouped kernel is compiled for (diagnostic builds: 3 with SVIT_TN_BIG_NS=2 = three workgroups per CU)
-#define SVIT_TN_WPE 2
-#endif
-__global__ __launch_bounds__(256, SVIT_TN_WPE) void gemm_tn_grouped_kernel(const TnGroup g) {
-  __shared__ __attribute__((aligned(16))) unsigned char lds[TN_DMA_LDS];
+// ---------------------------------------------------------------------------------------
+// Slab form (svit_gemm_tn_grouped_slab): the same grid and the same main loop, but no two workgroups
+// ever write one address.  Workgroup (problem, split, tile) -- its LOGICAL id, not the XCD-remapped
+// block index -- stores its fp32 tile into slab number `local` of its problem and, on k-tile 0 of a
+// problem with a bias, its 128 bias partials into the second region; tn_slab_reduce_kernel, launched
+// right behind on the same stream, sums the splits of every output element in index order and adds
+// the sum to dW / dbias with one plain read-modify-write.  One writer per element: the result does
+// not depend on how the workgroups were scheduled.
+struct TnSlabs {
+  long long tile_off[SVIT_TN_GROUP_MAX];   // float offset of the problem's slab 0 (slab = 128 x w floats)
+  long long bias_off[SVIT_TN_GROUP_MAX];   // float offset of its bias partials [split][n tile][128]
+  int red_first[SVIT_TN_GROUP_MAX + 1];    // first block of the reduce grid
+  int w[SVIT_TN_GROUP_MAX];                // slab columns: min(tile width, K rounded up to 32)
+};
+constexpr int TN_RED_THREADS = 128;
+static_assert(TnSmallD::TN == 128 && TnBigD::TN == 128, "slabs and bias partials are 128 rows");
+
+// One workgroup of a grouped launch, both forms: which (problem, split, tile) it is, where its flush goes, and its tile
+// through the body of the problem's tile shape.  SLAB (sl, ws): the flush goes to the workgroup's own slab and bias partials.
+template <bool SLAB>
+__device__ __forceinline__ void tn_grouped_workgroup(unsigned char* lds, const TnGroup& g, const TnSlabs* sl, float* ws) {
   // Logical ids are (problem, split)-major, tile-minor: the tiles of one split walk the SAME
   // rows in lock-step and re-read each other's A / B column panels (A once per k-tile, B once
   // per n-tile).  Consecutive logical ids are therefore placed on ONE XCD, so those re-reads
@@ -341,60 +347,37 @@ __global__ __launch_bounds__(256, SVIT_TN_WPE) void gemm_tn_grouped_kernel(const
   const svit_tn_problem& p = g.p[pi];
   const int tn = tile % g.tiles_n[pi], tk = tile / g.tiles_n[pi];
   const int m_begin = split * g.rows_per_split[pi];
+  float *out, *bias;
+  int ld;
+  if constexpr (SLAB) {
+    ld = sl->w[pi];
+    out = ws + sl->tile_off[pi] + (long long)local * (128 * ld);
+    bias = p.dbias ? ws + sl->bias_off[pi] + (long long)(split * g.tiles_n[pi] + tn) * 128 : nullptr;
+  } else {
+    out = p.dW, ld = p.lddw, bias = p.dbias;
+  }
   if (g.big[pi])
-    tn_tile_dma<TnBigD, false>(lds, (const bf16_t*)p.A, p.lda, (const bf16_t*)p.B, p.ldb, p.dW, p.lddw, p.M, p.N, p.K,
-                        tn * TnBig::TN, tk * TnBig::TK, m_begin, min(p.M, m_begin + g.rows_per_split[pi]),
-                        p.dbias, tk == 0);
+    tn_tile_dma<TnBigD, SLAB>(lds, (const bf16_t*)p.A, p.lda, (const bf16_t*)p.B, p.ldb, out, ld, p.M, p.N, p.K,
+                              tn * TnBigD::TN, tk * TnBigD::TK, m_begin, min(p.M, m_begin + g.rows_per_split[pi]),
+                              bias, tk == 0);
   else
-    tn_tile_dma<TnSmallD, false>(lds, (const bf16_t*)p.A, p.lda, (const bf16_t*)p.B, p.ldb, p.dW, p.lddw, p.M, p.N, p.K,
-                          tn * TnSmall::TN, tk * TnSmall::TK, m_begin, min(p.M, m_begin + g.rows_per_split[pi]),
-                          p.dbias, tk == 0);
+    tn_tile_dma<TnSmallD, SLAB>(lds, (const bf16_t*)p.A, p.lda, (const bf16_t*)p.B, p.ldb, out, ld, p.M, p.N, p.K,
+                                tn * TnSmallD::TN, tk * TnSmallD::TK, m_begin, min(p.M, m_begin + g.rows_per_split[pi]),
+                                bias, tk == 0);
 }
 
-// ---------------------------------------------------------------------------------------
-// Slab form (svit_gemm_tn_grouped_slab): the same grid and the same main loop, but no two workgroups
-// ever write one address.  Workgroup (problem, split, tile) -- its LOGICAL id, not the XCD-remapped
-// block index -- stores its fp32 tile into slab number `local` of its problem and, on k-tile 0 of a
-// problem with a bias, its 128 bias partials into the second region; tn_slab_reduce_kernel, launched
-// right behind on the same stream, sums the splits of every output element in index order and adds
-// the sum to dW / dbias with one plain read-modify-write.  One writer per element: the result does
-// not depend on how the workgroups were scheduled.
-struct TnSlabs {
-  long long tile_off[SVIT_TN_GROUP_MAX];   // float offset of the problem's slab 0 (slab = 128 x w floats)
-  long long bias_off[SVIT_TN_GROUP_MAX];   // float offset of its bias partials [split][n tile][128]
-  int red_first[SVIT_TN_GROUP_MAX + 1];    // first block of the reduce grid
-  int w[SVIT_TN_GROUP_MAX];                // slab columns: min(tile width, K rounded up to 32)
-};
-constexpr int TN_RED_THREADS = 128;
-static_assert(TnSmall::TN == 128 && TnBig::TN == 128, "slabs and bias partials are 128 rows");
+#ifndef SVIT_TN_WPE         // waves per SIMD the grouped kernel is compiled for (diagnostic builds: 3 with SVIT_TN_BIG_NS=2 = three workgroups per CU)
+#define SVIT_TN_WPE 2
+#endif
+__global__ __launch_bounds__(256, SVIT_TN_WPE) void gemm_tn_grouped_kernel(const TnGroup g) {
+  __shared__ __attribute__((aligned(16))) unsigned char lds[TN_DMA_LDS];
+  tn_grouped_workgroup<false>(lds, g, nullptr, nullptr);
+}
 
 __global__ __launch_bounds__(256, SVIT_TN_WPE) void gemm_tn_grouped_slab_kernel(const TnGroup g, const TnSlabs sl,
                                                                                float* __restrict__ ws) {
   __shared__ __attribute__((aligned(16))) unsigned char lds[TN_DMA_LDS];
-  // (placement as in gemm_tn_grouped_kernel)
-  const int nwg = gridDim.x, lin = blockIdx.x;
-  const int xq = nwg >> 3, xr = nwg & 7, xcd = lin & 7;
-  int pi = 0;
-  const int bid = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + (lin >> 3);
-#pragma unroll
-  for (int i = 1; i < SVIT_TN_GROUP_MAX; ++i)
-    if (i < g.count && bid >= g.first_block[i]) pi = i;
-  const int local = bid - g.first_block[pi];
-  const int tile = local % g.tiles[pi], split = local / g.tiles[pi];
-  const svit_tn_problem& p = g.p[pi];
-  const int tn = tile % g.tiles_n[pi], tk = tile / g.tiles_n[pi];
-  const int m_begin = split * g.rows_per_split[pi];
-  const int w = sl.w[pi];
-  float* slab = ws + sl.tile_off[pi] + (long long)local * (128 * w);
-  float* bslab = p.dbias ? ws + sl.bias_off[pi] + (long long)(split * g.tiles_n[pi] + tn) * 128 : nullptr;
-  if (g.big[pi])
-    tn_tile_dma<TnBigD, true>(lds, (const bf16_t*)p.A, p.lda, (const bf16_t*)p.B, p.ldb, slab, w, p.M, p.N, p.K,
-                              tn * TnBig::TN, tk * TnBig::TK, m_begin, min(p.M, m_begin + g.rows_per_split[pi]),
-                              bslab, tk == 0);
-  else
-    tn_tile_dma<TnSmallD, true>(lds, (const bf16_t*)p.A, p.lda, (const bf16_t*)p.B, p.ldb, slab, w, p.M, p.N, p.K,
-                                tn * TnSmall::TN, tk * TnSmall::TK, m_begin, min(p.M, m_begin + g.rows_per_split[pi]),
-                                bslab, tk == 0);
+  tn_grouped_workgroup<true>(lds, g, &sl, ws);
 }
 
 // thread -> (four adjacent rows, one column) of one problem's dW, consecutive lanes on consecutive
@@ -418,7 +401,7 @@ __global__ __launch_bounds__(TN_RED_THREADS) void tn_slab_reduce_kernel(const Tn
   long long stride;       // floats between the same element of consecutive splits
   if (e < nmat) {
     const int rg = (int)(e / K), col = (int)(e - (long long)rg * K);
-    const int tk_w = g.big[pi] ? TnBig::TK : TnSmall::TK, w = sl.w[pi];
+    const int tk_w = g.big[pi] ? TnBigD::TK : TnSmallD::TK, w = sl.w[pi];
     const int tile = (col / tk_w) * tiles_n + rg / 32;
     stride = (long long)tiles * (128 * w);
     src = ws + sl.tile_off[pi] + (long long)tile * (128 * w) + ((long long)(rg % 32) * w + col % tk_w) * 4;
@@ -490,46 +473,18 @@ __global__ void colsum_kernel(const bf16_t* __restrict__ A, int lda, float* __re
 
 }  // namespace
 
-extern "C" int svit_gemm_tn(const void* A, int lda, const void* B, int ldb, float* dW, int lddw,
-                            int M, int N, int K, int splits, float* dbias, void* stream) {
-  if (!A || !B || !dW) return SVIT_ERR_ARG;
-  if (M <= 0 || N <= 0 || K <= 0) return SVIT_ERR_SHAPE;
-  if (lda % 8 != 0 || ldb % 8 != 0 || lda < N || ldb < K || lddw < K) return SVIT_ERR_ALIGN;
-  if (((uintptr_t)A | (uintptr_t)B) & 15) return SVIT_ERR_ALIGN;
-  const int tiles = ((N + TN_TN - 1) / TN_TN) * ((K + TN_TK - 1) / TN_TK);
-  if (splits <= 0) {
-    // Cost model fitted on MI355X (tools/bench_kernels.py tnsplit): a block needs ~0.85 us per
-    // 64-row step, 512 blocks run concurrently, and every split adds the whole [N,K] fp32 tile
-    // set with atomics at ~0.75 TB/s effective.  Take the split count minimising the sum.
-    const double atom_us = (double)N * K * 4.0 / 0.75e6;
-    double best = 1e30;
-    static const int cand[] = {1, 2, 3, 4, 6, 8, 12, 16, 24, 32, 48, 64, 96, 128, 192, 256, 384, 512};
-    for (int ci = 0; ci < (int)(sizeof(cand) / sizeof(cand[0])); ++ci) {
-      const int s = cand[ci];
-      const long steps = ((M + s - 1) / s + TN_BM - 1) / TN_BM;
-      if (steps < 2 && s > 1) break;
-      const long rounds = ((long)tiles * s + 511) / 512;
-      const double t = (double)rounds * steps * 0.85 + s * atom_us;
-      if (t < best) { best = t; splits = s; }
-    }
-  }
-  int rows_per_split = (M + splits - 1) / splits;
-  rows_per_split = ((rows_per_split + TN_BM - 1) / TN_BM) * TN_BM;
-  splits = (M + rows_per_split - 1) / rows_per_split;
-  dim3 grid((N + TN_TN - 1) / TN_TN, (K + TN_TK - 1) / TN_TK, splits);
-  hipLaunchKernelGGL(gemm_tn_kernel, grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)A,
-                     lda, (const bf16_t*)B, ldb, dW, lddw, M, N, K, rows_per_split, dbias);
-  SVIT_LAUNCH_CHECK();
-  return SVIT_OK;
+// ---------------------------------------------------------------------------------------
+// Host side: check -> plan -> launch, once each.  tn_check is the only argument check; tn_single_plan (the stand-alone
+// svit_gemm_tn) and tn_plan (every grouped form) are the only planners, pure functions of the shapes and the knob
+// table; tn_chunks is the only walk over a problem list.  svit_debug_gemm_tn_plan answers from the same three, so
+// what it reports is what a launch runs.
+// ---------------------------------------------------------------------------------------
+struct TnTileDims { int tn, tk, bm; };       // tile rows (n), tile columns (k), reduction rows per stage
+static constexpr TnTileDims tn_dims(int big) {
+  return big ? TnTileDims{TnBigD::TN, TnBigD::TK, TnBigD::BM} : TnTileDims{TnSmallD::TN, TnSmallD::TK, TnSmallD::BM};
 }
+static constexpr int tn_ceil(long a, long b) { return (int)((a + b - 1) / b); }
 
-// cost-model constants of the grouped launch: SVIT_K_TN_STEP_US_X100 (one 64-row step of a workgroup, 512 resident),
-// SVIT_K_TN_ATOMIC_TBS_X100 (effective fp32 atomic flush rate) and the tile mode SVIT_K_TN_TILE of the knob table in
-// common.h -- 2 = 128x192 everywhere since the in-step A/B of round 3 (13.46 -> 13.30 ms per step,
-// profiles/r03_tn_tile_modes.txt: inside the step the operands come from HBM, not from the Infinity Cache an isolated
-// loop keeps them in, and fewer, fatter tiles re-read less).  The 128x384 forms (eight waves, four waves, ring with loader
-// waves) and the XCD-packed placement table of round 4 measured level or behind (profiles/r04_tn_l2_counters.txt) and
-// live on only as tools/diag/variants/gemm_tn_r04_forms.hip.
 static int tn_check(const svit_tn_problem& p) {
   if (!p.A || !p.B || !p.dW) return SVIT_ERR_ARG;
   if (p.M <= 0 || p.N <= 0 || p.K <= 0) return SVIT_ERR_SHAPE;
@@ -538,68 +493,6 @@ static int tn_check(const svit_tn_problem& p) {
   if (((uintptr_t)p.A | (uintptr_t)p.B) & 15) return SVIT_ERR_ALIGN;
   return SVIT_OK;
 }
-
-
-// The ONE split planner: fills g for problems [0, n) (n <= SVIT_TN_GROUP_MAX) and returns the grid size.  A pure
-// function of the shapes and the knob table (the atomic launch, the slab launch and the slab workspace query share it).
-static int tn_plan(const svit_tn_problem* probs, int n, int ordered, TnGroup& g) {
-  g.count = n;
-  long max_steps = 1;
-  const int big_mode = svit_knob(SVIT_K_TN_TILE);
-  const double step_us = svit_knob(SVIT_K_TN_STEP_US_X100) * 0.01, atomic_tbs = svit_knob(SVIT_K_TN_ATOMIC_TBS_X100) * 0.01;
-  constexpr long slots = 512;      // resident 4-wave workgroups the planner counts on
-  int bm[SVIT_TN_GROUP_MAX];
-  double tile_bytes[SVIT_TN_GROUP_MAX];
-  for (int i = 0; i < g.count; ++i) {
-    g.p[i] = probs[i];
-    // 128 x 192 tiles where they are fully used (K a multiple of 192) and measured faster with the
-    // round-3 LDS-DMA body (tools/bench_kernels.py tngroup, profiles/r03_tn_tile_modes.txt): the
-    // M = 3656 groups of blocks 14-15 (-5 / -11 %) and the M = 50696 groups of blocks 2-3 (-16 / -22 %);
-    // not the M = 13064 groups of blocks 4-13 (+10 %: the doubled fp32 tile a workgroup flushes with
-    // atomics outweighs the smaller operand traffic) nor the M = 201224 group of block 0 (+11 %)
-    g.big[i] = big_mode == 1 ? (g.p[i].K % TnBig::TK == 0 && g.p[i].N >= 128 &&
-                                (g.p[i].M <= 4096 || (g.p[i].M >= 32768 && g.p[i].M < 131072)))
-               : big_mode == 3 ? (g.p[i].K % TnBig::TK == 0 && g.p[i].N >= 128)
-                               : (big_mode == 2);
-    const int tn = g.big[i] ? TnBig::TN : TnSmall::TN, tk = g.big[i] ? TnBig::TK : TnSmall::TK;
-    bm[i] = g.big[i] ? TnBigD::BM : TnSmall::BM;
-    tile_bytes[i] = (double)tn * tk * 4.0;
-    g.tiles_n[i] = (g.p[i].N + tn - 1) / tn;
-    g.tiles[i] = g.tiles_n[i] * ((g.p[i].K + tk - 1) / tk);
-    const long st = (g.p[i].M + bm[i] - 1) / bm[i];
-    if (st > max_steps) max_steps = st;
-  }
-  // Every problem is cut into chunks of `steps` steps (64 reduction rows on 128 x 96 tiles, 32 on
-  // 128 x 192: the same 12 MFMAs per wave), so all workgroups run about equally long.  Same
-  // fitted model as svit_gemm_tn: 0.85 us per step with 512 resident workgroups, plus the atomic
-  // flush of one fp32 tile per workgroup at ~0.75 TB/s.
-  double best = 1e30;
-  long best_steps = max_steps;
-  for (long steps = 2; steps <= max_steps; steps += (steps < 32 ? 1 : steps / 16)) {
-    long blocks = 0;
-    double flush = 0.0;
-    for (int i = 0; i < g.count; ++i) {
-      const long st = (g.p[i].M + bm[i] - 1) / bm[i];
-      const long nb = (long)g.tiles[i] * ((st + steps - 1) / steps);
-      blocks += nb;
-      flush += (double)nb * tile_bytes[i];
-    }
-    const double t = (double)((blocks + slots - 1) / slots) * steps * step_us +
-                     flush / (atomic_tbs * 1e6);
-    if (t < best) { best = t; best_steps = steps; }
-  }
-  if (ordered) best_steps = max_steps;
-  int total = 0;
-  for (int i = 0; i < g.count; ++i) {
-    g.rows_per_split[i] = (int)best_steps * bm[i];
-    const int splits = (g.p[i].M + g.rows_per_split[i] - 1) / g.rows_per_split[i];
-    g.first_block[i] = total;
-    total += g.tiles[i] * splits;
-  }
-  for (int i = g.count; i <= SVIT_TN_GROUP_MAX; ++i) g.first_block[i] = total;
-  return total;
-}
-
 static int tn_check_all(const svit_tn_problem* probs, int count) {
   if (!probs || count <= 0) return SVIT_ERR_ARG;
   for (int i = 0; i < count; ++i) {
@@ -609,28 +502,117 @@ static int tn_check_all(const svit_tn_problem* probs, int count) {
   return SVIT_OK;
 }
 
-static int tn_grouped(const svit_tn_problem* probs, int count, int ordered, void* stream) {
-  const int rc = tn_check_all(probs, count);
-  if (rc) return rc;
-  for (int base = 0; base < count; base += SVIT_TN_GROUP_MAX) {
-    TnGroup g;
-    const int total = tn_plan(probs + base, count - base < SVIT_TN_GROUP_MAX ? count - base : SVIT_TN_GROUP_MAX, ordered, g);
-    hipLaunchKernelGGL(gemm_tn_grouped_kernel, dim3(total), dim3(256), 0, (hipStream_t)stream, g);
-    SVIT_LAUNCH_CHECK();
+// ---- the stand-alone GEMM: 128 x 96 tiles, its own split chooser (NOT the grouped planner's: other constants, other
+// candidates -- folding the two would move kernels and splits)
+struct TnSingle { int tiles_n, tiles_k, splits, rows_per_split; };
+static int tn_single_splits(int M, int N, int K) {
+  // Cost model fitted on MI355X (tools/bench_kernels.py tnsplit): a block needs ~0.85 us per
+  // 64-row step, 512 blocks run concurrently, and every split adds the whole [N,K] fp32 tile
+  // set with atomics at ~0.75 TB/s effective.  Take the split count minimising the sum.
+  constexpr TnTileDims t = tn_dims(0);
+  const int tiles = tn_ceil(N, t.tn) * tn_ceil(K, t.tk);
+  const double atom_us = (double)N * K * 4.0 / 0.75e6;
+  double best = 1e30;
+  int splits = 1;
+  static const int cand[] = {1, 2, 3, 4, 6, 8, 12, 16, 24, 32, 48, 64, 96, 128, 192, 256, 384, 512};
+  for (int ci = 0; ci < (int)(sizeof(cand) / sizeof(cand[0])); ++ci) {
+    const int s = cand[ci];
+    const long steps = ((M + s - 1) / s + t.bm - 1) / t.bm;
+    if (steps < 2 && s > 1) break;
+    const long rounds = ((long)tiles * s + 511) / 512;
+    const double time = (double)rounds * steps * 0.85 + s * atom_us;
+    if (time < best) { best = time; splits = s; }
   }
+  return splits;
+}
+static TnSingle tn_single_plan(int M, int N, int K, int splits) {      // splits <= 0: the chooser's
+  constexpr TnTileDims t = tn_dims(0);
+  if (splits <= 0) splits = tn_single_splits(M, N, K);
+  const int rows_per_split = tn_ceil(tn_ceil(M, splits), t.bm) * t.bm;
+  return {tn_ceil(N, t.tn), tn_ceil(K, t.tk), tn_ceil(M, rows_per_split), rows_per_split};
+}
+
+extern "C" int svit_gemm_tn(const void* A, int lda, const void* B, int ldb, float* dW, int lddw,
+                            int M, int N, int K, int splits, float* dbias, void* stream) {
+  const svit_tn_problem p = {A, B, dW, dbias, lda, ldb, lddw, M, N, K};
+  const int rc = tn_check(p);
+  if (rc) return rc;
+  const TnSingle s = tn_single_plan(M, N, K, splits);
+  hipLaunchKernelGGL(gemm_tn_kernel, dim3(s.tiles_n, s.tiles_k, s.splits), dim3(256), 0, (hipStream_t)stream,
+                     (const bf16_t*)A, lda, (const bf16_t*)B, ldb, dW, lddw, M, N, K, s.rows_per_split, dbias);
+  SVIT_LAUNCH_CHECK();
   return SVIT_OK;
 }
 
-extern "C" int svit_gemm_tn_grouped(const svit_tn_problem* probs, int count, void* stream) {
-  return tn_grouped(probs, count, 0, stream);
+// ---- the grouped forms: tn_plan = tile rule per problem -> chunk-length search over the group -> fill.
+// The knobs: SVIT_K_TN_TILE (the tile mode), SVIT_K_TN_STEP_US_X100 (one 64-row step of a workgroup, 512 resident) and
+// SVIT_K_TN_ATOMIC_TBS_X100 (effective fp32 atomic flush rate) of the knob table in common.h.
+
+// Tile mode 2 = 128x192 everywhere since the in-step A/B of round 3 (13.46 -> 13.30 ms per step,
+// profiles/r03_tn_tile_modes.txt: inside the step the operands come from HBM, not from the Infinity Cache an isolated
+// loop keeps them in, and fewer, fatter tiles re-read less).  The 128x384 forms (eight waves, four waves, ring with loader
+// waves) and the XCD-packed placement table of round 4 measured level or behind (profiles/r04_tn_l2_counters.txt) and
+// live on only as tools/diag/variants/gemm_tn_r04_forms.hip.
+static int tn_tile_rule(const svit_tn_problem& p, int mode) {
+  // mode 1: 128 x 192 tiles where they are fully used (K a multiple of 192) and measured faster with the
+  // round-3 LDS-DMA body (tools/bench_kernels.py tngroup, profiles/r03_tn_tile_modes.txt): the
+  // M = 3656 groups of blocks 14-15 (-5 / -11 %) and the M = 50696 groups of blocks 2-3 (-16 / -22 %);
+  // not the M = 13064 groups of blocks 4-13 (+10 %: the doubled fp32 tile a workgroup flushes with
+  // atomics outweighs the smaller operand traffic) nor the M = 201224 group of block 0 (+11 %)
+  const bool whole = p.K % TnBigD::TK == 0 && p.N >= 128;
+  return mode == 1 ? (whole && (p.M <= 4096 || (p.M >= 32768 && p.M < 131072))) : mode == 3 ? whole : (mode == 2);
 }
 
-// ordered != 0: no problem is cut along its reduction rows, so every element of every dW
-// receives exactly ONE atomic add -- the weight gradients are bit-reproducible (a debugging /
-// regression-diff mode: few workgroups, several times slower than the split form).
-extern "C" int svit_gemm_tn_grouped_ex(const svit_tn_problem* probs, int count, int ordered,
-                                       void* stream) {
-  return tn_grouped(probs, count, ordered, stream);
+// Every problem is cut into chunks of `steps` steps (64 reduction rows on 128 x 96 tiles, 32 on
+// 128 x 192: the same 12 MFMAs per wave), so all workgroups run about equally long.  Same
+// fitted model as svit_gemm_tn: 0.85 us per step with 512 resident workgroups, plus the atomic
+// flush of one fp32 tile per workgroup at ~0.75 TB/s.  Reads g.p, g.big, g.tiles; ordered: nothing is cut.
+static long tn_chunk_steps(const TnGroup& g, int ordered, double step_us, double atomic_tbs) {
+  constexpr long slots = 512;      // resident 4-wave workgroups the planner counts on
+  long st[SVIT_TN_GROUP_MAX], max_steps = 1;
+  for (int i = 0; i < g.count; ++i) {
+    st[i] = tn_ceil(g.p[i].M, tn_dims(g.big[i]).bm);
+    if (st[i] > max_steps) max_steps = st[i];
+  }
+  if (ordered) return max_steps;
+  double best = 1e30;
+  long best_steps = max_steps;
+  for (long steps = 2; steps <= max_steps; steps += (steps < 32 ? 1 : steps / 16)) {
+    long blocks = 0;
+    double flush = 0.0;
+    for (int i = 0; i < g.count; ++i) {
+      const TnTileDims t = tn_dims(g.big[i]);
+      const long nb = (long)g.tiles[i] * ((st[i] + steps - 1) / steps);
+      blocks += nb;
+      flush += (double)nb * ((double)t.tn * t.tk * 4.0);
+    }
+    const double time = (double)((blocks + slots - 1) / slots) * steps * step_us + flush / (atomic_tbs * 1e6);
+    if (time < best) { best = time; best_steps = steps; }
+  }
+  return best_steps;
+}
+
+// The ONE planner of the grouped forms: fills g for problems [0, n) (n <= SVIT_TN_GROUP_MAX) and returns the grid size.
+static int tn_plan(const svit_tn_problem* probs, int n, int ordered, TnGroup& g) {
+  const int mode = svit_knob(SVIT_K_TN_TILE);
+  g.count = n;
+  for (int i = 0; i < n; ++i) {
+    g.p[i] = probs[i];
+    g.big[i] = tn_tile_rule(probs[i], mode);
+    const TnTileDims t = tn_dims(g.big[i]);
+    g.tiles_n[i] = tn_ceil(probs[i].N, t.tn);
+    g.tiles[i] = g.tiles_n[i] * tn_ceil(probs[i].K, t.tk);
+  }
+  const long steps = tn_chunk_steps(g, ordered, svit_knob(SVIT_K_TN_STEP_US_X100) * 0.01,
+                                    svit_knob(SVIT_K_TN_ATOMIC_TBS_X100) * 0.01);
+  int total = 0;
+  for (int i = 0; i < n; ++i) {      // the fill: rows per split, (problem, split)-major block ranges
+    g.rows_per_split[i] = (int)steps * tn_dims(g.big[i]).bm;
+    g.first_block[i] = total;
+    total += g.tiles[i] * tn_ceil(g.p[i].M, g.rows_per_split[i]);
+  }
+  for (int i = n; i <= SVIT_TN_GROUP_MAX; ++i) g.first_block[i] = total;
+  return total;
 }
 
 // slab regions of a planned group -> floats of workspace (every offset a multiple of 4 floats)
@@ -638,7 +620,7 @@ static int64_t tn_slab_layout(const TnGroup& g, TnSlabs& sl) {
   long long off = 0;
   int red = 0;
   for (int i = 0; i < g.count; ++i) {
-    const int tk = g.big[i] ? TnBig::TK : TnSmall::TK, k32 = (g.p[i].K + 31) / 32 * 32;
+    const int tk = tn_dims(g.big[i]).tk, k32 = (g.p[i].K + 31) / 32 * 32;
     sl.w[i] = k32 < tk ? k32 : tk;
     sl.tile_off[i] = off;
     off += (long long)(g.first_block[i + 1] - g.first_block[i]) * (128 * sl.w[i]);
@@ -656,40 +638,104 @@ static int64_t tn_slab_layout(const TnGroup& g, TnSlabs& sl) {
   return off;
 }
 
-extern "C" int64_t svit_gemm_tn_grouped_workspace(const svit_tn_problem* probs, int count) {
+// The ONE walk over a problem list: checked, cut into launch groups of SVIT_TN_GROUP_MAX, each planned once (with its
+// slab layout where wanted).  Every launch form and both queries go through it.
+struct TnChunk {
+  TnGroup g;
+  TnSlabs sl;                // (slabs only)
+  int grid;
+  int64_t slab_floats;       // (slabs only, else 0)
+};
+static int tn_chunks(const svit_tn_problem* probs, int count, int ordered, bool slabs, std::vector<TnChunk>& chunks) {
   const int rc = tn_check_all(probs, count);
   if (rc) return rc;
-  int64_t need = 0;
-  for (int base = 0; base < count; base += SVIT_TN_GROUP_MAX) {
-    TnGroup g;
-    TnSlabs sl;
-    tn_plan(probs + base, count - base < SVIT_TN_GROUP_MAX ? count - base : SVIT_TN_GROUP_MAX, 0, g);
-    const int64_t n = tn_slab_layout(g, sl);
-    if (n > need) need = n;
+  chunks.resize((count + SVIT_TN_GROUP_MAX - 1) / SVIT_TN_GROUP_MAX);
+  for (size_t c = 0; c < chunks.size(); ++c) {
+    const int base = (int)c * SVIT_TN_GROUP_MAX;
+    chunks[c].grid = tn_plan(probs + base, std::min(count - base, SVIT_TN_GROUP_MAX), ordered, chunks[c].g);
+    chunks[c].slab_floats = slabs ? tn_slab_layout(chunks[c].g, chunks[c].sl) : 0;
   }
+  return SVIT_OK;
+}
+static int64_t tn_slab_need(const std::vector<TnChunk>& chunks) {      // every chunk reuses the workspace from offset 0
+  int64_t need = 0;
+  for (const TnChunk& c : chunks) need = std::max(need, c.slab_floats);
   return need;
+}
+
+// ordered != 0: no problem is cut along its reduction rows, so every element of every dW
+// receives exactly ONE atomic add -- the weight gradients are bit-reproducible (a debugging /
+// regression-diff mode: few workgroups, several times slower than the split form).
+extern "C" int svit_gemm_tn_grouped_ex(const svit_tn_problem* probs, int count, int ordered, void* stream) {
+  std::vector<TnChunk> chunks;
+  const int rc = tn_chunks(probs, count, ordered, false, chunks);
+  if (rc) return rc;
+  for (const TnChunk& c : chunks) {
+    hipLaunchKernelGGL(gemm_tn_grouped_kernel, dim3(c.grid), dim3(256), 0, (hipStream_t)stream, c.g);
+    SVIT_LAUNCH_CHECK();
+  }
+  return SVIT_OK;
+}
+extern "C" int svit_gemm_tn_grouped(const svit_tn_problem* probs, int count, void* stream) {
+  return svit_gemm_tn_grouped_ex(probs, count, 0, stream);
+}
+
+extern "C" int64_t svit_gemm_tn_grouped_workspace(const svit_tn_problem* probs, int count) {
+  std::vector<TnChunk> chunks;
+  const int rc = tn_chunks(probs, count, 0, true, chunks);
+  return rc ? rc : tn_slab_need(chunks);
 }
 
 extern "C" int svit_gemm_tn_grouped_slab(const svit_tn_problem* probs, int count, float* workspace,
                                          int64_t workspace_floats, void* stream) {
-  const int64_t need = svit_gemm_tn_grouped_workspace(probs, count);
-  if (need < 0) return (int)need;
-  if (!workspace || workspace_floats < need) return SVIT_ERR_ARG;
+  std::vector<TnChunk> chunks;
+  const int rc = tn_chunks(probs, count, 0, true, chunks);
+  if (rc) return rc;
+  if (!workspace || workspace_floats < tn_slab_need(chunks)) return SVIT_ERR_ARG;
   if ((uintptr_t)workspace & 15) return SVIT_ERR_ALIGN;
-  // every group chunk reuses the workspace from offset 0: the chunk's reduce is behind its GEMM and in front of the
-  // next chunk's GEMM on the one stream
-  for (int base = 0; base < count; base += SVIT_TN_GROUP_MAX) {
-    TnGroup g;
-    TnSlabs sl;
-    const int total = tn_plan(probs + base, count - base < SVIT_TN_GROUP_MAX ? count - base : SVIT_TN_GROUP_MAX, 0, g);
-    tn_slab_layout(g, sl);
-    hipLaunchKernelGGL(gemm_tn_grouped_slab_kernel, dim3(total), dim3(256), 0, (hipStream_t)stream, g, sl, workspace);
+  // the chunk's reduce is behind its GEMM and in front of the next chunk's GEMM on the one stream
+  for (const TnChunk& c : chunks) {
+    hipLaunchKernelGGL(gemm_tn_grouped_slab_kernel, dim3(c.grid), dim3(256), 0, (hipStream_t)stream, c.g, c.sl, workspace);
     SVIT_LAUNCH_CHECK();
-    hipLaunchKernelGGL(tn_slab_reduce_kernel, dim3(sl.red_first[SVIT_TN_GROUP_MAX]), dim3(TN_RED_THREADS), 0,
-                       (hipStream_t)stream, g, sl, (const float*)workspace);
+    hipLaunchKernelGGL(tn_slab_reduce_kernel, dim3(c.sl.red_first[SVIT_TN_GROUP_MAX]), dim3(TN_RED_THREADS), 0,
+                       (hipStream_t)stream, c.g, c.sl, (const float*)workspace);
     SVIT_LAUNCH_CHECK();
   }
   return SVIT_OK;
+}
+
+// What a call would launch (include/svit_hip.h has the layout): the check, planners and walk above, no HIP call.
+extern "C" int svit_debug_gemm_tn_plan(const svit_tn_problem* probs, int count, int form, int arg, int64_t* out,
+                                       int n_out) {
+  if (form < 0 || form > 3 || !out || (form == 3 && count != 1)) return SVIT_ERR_ARG;
+  std::vector<TnChunk> chunks;
+  const int rc = form == 3 ? tn_check_all(probs, count) : tn_chunks(probs, count, form == 1, form == 2, chunks);
+  if (rc) return rc;
+  const int groups = form == 3 ? 1 : (int)chunks.size(), n = 2 + 3 * groups + 10 * count;
+  if (n_out < n) return SVIT_ERR_ARG;
+  int64_t* o = out;
+  *o++ = groups;
+  *o++ = tn_slab_need(chunks);
+  if (form == 3) {
+    const TnSingle s = tn_single_plan(probs[0].M, probs[0].N, probs[0].K, arg);
+    const int64_t v[13] = {1, (int64_t)s.tiles_n * s.tiles_k * s.splits, 0,
+                           0, s.tiles_n, s.tiles_k, s.rows_per_split, s.splits, 0, 0, 0, 0, 0};
+    o = std::copy(v, v + 13, o);
+  }
+  for (const TnChunk& c : chunks) {
+    const TnGroup& g = c.g;
+    const bool slab = form == 2;
+    const int64_t head[3] = {g.count, c.grid, slab ? c.sl.red_first[SVIT_TN_GROUP_MAX] : 0};
+    o = std::copy(head, head + 3, o);
+    for (int i = 0; i < g.count; ++i) {
+      const int64_t v[10] = {g.big[i], g.tiles_n[i], g.tiles[i] / g.tiles_n[i], g.rows_per_split[i],
+                             (g.first_block[i + 1] - g.first_block[i]) / g.tiles[i], g.first_block[i],
+                             slab ? c.sl.w[i] : 0, slab ? c.sl.tile_off[i] : 0, slab ? c.sl.bias_off[i] : 0,
+                             slab ? c.sl.red_first[i] : 0};
+      o = std::copy(v, v + 10, o);
+    }
+  }
+  return (int)(o - out);
 }
 
 extern "C" int svit_colsum_bf16(const void* A, int lda, float* out, int M, int N, void* stream) {

@@ -227,6 +227,7 @@ _SIGS = {
     "svit_debug_pool_bwd_path": (i32, []),
     "svit_debug_pool_plan": (i32, [i32] * 13 + [C.POINTER(C.c_int32), i32]),
     "svit_debug_gemm_nt_plan": (i32, [i32] * 4 + [C.POINTER(C.c_int32), i32]),
+    "svit_debug_gemm_tn_plan": (i32, [C.POINTER(TnProblem), i32, i32, i32, C.POINTER(i64), i32]),
 }
 EXPORTS = tuple(sorted(_SIGS))
 

@@ -125,46 +125,67 @@ def gemm_tn(a, b, dw, splits=0, dbias=None):
     return dw
 
 
-def gemm_tn_grouped(problems, ordered=False):
-    """problems: [(a[M,N], b[M,K'], dw[N,K] f32, dbias or None)], each as for gemm_tn; all are
-    accumulated by one launch (per group of 8).  ordered: no split along the reduction rows
-    (bit-reproducible weight gradients, slower)."""
-    n = len(problems)
-    if n == 0:
-        return
-    arr = (hip.TnProblem * n)()
-    flop = 0.0
-    for i, (a, b, dw, dbias) in enumerate(problems):
-        _chk_rows(a, b)
-        _chk_dev(dw)
-        M, N = a.shape
-        K = dw.shape[-1]
-        assert b.shape[0] == M and b.shape[1] >= K and dw.shape[-2] == N and dw.dtype == F32
-        t = arr[i]
-        t.A, t.B, t.dW, t.dbias = ptr(a), ptr(b), ptr(dw), ptr(dbias)
-        t.lda, t.ldb, t.lddw, t.M, t.N, t.K = a.stride(0), b.stride(0), dw.stride(-2), M, N, K
-        flop += 2.0 * M * N * K
-    if ordered:
-        hip.call("svit_gemm_tn_grouped_ex", arr, n, 1, meta=("flop", flop))
-    else:
-        hip.call("svit_gemm_tn_grouped", arr, n, meta=("flop", flop))
-
-
 def _tn_problem_array(problems):
-    n = len(problems)
-    arr = (hip.TnProblem * n)()
+    """[(a[M,N], b[M,K'], dw[N,K] f32, dbias or None)], each as for gemm_tn -> (svit_tn_problem array, flop)"""
+    arr = (hip.TnProblem * len(problems))()
     flop = 0.0
-    for i, (a, b, dw, dbias) in enumerate(problems):
+    for t, (a, b, dw, dbias) in zip(arr, problems):
         _chk_rows(a, b, dw)          # (dw too may be the leading columns of wider rows: lddw = its row stride)
         _chk_dev(dbias)
         M, N = a.shape
-        K = dw.shape[1]
+        K = dw.shape[1]  # may be smaller than b's padded width
         assert b.shape[0] == M and b.shape[1] >= K and dw.shape[0] == N and dw.dtype == F32
-        t = arr[i]
         t.A, t.B, t.dW, t.dbias = ptr(a), ptr(b), ptr(dw), ptr(dbias)
         t.lda, t.ldb, t.lddw, t.M, t.N, t.K = a.stride(0), b.stride(0), dw.stride(0), M, N, K
         flop += 2.0 * M * N * K
     return arr, flop
+
+
+def gemm_tn_grouped(problems, ordered=False):
+    """problems: [(a[M,N], b[M,K'], dw[N,K] f32, dbias or None)], each as for gemm_tn with a 2-D dw; all are accumulated
+    by one launch per group of 16 (SVIT_TN_GROUP_MAX).  ordered: no split along the reduction rows (bit-reproducible
+    weight gradients, slower)."""
+    if not problems:
+        return
+    arr, flop = _tn_problem_array(problems)
+    if ordered:
+        hip.call("svit_gemm_tn_grouped_ex", arr, len(problems), 1, meta=("flop", flop))
+    else:
+        hip.call("svit_gemm_tn_grouped", arr, len(problems), meta=("flop", flop))
+
+
+TN_FORMS = ("atomic", "ordered", "slab", "single")
+_TN_PLAN_FIELDS = ("tile_kind", "tiles_n", "tiles_k", "rows_per_split", "splits", "first_block", "w", "tile_off", "bias_off",
+                   "red_first")
+
+
+def gemm_tn_plan(problems, form="atomic", splits=0):
+    """What gemm_tn_grouped ("atomic"; "ordered"), gemm_tn_grouped_slab ("slab") or gemm_tn ("single": one problem, with
+    `splits`) would launch for these problems under the current knobs (svit_debug_gemm_tn_plan: the launch path's own check
+    and planners; launches nothing, needs no device).  problems: as for gemm_tn_grouped, or plain (M, N, K, has_bias) tuples
+    (no tensors: fake aligned pointers and the smallest legal leading dimensions stand in).  form: a name or its index in
+    TN_FORMS.  -> dict of form, workspace_floats (slab) and groups: per launch group grid, reduce_grid (slab) and problems,
+    a dict each of tile_kind (0 = 128x96, 1 = 128x192), tiles_n, tiles_k, rows_per_split, splits, first_block and, for the
+    slab form, w, tile_off, bias_off, red_first."""
+    form = TN_FORMS.index(form) if isinstance(form, str) else form
+    n = len(problems)
+    if n and isinstance(problems[0][0], int):
+        arr = (hip.TnProblem * n)()
+        for t, (M, N, K, has_bias) in zip(arr, problems):
+            t.A, t.B, t.dW, t.dbias = 1 << 20, 2 << 20, 3 << 20, (4 << 20) if has_bias else None
+            t.lda, t.ldb, t.lddw, t.M, t.N, t.K = -(-N // 8) * 8, -(-K // 8) * 8, K, M, N, K
+    else:
+        arr = _tn_problem_array(problems)[0]
+    size = 2 + 3 * (n // 16 + 1) + 10 * n
+    out = (C.c_int64 * size)()
+    got = hip.load().svit_debug_gemm_tn_plan(arr, n, form, splits, out, size)
+    hip.check(min(got, 0), "svit_debug_gemm_tn_plan")
+    vals, groups = iter(out[2:got]), []
+    for _ in range(out[0]):
+        count, grid, reduce_grid = next(vals), next(vals), next(vals)
+        groups.append(dict(grid=grid, reduce_grid=reduce_grid,
+                           problems=[dict(zip(_TN_PLAN_FIELDS, vals)) for _ in range(count)]))
+    return dict(form=TN_FORMS[form], workspace_floats=out[1], groups=groups)
 
 
 _tn_slab_need = {}      # shape set -> floats of slab workspace (the planner is a pure function of the shapes)

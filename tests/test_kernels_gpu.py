@@ -182,7 +182,7 @@ def test_gemm_tn_grouped(ops, count, tile_mode):
         lib.svit_debug_reset()
 
 
-def _tn_grouped_case(ops, count, shapes=None):
+def _tn_grouped_case(ops, count, shapes=None, ordered=False):
     shapes = (shapes or [(1000, 288, 96), (4100, 384, 1536), (70, 96, 441), (13064, 384, 384), (333, 40, 96),
               (64, 3072, 768), (2000, 1152, 384), (5000, 96, 96), (129, 128, 96), (8000, 64, 96),
               (700, 768, 768)])[:count]
@@ -196,11 +196,29 @@ def _tn_grouped_case(ops, count, shapes=None):
         probs.append((a, b, dw, db))
         refs.append((a.float().t() @ b.float()[:, :K] + 0.5,
                      None if db is None else a.float().sum(0) + 0.25))
-    ops.gemm_tn_grouped(probs)
+    ops.gemm_tn_grouped(probs, ordered=ordered)
     for (a, b, dw, db), (rw, rb) in zip(probs, refs):
         assert rel_err(dw, rw) < 2e-4
         if db is not None:
             assert rel_err(db, rb) < 2e-4
+    return [(dw, db) for a, b, dw, db in probs]
+
+
+def test_gemm_tn_grouped_past_one_launch_group(ops):
+    """17 small problems = two launch groups (16 + 1) in the atomic and the ordered form: partial tiles in both directions,
+    ragged last stages (one M below a 32-row stage, one of exactly 64), K tails inside a padded ldb; the ordered form gives
+    the same bits twice"""
+    Ms = (20, 64, 300, 33, 129, 250, 97, 200, 31, 65, 128, 299, 45, 160, 77, 256, 111)
+    Ns, Ks = (40, 96, 128, 288), (96, 192, 200, 441)
+    shapes = [(M, Ns[i % 4], Ks[(i + i // 4) % 4]) for i, M in enumerate(Ms)]
+    assert len(shapes) == 17 and {s[1] for s in shapes} == set(Ns) and {s[2] for s in shapes} == set(Ks)
+    assert [g["grid"] > 0 for g in ops.gemm_tn_plan([s + (True,) for s in shapes])["groups"]] == [True, True]
+    _tn_grouped_case(ops, 17, shapes=shapes)
+    first = _tn_grouped_case(ops, 17, shapes=shapes, ordered=True)
+    second = _tn_grouped_case(ops, 17, shapes=shapes, ordered=True)
+    for (dw0, db0), (dw1, db1) in zip(first, second):
+        assert dw0 is not dw1 and torch.equal(dw0, dw1)
+        assert (db0 is None and db1 is None) or torch.equal(db0, db1)
 
 
 def test_colsum_cast_scale(ops):
