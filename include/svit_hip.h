@@ -92,6 +92,14 @@ int svit_gemm_tn_grouped_slab(const svit_tn_problem* probs, int count, float* wo
  * table (no HIP call: works without a GPU), never smaller than what svit_gemm_tn_grouped_slab checks for; a negative
  * SVIT_ERR_* for the argument errors that entry point reports. */
 int64_t svit_gemm_tn_grouped_workspace(const svit_tn_problem* probs, int count);
+/* svit_gemm_tn_grouped_slab for the LEADING launch_count problems (1 <= launch_count <= count, else SVIT_ERR_ARG) of a
+ * list that is checked and planned whole; the pointers of the rest are never followed (any aligned non-null address).
+ * The planner cuts every problem of a launch by one step count found over all its problems, so the leading problems
+ * get the row splits -- hence, bit for bit, the results -- they have in svit_gemm_tn_grouped_slab over the whole list.
+ * The backward that stops above frozen blocks (svit_amd/engine.py) passes, behind its own problems, the shapes of the
+ * problems the full backward queues into the same launch.  Workspace as for the whole list. */
+int svit_gemm_tn_grouped_slab_lead(const svit_tn_problem* probs, int count, int launch_count, float* workspace,
+                                   int64_t workspace_floats, void* stream);
 /* dbias[N] (f32, atomically accumulated) += column sums of bf16 A[M,N]. */
 int svit_colsum_bf16(const void* A, int lda, float* out, int M, int N, void* stream);
 
@@ -623,6 +631,29 @@ int svit_step_guard(const float* g, int64_t n, const svit_step_host* host_rec, s
 int svit_adamw_step_guarded(float* p, const float* g, float* m, float* v, int64_t n, int64_t n_decay,
                             const svit_step_host* host_rec, const svit_step_dev* dev_rec, float beta1, float beta2,
                             float eps, void* stream);
+
+/* The guarded tail over the TRAINABLE part of the flat buffers (parameters with requires_grad = False are frozen:
+ * never read, never written, not counted in the norm).  The trainable set is a segment table: `segs` = int64 [S][2] of
+ * (begin, end) float indices IN HOST MEMORY, 1 <= S <= SVIT_MAX_SEGS, ascending and disjoint (begin >= the previous
+ * end), no empty segment, end <= n, every bound a multiple of 4 (the flat layout aligns slots to 8 floats).  The table
+ * is checked on the host before any HIP call and travels to the device inside the kernel arguments (1 KB, read by
+ * scalar loads at workgroup-uniform indices; a captured graph keeps its copy), so the caller may free it after the call.
+ * SVIT_ERR_ARG: S out of range, NULL table, an unsorted, overlapping or empty segment, end > n, and for the AdamW entry
+ * point a segment that straddles n_decay; SVIT_ERR_ALIGN: a bound not a multiple of 4, g / p / m / v not 16-byte aligned.
+ *
+ * svit_step_guard_seg: svit_step_guard over the segments.  Elements keep svit_sumsq's assignment to partial sums by
+ * absolute position; one outside every segment contributes 0 and is not loaded.  The record it leaves is therefore bit
+ * for bit svit_step_guard's on a buffer whose other ranges hold zeros (data-parallel replicas keep deriving the same
+ * coefficient), and a NaN or inf outside the segments does not drop the step.
+ * svit_adamw_step_guarded_seg: svit_adamw_step_guarded's arithmetic in its order on the elements inside a segment, ONE
+ * launch; no load or store of p, g, m or v outside the segments; returns early on a dropped step. */
+#define SVIT_MAX_SEGS 64
+int svit_step_guard_seg(const float* g, int64_t n, const int64_t* segs, int64_t S, const svit_step_host* host_rec,
+                        svit_step_dev* dev_rec, const float* bias_table, int64_t table_entries, float* workspace,
+                        int64_t workspace_floats, void* stream);
+int svit_adamw_step_guarded_seg(float* p, const float* g, float* m, float* v, int64_t n, int64_t n_decay,
+                                const int64_t* segs, int64_t S, const svit_step_host* host_rec,
+                                const svit_step_dev* dev_rec, float beta1, float beta2, float eps, void* stream);
 
 /* ------------------------------------------------------------------ head (K15) ---------- */
 /* SViT head (slowfast/models/video_model_builder.py:408-551) in one launch each way, fp32: dropout factors

@@ -704,6 +704,34 @@ extern "C" int svit_gemm_tn_grouped_slab(const svit_tn_problem* probs, int count
   return SVIT_OK;
 }
 
+// svit_gemm_tn_grouped_slab for the LEADING `launch_count` problems of a list that is checked and planned whole: the
+// rest only takes part in the plan (its pointers are never followed).  A backward that stops above frozen blocks hands
+// over the problems the full backward would have had in the same launch, and the leading ones get the full backward's
+// row splits -- the planner cuts every problem of a launch by one step count found over all of them -- hence its
+// weight gradients, bit for bit.  Logical workgroup ids are problem-major: the leading problems own the ids below
+// first_block[lead], the reduce blocks below red_first[lead], and the XCD remap is a bijection for any grid size.
+extern "C" int svit_gemm_tn_grouped_slab_lead(const svit_tn_problem* probs, int count, int launch_count,
+                                              float* workspace, int64_t workspace_floats, void* stream) {
+  if (launch_count < 1 || launch_count > count) return SVIT_ERR_ARG;
+  std::vector<TnChunk> chunks;
+  const int rc = tn_chunks(probs, count, 0, true, chunks);
+  if (rc) return rc;
+  if (!workspace || workspace_floats < tn_slab_need(chunks)) return SVIT_ERR_ARG;
+  if ((uintptr_t)workspace & 15) return SVIT_ERR_ALIGN;
+  for (size_t i = 0; i < chunks.size(); ++i) {
+    const TnChunk& c = chunks[i];
+    const int lead = std::min(launch_count - (int)i * SVIT_TN_GROUP_MAX, c.g.count);
+    if (lead <= 0) break;
+    hipLaunchKernelGGL(gemm_tn_grouped_slab_kernel, dim3(c.g.first_block[lead]), dim3(256), 0, (hipStream_t)stream, c.g,
+                       c.sl, workspace);
+    SVIT_LAUNCH_CHECK();
+    hipLaunchKernelGGL(tn_slab_reduce_kernel, dim3(c.sl.red_first[lead]), dim3(TN_RED_THREADS), 0, (hipStream_t)stream,
+                       c.g, c.sl, (const float*)workspace);
+    SVIT_LAUNCH_CHECK();
+  }
+  return SVIT_OK;
+}
+
 // What a call would launch (include/svit_hip.h has the layout): the check, planners and walk above, no HIP call.
 extern "C" int svit_debug_gemm_tn_plan(const svit_tn_problem* probs, int count, int form, int arg, int64_t* out,
                                        int n_out) {

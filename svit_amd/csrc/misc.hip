@@ -578,6 +578,103 @@ __global__ __launch_bounds__(256) void adamw_guarded_kernel(float* __restrict__ 
   else adamw_guarded_range<false>(p, g, m, v, n, n_decay, h, coef, bc1, bc2_sqrt, b1, b2, eps);
 }
 
+// ---- the guarded tail over a segment table (frozen parameters: svit_step_guard_seg / svit_adamw_step_guarded_seg) ----
+// The table rides in the kernel arguments: every read of it is a scalar load at a workgroup-uniform index, no lane ever
+// looks a segment up.  Both kernels walk the buffer the way their plain twins do -- workgroup b takes the 1024 floats at
+// b * 1024 + pass * gridDim.x * 1024 -- and since windows and segments both ascend, a cursor that only moves forward finds
+// the segments a window meets: S scalar steps per workgroup for the whole buffer, and per 16-byte access one or two
+// compares (a window meets more than one segment only at a boundary).
+struct SegTable {
+  int64_t v[SVIT_MAX_SEGS][2];
+  int32_t S;
+};
+// is the quad at float index i, which lies in the window [lo, hi), inside a segment?  k: first segment that ends past lo
+__device__ __forceinline__ bool seg_inside(const SegTable& t, int& k, int64_t lo, int64_t hi, int64_t i) {
+  while (k < t.S && t.v[k][1] <= lo) ++k;
+  bool in = false;
+  for (int j = k; j < t.S && t.v[j][0] < hi; ++j) in |= (i >= t.v[j][0]) & (i < t.v[j][1]);
+  return in;
+}
+
+// sumsq_kernel with the same element -> (workgroup, thread, pass) mapping: an element outside every segment adds nothing
+// and is not loaded, so the partials equal sumsq_kernel's on a buffer that holds zeros there (s >= 0: s + 0 is s).
+// Segment bounds are multiples of 4 and end <= n: a quad is inside whole or not at all, the n % 4 tail never is.
+__global__ void sumsq_seg_kernel(const float* __restrict__ g, int64_t n, float* __restrict__ partial, const SegTable t) {
+  float s = 0.f;
+  const int64_t window = (int64_t)blockDim.x * 4, stride = (int64_t)gridDim.x * window;
+  int k = 0;
+  for (int64_t lo = (int64_t)blockIdx.x * window; lo < n; lo += stride) {
+    const int64_t i = lo + (int64_t)threadIdx.x * 4;
+    if (seg_inside(t, k, lo, lo + window, i)) {
+      const float4 v = *(const float4*)(g + i);
+      s += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
+    }
+  }
+  s = wave_sum(s);
+  __shared__ float red[4];
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+template <bool CLAMP>
+__device__ __forceinline__ void adamw_guarded_seg_range(float* __restrict__ p, const float* __restrict__ g,
+                                                        float* __restrict__ m, float* __restrict__ v, int64_t n,
+                                                        int64_t n_decay, const svit_step_host* __restrict__ h,
+                                                        float coef, float bc1, float bc2_sqrt, float b1, float b2,
+                                                        float eps, const SegTable& t) {
+  const float cv = h->clip_value;
+  const float lr0 = h->lr[0], lr1 = h->lr[1], wd0 = h->weight_decay[0], wd1 = h->weight_decay[1];
+  const int64_t window = (int64_t)blockDim.x * 4, stride = (int64_t)gridDim.x * window;
+  int k = 0;
+  for (int64_t lo = (int64_t)blockIdx.x * window; lo < n; lo += stride) {
+    const int64_t i = lo + (int64_t)threadIdx.x * 4;
+    if (!seg_inside(t, k, lo, lo + window, i)) continue;
+    const int64_t q = i >> 2;
+    float4 P = ((const float4*)p)[q], M = ((const float4*)m)[q], V = ((const float4*)v)[q];
+    const float4 G = ((const float4*)g)[q];
+    const bool d0 = i < n_decay, d1 = i + 1 < n_decay, d2 = i + 2 < n_decay, d3 = i + 3 < n_decay;
+    adamw_guarded_update<CLAMP>(P.x, G.x, M.x, V.x, coef, cv, d0 ? lr0 : lr1, d0 ? wd0 : wd1, b1, b2, eps, bc1, bc2_sqrt);
+    adamw_guarded_update<CLAMP>(P.y, G.y, M.y, V.y, coef, cv, d1 ? lr0 : lr1, d1 ? wd0 : wd1, b1, b2, eps, bc1, bc2_sqrt);
+    adamw_guarded_update<CLAMP>(P.z, G.z, M.z, V.z, coef, cv, d2 ? lr0 : lr1, d2 ? wd0 : wd1, b1, b2, eps, bc1, bc2_sqrt);
+    adamw_guarded_update<CLAMP>(P.w, G.w, M.w, V.w, coef, cv, d3 ? lr0 : lr1, d3 ? wd0 : wd1, b1, b2, eps, bc1, bc2_sqrt);
+    ((float4*)p)[q] = P; ((float4*)m)[q] = M; ((float4*)v)[q] = V;
+  }
+}
+
+// adamw_guarded_kernel on the quads inside a segment; nothing outside is loaded or stored
+__global__ __launch_bounds__(256) void adamw_guarded_seg_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                                float* __restrict__ m, float* __restrict__ v, int64_t n,
+                                                                int64_t n_decay, const svit_step_host* __restrict__ h,
+                                                                const svit_step_dev* __restrict__ d, float b1, float b2,
+                                                                float eps, const SegTable t) {
+  if (d->apply == 0) return;
+  const float coef = d->coef, bc1 = d->bc1, bc2_sqrt = d->bc2_sqrt;
+  if (h->clip_value > 0.f) adamw_guarded_seg_range<true>(p, g, m, v, n, n_decay, h, coef, bc1, bc2_sqrt, b1, b2, eps, t);
+  else adamw_guarded_seg_range<false>(p, g, m, v, n, n_decay, h, coef, bc1, bc2_sqrt, b1, b2, eps, t);
+}
+
+// host side of both: the table's checks (before any HIP call) and its copy into the kernel-argument form.
+// n_decay < 0: no weight-decay boundary to respect (the guard).
+static int seg_table_take(const int64_t* segs, int64_t S, int64_t n, int64_t n_decay, SegTable* out) {
+  if (!segs || S < 1 || S > SVIT_MAX_SEGS) return SVIT_ERR_ARG;
+  int64_t prev = 0;
+  for (int64_t s = 0; s < S; ++s) {
+    const int64_t b = segs[2 * s], e = segs[2 * s + 1];
+    if (b < prev || e <= b || e > n) return SVIT_ERR_ARG;                   // unsorted / overlapping, empty, past the buffer
+    if (n_decay >= 0 && b < n_decay && e > n_decay) return SVIT_ERR_ARG;    // straddles the weight-decay boundary
+    prev = e;
+  }
+  for (int64_t s = 0; s < 2 * S; ++s)
+    if (segs[s] & 3) return SVIT_ERR_ALIGN;
+  for (int64_t s = 0; s < SVIT_MAX_SEGS; ++s) {
+    out->v[s][0] = s < S ? segs[2 * s] : 0;
+    out->v[s][1] = s < S ? segs[2 * s + 1] : 0;
+  }
+  out->S = (int32_t)S;
+  return SVIT_OK;
+}
+
 inline unsigned grid_for(int64_t work_items, int block, unsigned cap = 8192) {
   int64_t b = (work_items + block - 1) / block;
   if (b < 1) b = 1;
@@ -967,6 +1064,43 @@ extern "C" int svit_adamw_step_guarded(float* p, const float* g, float* m, float
   if (((uintptr_t)host_rec | (uintptr_t)dev_rec) & 7) return SVIT_ERR_ALIGN;
   hipLaunchKernelGGL(adamw_guarded_kernel, dim3(grid_for(n >> 2, 256, 4096)), dim3(256), 0, (hipStream_t)stream,
                      p, g, m, v, n, n_decay, host_rec, dev_rec, beta1, beta2, eps);
+  SVIT_LAUNCH_CHECK();
+  return SVIT_OK;
+}
+
+extern "C" int svit_step_guard_seg(const float* g, int64_t n, const int64_t* segs, int64_t S,
+                                   const svit_step_host* host_rec, svit_step_dev* dev_rec, const float* bias_table,
+                                   int64_t table_entries, float* workspace, int64_t workspace_floats, void* stream) {
+  if (!g || !host_rec || !dev_rec || !workspace || n <= 0 || table_entries < 0 || (table_entries > 0 && !bias_table))
+    return SVIT_ERR_ARG;
+  SegTable t;
+  if (int rc = seg_table_take(segs, S, n, -1, &t)) return rc;
+  if ((uintptr_t)g & 15) return SVIT_ERR_ALIGN;
+  if (((uintptr_t)host_rec | (uintptr_t)dev_rec | (uintptr_t)bias_table) & 7) return SVIT_ERR_ALIGN;
+  unsigned blocks = grid_for((n + 3) / 4, 256, 1024);      // svit_sumsq's grid: the same partials, bit for bit
+  if ((int64_t)blocks > workspace_floats) blocks = (unsigned)workspace_floats;
+  if (blocks < 1) return SVIT_ERR_ARG;
+  hipLaunchKernelGGL(sumsq_seg_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, g, n, workspace, t);
+  SVIT_LAUNCH_CHECK();
+  hipLaunchKernelGGL(step_guard_final_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, workspace, (int)blocks,
+                     host_rec, dev_rec, (const float2*)bias_table, table_entries);
+  SVIT_LAUNCH_CHECK();
+  return SVIT_OK;
+}
+
+extern "C" int svit_adamw_step_guarded_seg(float* p, const float* g, float* m, float* v, int64_t n, int64_t n_decay,
+                                           const int64_t* segs, int64_t S, const svit_step_host* host_rec,
+                                           const svit_step_dev* dev_rec, float beta1, float beta2, float eps,
+                                           void* stream) {
+  if (!p || !g || !m || !v || !host_rec || !dev_rec || n <= 0 || n_decay < 0 || n_decay > n) return SVIT_ERR_ARG;
+  SegTable t;
+  if (int rc = seg_table_take(segs, S, n, n_decay, &t)) return rc;
+  if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) return SVIT_ERR_ALIGN;
+  if (((uintptr_t)host_rec | (uintptr_t)dev_rec) & 7) return SVIT_ERR_ALIGN;
+  // the segments' extent decides the grid: a head-only step does not launch 4096 workgroups to find 140 of them busy
+  const int64_t span = t.v[S - 1][1];
+  hipLaunchKernelGGL(adamw_guarded_seg_kernel, dim3(grid_for(span >> 2, 256, 4096)), dim3(256), 0, (hipStream_t)stream,
+                     p, g, m, v, span, n_decay, host_rec, dev_rec, beta1, beta2, eps, t);
   SVIT_LAUNCH_CHECK();
   return SVIT_OK;
 }

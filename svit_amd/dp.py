@@ -13,6 +13,8 @@ import torch
 import torch.distributed as dist
 import torch.nn as nn
 
+from . import freeze
+
 RankRole = collections.namedtuple("RankRole", "is_image data_rank replicas batch_size dataset")
 
 
@@ -66,6 +68,7 @@ class DataParallel(nn.Module):
         self.force_collectives = bool(force_collectives) and dist.is_initialized()
         self._works = []
         self._pending = []
+        self._bytes, self.exchanged_bytes = 0, 0    # gradient bytes handed to collectives: this step so far / the last step
         module._grad_ready_hook = self._on_ready
         module._grad_ready_ranks = self.launch_ranks()
         if self.world_size > 1 or self.force_collectives:
@@ -82,6 +85,7 @@ class DataParallel(nn.Module):
     # ------------------------------------------------------------------ gradient exchange ---
     def _reduce_slice(self, a, b):
         g = self.module.flat.grad[a:b]
+        self._bytes += 4 * (b - a)
         backend = dist.get_backend(self.process_group)
         if self.average and backend == "nccl":
             op = dist.ReduceOp.AVG
@@ -101,7 +105,10 @@ class DataParallel(nn.Module):
         if self.world_size == 1 and not self.force_collectives:
             return
         flat = self.module.flat
-        self._pending.extend(flat.ready_ranges[rank])
+        ranges = flat.ready_ranges[rank]
+        if getattr(self.module, "_cut", 0):    # frozen parameters (svit_amd/freeze.py): their gradients are zero everywhere, nothing to exchange
+            ranges = freeze.intersect(ranges, self.module.trainable_segments())
+        self._pending.extend(ranges)
         last = rank == flat.n_ranks - 1
         if (rank + 1) % self.bucket_ranks == 0 or last:
             # merge adjacent slices, then launch one collective per contiguous slice
@@ -115,6 +122,7 @@ class DataParallel(nn.Module):
             for a, b in merged:
                 self._reduce_slice(a, b)
         if last:
+            self.exchanged_bytes, self._bytes = self._bytes, 0
             self.finish()
 
     def finish(self):

@@ -34,28 +34,34 @@ class FlatParams:
     """One fp32 buffer for all parameters ([decayed | not decayed]), one for their grads, a bf16
     mirror for GEMM operands and a bf16 buffer of transposed Linear weights for dgrad."""
 
-    def __init__(self, shapes, decay_of, device, rank_of):
+    @staticmethod
+    def layout(shapes, decay_of, rank_of):
+        """The placement alone (no memory): (order, slots, n_decay, ready_ranges, total, depth)."""
         names = list(shapes)
         depth = 1 + max([int(n.split(".")[1]) for n in names if n.startswith("blocks.")] or [0])
         ranks = {n: rank_of(n, depth) for n in names}
         # [decayed | not decayed]; inside each group in gradient-readiness order
         order = sorted(names, key=lambda n: (not decay_of(n, shapes[n]), ranks[n]))
-        self.slots, off = {}, 0
-        self.n_decay = 0
-        self.n_ranks = depth + 2
+        slots, off, n_decay = {}, 0, 0
         # ready_ranges[r] = list of (begin, end) slices of the flat buffer final after rank r
-        self.ready_ranges = [[] for _ in range(self.n_ranks)]
+        ready_ranges = [[] for _ in range(depth + 2)]
         for n in order:
             numel = int(math.prod(shapes[n]))
-            self.slots[n] = (off, numel, tuple(shapes[n]))
-            rr = self.ready_ranges[ranks[n]]
+            slots[n] = (off, numel, tuple(shapes[n]))
+            rr = ready_ranges[ranks[n]]
             if rr and rr[-1][1] == off:
                 rr[-1] = (rr[-1][0], off + _align(numel))
             else:
                 rr.append((off, off + _align(numel)))
             off += _align(numel)
             if decay_of(n, shapes[n]):
-                self.n_decay = off
+                n_decay = off
+        return order, slots, n_decay, ready_ranges, off, depth
+
+    def __init__(self, shapes, decay_of, device, rank_of):
+        names = list(shapes)
+        order, self.slots, self.n_decay, self.ready_ranges, off, depth = self.layout(shapes, decay_of, rank_of)
+        self.n_ranks = depth + 2
         self.total = off
         self.data = torch.zeros(off, device=device, dtype=F32)
         self.grad = torch.zeros(off, device=device, dtype=F32)
@@ -332,8 +338,11 @@ class Engine:
         return out
 
     # ------------------------------------------------------------------ forward ----------
-    def forward(self, video, drop_scales=None, save=True):
-        """video f32 [B,3,Tx,S,S] (or U8Clips / AugClips / FramesView) -> (normed tokens f32 [B,N_last,C_last], saved-state dict)."""
+    def forward(self, video, drop_scales=None, save=True, cut=0):
+        """video f32 [B,3,Tx,S,S] (or U8Clips / AugClips / FramesView) -> (normed tokens f32 [B,N_last,C_last], saved-state dict).
+        cut (svit_amd/freeze.py): the lowest trainable network position.  Block i saves its activations only when
+        1 + i >= cut -- the backward stops above the frozen blocks -- and the stem's im2col operand is kept only for
+        cut 0.  What a pass computes does not depend on what it keeps."""
         plan, f = self.plan, self.flat
         if isinstance(video, U8Clips):       # decoded uint8 frames + crop table (svit_amd/input.py)
             cols, (To, Ho, Wo) = ops.im2col_patch_u8(video)
@@ -357,14 +366,21 @@ class Engine:
                     out=x.view(B * N, C), remap=(L, N, 1))
         ops.fill_special_tokens(x, f.p("cls_token"), f.p("object_queries"),
                                 f.p("pos_embed_temporal"), L, Tx, plan.objects, Tx > 1)
-        st = {"B": B, "Tx": Tx, "n_obj": n_obj, "L0": L, "cols": cols if save else None,
-              "blocks": []}
+        st = {"B": B, "Tx": Tx, "n_obj": n_obj, "L0": L, "cols": cols if save and cut == 0 else None,
+              "blocks": [], "cut": cut}
         thw = (T, Ho, Wo)
         self._interp_tables(thw, save)
         hip.mark("stem")
         for blk in plan.blocks:
             ds = drop_scales[blk.index] if drop_scales is not None else None
-            x, thw, sv = self._block_fwd(blk, x, thw, n_obj, ds, save)
+            keep = save and 1 + blk.index >= cut
+            # a frozen block under REPRODUCIBLE: only the shapes of its weight-gradient GEMMs, for the plan of the launch
+            # the full backward would share between it and the lowest trainable block (backward())
+            shapes = (self._tn_shapes(blk, x.shape[0], x.shape[1], thw, n_obj)
+                      if save and not keep and self.reproducible and not self.deterministic else None)
+            x, thw, sv = self._block_fwd(blk, x, thw, n_obj, ds, keep)
+            if shapes is not None:
+                sv = {"tn_shapes": shapes}
             st["blocks"].append(sv)
             hip.mark("fwd%d" % blk.index)
         y16, y32, mean, rstd = ops.layernorm_fwd(x, f.p("norm.weight"), f.p("norm.bias"),
@@ -376,6 +392,26 @@ class Engine:
         # or in `save`; two saved forwards of one geometry with a weight update between them would share the operand).
         self._interp_out = {}
         return y32, st
+
+    def _tn_shapes(self, blk, B, N, thw, n_obj):
+        """(M, N, K, has_bias) of the weight-gradient GEMMs _block_bwd queues for this block, in its order"""
+        f = self.flat
+        pre = "blocks.%d." % blk.index
+        sq, skv = blk.stride_q[1], blk.stride_kv[1]
+        q_thw = (thw[0], arch.pooled(thw[1], sq), arch.pooled(thw[2], sq))
+        k_thw = (thw[0], arch.pooled(thw[1], skv), arch.pooled(thw[2], skv))
+        Nq = 1 + q_thw[0] * q_thw[1] * q_thw[2] + n_obj
+        hid, Co = f.slots[pre + "mlp.fc1.weight"][2]
+        C = f.slots[pre + "attn.qkv.weight"][2][1]
+        M, Mq = B * N, B * Nq
+        out = [(Mq, Co, hid, True), (Mq, hid, Co, True), (Mq, Co, Co, True)]         # fc2, fc1, attn.proj
+        for a, m in zip("hwt", self._rel(blk, q_thw, k_thw)[1]):
+            if m is None:       # (an interpolated table's gradient is a stand-alone GEMM, not queued)
+                out.append((B * blk.heads * Nq, f.slots[pre + "attn.rel_pos_" + a][2][0], HD, False))
+        out.append((M, 3 * Co, C, True))                                              # qkv
+        if blk.has_proj:
+            out.append((M, Co, C, True))
+        return out
 
     def _block_fwd(self, blk, x, thw, n_obj, ds, save):
         f = self.flat
@@ -462,6 +498,17 @@ class Engine:
                 on_ready(rank)
         plan, f = self.plan, self.flat
         depth = len(plan.blocks)
+        # frozen parameters: the pass stops at the lowest trainable block `lo` (cut 0: block 0, and then the stem)
+        cut = st.get("cut", 0)
+        lo = max(cut - 1, 0)
+        if cut > depth:       # every block is frozen: the final LayerNorm's d(gamma) / d(beta) and nothing else
+            if cut == depth + 1:
+                ops.layernorm_bwd(dy.contiguous(), st["x_last"], f.p("norm.weight"), st["mean"], st["rstd"],
+                                  f.g("norm.weight"), f.g("norm.bias"), want_bf16=False,
+                                  rows_per_sample=st["x_last"].shape[1])
+            for rank in range(depth + 2):
+                ready(rank)
+            return
         last = st["blocks"][depth - 1]
         dx, dx16 = ops.layernorm_bwd(dy.contiguous(), st["x_last"], f.p("norm.weight"), st["mean"],
                                      st["rstd"], f.g("norm.weight"), f.g("norm.bias"),
@@ -469,14 +516,14 @@ class Engine:
                                      rows_per_sample=st["x_last"].shape[1])
         ready(0)
         hip.mark("bwd_norm")
-        for blk in reversed(plan.blocks):
-            below = st["blocks"][blk.index - 1] if blk.index > 0 else None
+        for blk in reversed(plan.blocks[lo:]):
+            below = st["blocks"][blk.index - 1] if blk.index > lo else None
             try:
                 # second-stage reductions: queued per group of RED_GROUP blocks, one launch when the group's last block is done
                 G = self.RED_GROUP
                 dx, dx16 = self._block_bwd(blk, st["blocks"][blk.index], dx, dx16, st["n_obj"], below,
                                            red_begin=blk.index % G == G - 1 or blk.index == depth - 1,
-                                           red_end=blk.index % G == 0, red_slot=blk.index % G)
+                                           red_end=blk.index % G == 0 or blk.index == lo, red_slot=blk.index % G)
             except BaseException:
                 # a failed launch / allocation inside the bracket: the queued second-stage
                 # reductions and weight-gradient GEMMs hold pointers into this step's scratch
@@ -485,6 +532,21 @@ class Engine:
                 raise
             hip.mark("bwd%d" % blk.index)
             ready(1 + (depth - 1 - blk.index))
+        if cut > 0:     # nothing below needs a gradient: the ranks of the frozen positions are final as they are
+            # The queued weight-gradient GEMMs of the lowest trainable blocks: the full backward would go on queueing
+            # those of the blocks below until more than 8 wait (_flush_tn), and under REPRODUCIBLE the planner cuts all
+            # problems of a launch by one step count -- so the launch is planned with the shapes of what would follow
+            behind = []
+            if self._tn and self.reproducible and not self.deterministic:
+                for j in range(lo - 1, -1, -1):
+                    behind += st["blocks"][j]["tn_shapes"]
+                    if len(self._tn) + len(behind) > 8:
+                        break
+            self._flush_tn(behind=behind)
+            self._join()
+            for rank in range(1 + (depth - lo), depth + 2):
+                ready(rank)
+            return
         # block-0 input: [cls | patches | objects]
         B, Tx, L, O, C = st["B"], st["Tx"], st["L0"], plan.objects, plan.embed_dim
         ops.special_token_grads(dx, f.g("cls_token"), f.g("object_queries"),
@@ -544,9 +606,10 @@ class Engine:
             self._side_keep.clear()
             self._side_active = False
 
-    def _flush_tn(self, force=True):
+    def _flush_tn(self, force=True, behind=()):
         """queued weight-gradient GEMMs in one grouped launch (ops.gemm_tn_grouped).  Two blocks
-        share a launch (<= 16 problems): the machine-wide accumulator flush is paid half as often."""
+        share a launch (<= 16 problems): the machine-wide accumulator flush is paid half as often.
+        behind (REPRODUCIBLE, a backward cut short): shapes of the problems that would follow in this launch."""
         if not force and len(self._tn) <= 8:
             return
         q, self._tn = self._tn, []
@@ -556,7 +619,10 @@ class Engine:
         if self.reproducible and not det:
             # all queued weight-gradient work of a step sits on one stream (the side stream when overlap_wgrad is on):
             # one slab workspace serves every flush
-            self._fork(lambda: ops.gemm_tn_grouped_slab(q, tag="tn_slab_queue"), q)
+            if behind:
+                self._fork(lambda: ops.gemm_tn_grouped_slab_lead(q, behind, tag="tn_slab_queue"), q)
+            else:
+                self._fork(lambda: ops.gemm_tn_grouped_slab(q, tag="tn_slab_queue"), q)
             return
         self._fork(lambda: ops.gemm_tn_grouped(q, ordered=det), q)
 

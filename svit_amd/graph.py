@@ -109,6 +109,15 @@ class GraphedTrainStep:
             raise hip.SvitHipError("GraphedTrainStep needs a finalized (on-GPU) SViT")
         if not self.core.training:
             raise RuntimeError("GraphedTrainStep captures the training step: call model.train() first")
+        # frozen parameters (svit_amd/freeze.py): the flags are read HERE; the capture saves, back-propagates, exchanges and
+        # steps for this cut only, so `__call__` refuses a replay once a flag has changed
+        self.cut = self.core.frozen_cut()
+        self._flag_params = list(self.core.parameters())
+        self._flags = [p.requires_grad for p in self._flag_params]
+        if optimizer is not None and optimizer.cut != self.cut:
+            raise hip.SvitHipError("GraphedTrainStep(optimizer=...): the optimizer was built when the parameters' "
+                                   "requires_grad flags froze everything below position %d, now they say %d -- rebuild "
+                                   "the optimizer" % (optimizer.cut, self.cut))
         self.loss_fun = loss_fun
         self.dp = model if hasattr(model, "_on_ready") and (getattr(model, "world_size", 1) > 1 or
                                                            getattr(model, "force_collectives", False)) else None
@@ -178,7 +187,8 @@ class GraphedTrainStep:
         ds = core.sample_drop_scales(x.shape[0], x.device, Tx=Tx)      # (+ the head's dropout factors: one launch)
         head_keep, core._head_keep = core._head_keep, None
         with torch.no_grad():
-            y, st = eng.forward(x, ds, save=True)
+            # (the head alone trainable: nothing is kept, and backward() below only reports the ranks)
+            y, st = eng.forward(x, ds, save=self.cut <= len(core.plan.blocks) + 1, cut=self.cut)
         n_obj = Tx * core.O
         frames_out = None
         if self.frames_pass and Tx > 1:
@@ -301,8 +311,15 @@ class GraphedTrainStep:
         self._side = torch.cuda.Stream(device=dev)
 
     # ------------------------------------------------------------------------------------------
+    def check_flags(self):
+        """refuse a replay after a `requires_grad` flag has changed: the capture holds the old cut's launches"""
+        if [p.requires_grad for p in self._flag_params] != self._flags:
+            raise hip.SvitHipError("a parameter's requires_grad changed after this GraphedTrainStep was captured (it "
+                                   "froze everything below position %d): rebuild the optimizer and the step" % self.cut)
+
     def check_batch(self, inputs):
         """refuse a batch the capture does not fit (before anything is enqueued)"""
+        self.check_flags()
         x = inputs[0]
         if x.shape != self.x.shape:
             raise hip.SvitHipError("GraphedTrainStep was captured for input %s, got %s"
@@ -434,6 +451,10 @@ class AccumulatedTrainStep:
             if ms.dp is not self.dp:
                 raise hip.SvitHipError("micro-step %d and the AccumulatedTrainStep disagree about the data-parallel "
                                        "wrapper: build both over the same DataParallel (or both over the bare model)" % i)
+            if ms.cut != optimizer.cut:
+                raise hip.SvitHipError("micro-step %d was captured with everything below position %d frozen, the "
+                                       "optimizer with %d: rebuild them over the same requires_grad flags"
+                                       % (i, ms.cut, optimizer.cut))
         self.optimizer = optimizer
         self.meter = meter
         if meter is not None:
@@ -452,6 +473,7 @@ class AccumulatedTrainStep:
             raise RuntimeError("AccumulatedTrainStep runs the training step: call model.train() first")
         if len(batches) != self.k:
             raise hip.SvitHipError("AccumulatedTrainStep holds %d micro-steps, got %d batches" % (self.k, len(batches)))
+        self.micro_steps[0].check_flags()       # (every micro-step holds the optimizer's cut)
         for i, (ms, b) in enumerate(zip(self.micro_steps, batches)):
             if _is_feeder(b):
                 if b.target is not ms.x:
@@ -544,6 +566,10 @@ class GraphedEvalStep:
         if core.training:
             raise hip.SvitHipError("GraphedEvalStep captures the evaluation step: call model.eval() first (the training "
                                    "step is graph.GraphedTrainStep)")
+        try:        # an unsupported pattern of requires_grad flags is refused here as well; evaluation itself ignores the flags
+            core.frozen_cut()
+        except ValueError:
+            pass    # (nothing trainable: an evaluation needs no optimizer)
         if val_meter is not None and cfg is None:
             raise hip.SvitHipError("GraphedEvalStep(val_meter=...) needs cfg=: the validation losses are built from it")
         dev = inputs[0].device

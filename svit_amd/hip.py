@@ -151,6 +151,7 @@ _SIGS = {
     "svit_gemm_tn_grouped_ex": (i32, [C.POINTER(TnProblem), i32, i32, vp]),
     "svit_gemm_tn_grouped_slab": (i32, [C.POINTER(TnProblem), i32, vp, i64, vp]),
     "svit_gemm_tn_grouped_workspace": (i64, [C.POINTER(TnProblem), i32]),
+    "svit_gemm_tn_grouped_slab_lead": (i32, [C.POINTER(TnProblem), i32, i32, vp, i64, vp]),
     "svit_colsum_bf16": (i32, [vp, i32, vp, i32, i32, vp]),
     "svit_cast_f32_bf16": (i32, [vp, vp, i64, vp]),
     "svit_table_interp": (i32, [vp, i32, i32, vp, vp, vp, vp]),
@@ -206,6 +207,8 @@ _SIGS = {
     "svit_adamw_bias_table": (i32, [f32, f32, vp, i64, C.POINTER(i64)]),       # host only: no stream argument
     "svit_step_guard": (i32, [vp, i64, vp, vp, vp, i64, vp, i64, vp]),
     "svit_adamw_step_guarded": (i32, [vp, vp, vp, vp, i64, i64, vp, vp, f32, f32, f32, vp]),
+    "svit_step_guard_seg": (i32, [vp, i64, vp, i64, vp, vp, vp, i64, vp, i64, vp]),
+    "svit_adamw_step_guarded_seg": (i32, [vp, vp, vp, vp, i64, i64, vp, i64, vp, vp, f32, f32, f32, vp]),
     "svit_head_fwd": (i32, [C.POINTER(HeadArgs), vp]),
     "svit_head_bwd": (i32, [C.POINTER(HeadBwdArgs), vp]),
     "svit_head_eval": (i32, [C.POINTER(HeadArgs), i32, vp]),

@@ -15,7 +15,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import arch, hip, ops
+from . import arch, freeze, hip, ops
 from .engine import Engine, FlatParams
 
 
@@ -58,10 +58,10 @@ class _Backbone(torch.autograd.Function):
     into the flat grad buffer that every `param.grad` is a view of."""
 
     @staticmethod
-    def forward(ctx, model, video, drop_scales, need_grad, anchor):
+    def forward(ctx, model, video, drop_scales, need_grad, anchor, cut):
         with torch.no_grad():
-            y, st = model.engine.forward(video, drop_scales, save=need_grad)
-        ctx.model, ctx.st = model, (st if need_grad else None)
+            y, st = model.engine.forward(video, drop_scales, save=need_grad, cut=cut)
+        ctx.model, ctx.st, ctx.cut = model, (st if need_grad else None), cut
         return y
 
     @staticmethod
@@ -69,12 +69,33 @@ class _Backbone(torch.autograd.Function):
         model = ctx.model
         if ctx.st is None:
             raise RuntimeError("backward through an SViT forward that was run without grad")
-        model._attach_grads()
+        model._attach_grads(ctx.cut)
         with torch.no_grad():
             model.engine.backward(ctx.st, dy, on_ready=model._grad_ready_hook,
                                   ready_ranks=model._grad_ready_ranks)
         ctx.st = None
-        return None, None, None, None, None
+        return None, None, None, None, None, None
+
+
+class _Adopt(torch.autograd.Function):
+    """Head-only training (everything below the head frozen): the backbone runs outside autograd, and this identity
+    node under the head takes over the two duties of the backbone's backward that remain -- adopting the head's
+    gradients into the flat buffer and telling the gradient-ready hook that every rank is final."""
+
+    @staticmethod
+    def forward(ctx, model, tokens, anchor, cut):
+        ctx.model, ctx.cut = model, cut
+        return tokens.view_as(tokens)
+
+    @staticmethod
+    def backward(ctx, dtok):
+        model = ctx.model
+        model._attach_grads(ctx.cut)
+        hook = model._grad_ready_hook
+        if hook is not None:
+            for rank in range(model.flat.n_ranks):
+                hook(rank)
+        return None, None, None, None
 
 
 class _HeadFn(torch.autograd.Function):
@@ -201,7 +222,9 @@ class SViT(nn.Module):
         self._grad_ready_ranks = None  # ranks at which that hook launches collectives
         self._anchor = None
         self._keep = None
-        self._grad_views = None
+        self._grad_views = None     # (cut, [(parameter, its view of the flat grad buffer)]) of the trainable parameters
+        self._cut = 0               # svit_amd/freeze.py: lowest trainable network position, as the last pass read the flags
+        self._seg_cache = {}
 
     # -- parameters are registered under the reference's dotted names ---------------------------
     def _register(self, name, tensor):
@@ -265,18 +288,60 @@ class SViT(nn.Module):
         # opt-in, not a key of the default tree (like SVIT.CONSISTENCY's reader): bit-reproducible weight gradients
         self.engine.reproducible = bool(getattr(self.cfg.SVIT, "REPRODUCIBLE", False))
         self._grad_views = None
+        self._seg_cache = {}
         self._anchor = torch.zeros((), device=dev, requires_grad=True)
         return self
 
-    def _attach_grads(self):
-        """Make every `.grad` a view of the flat grad buffer before the engine accumulates into
-        it.  Called at the start of the backbone's backward, i.e. after the (tiny) head has
+    # -- frozen parameters (svit_amd/freeze.py) -----------------------------------------------------
+    def freeze_below(self, cut):
+        """Freeze every parameter at a network position below `cut` and unfreeze the rest: position 0 is the stem
+        (patch_embed.proj.*, cls_token, object_queries, pos_embed_temporal), 1 + i block i, depth + 1 the final norm,
+        depth + 2 the head.  0 = nothing frozen.  Only sets `requires_grad`: the flags are the truth, read when an
+        optimizer or a captured step is built and at each eager training forward."""
+        depth = len(self.plan.blocks)
+        cut = int(cut)
+        if not 0 <= cut <= depth + 2:
+            raise ValueError("freeze_below: cut %d outside 0..%d" % (cut, depth + 2))
+        for n, p in self.named_parameters():
+            p.requires_grad_(freeze.position(n, depth) >= cut)
+        return self
+
+    def frozen_cut(self):
+        """The cut the parameters' `requires_grad` flags describe now (0 = nothing frozen); NotImplementedError for a
+        pattern that is not "everything below a cut", ValueError when nothing is trainable.  Remembered as the cut of
+        the pass that follows (the gradient views, the head's backward)."""
+        self._cut = freeze.model_cut(self)
+        return self._cut
+
+    def trainable_segments(self, cut=None):
+        """int64 numpy [S, 2]: the ranges of the flat buffers that hold trainable parameters under `cut`"""
+        cut = self._cut if cut is None else cut
+        segs = self._seg_cache.get(cut)
+        if segs is None:
+            depth = len(self.plan.blocks)
+            names = freeze.trainable_names([n for n, _ in self.named_parameters()], depth, cut)
+            segs = self._seg_cache[cut] = freeze.segments(self.flat.slots, self.flat.n_decay, names)
+        return segs
+
+    def _attach_grads(self, cut=None):
+        """Make every trainable parameter's `.grad` a view of the flat grad buffer before the engine accumulates
+        into it (a frozen parameter keeps `grad is None`, its range of the buffer stays zero).  Called at the start
+        of the backbone's backward, i.e. after the (tiny) head has
         already back-propagated through ordinary autograd: grads it produced into fresh tensors
         (after `optimizer.zero_grad()` dropped ours, tools/train_net.py:133) are adopted."""
         flat = self.flat
-        if self._grad_views is None:
-            self._grad_views = [(p, flat.g(n)) for n, p in self.named_parameters()]
-        views = self._grad_views
+        cut = self._cut if cut is None else cut
+        if self._grad_views is None or self._grad_views[0] != cut:
+            depth = len(self.plan.blocks)
+            if cut > 0:     # the flags changed: what earlier steps left in the ranges frozen now goes
+                for n, p in self.named_parameters():
+                    if freeze.position(n, depth) < cut:
+                        p.grad = None
+                for a, b in freeze.complement(self.trainable_segments(cut), flat.total):
+                    flat.grad[a:b].zero_()
+            self._grad_views = (cut, [(p, flat.g(n)) for n, p in self.named_parameters()
+                                      if freeze.position(n, depth) >= cut])
+        views = self._grad_views[1]
         fresh = views[0][0].grad is not views[0][1]
         if fresh:
             flat.grad.zero_()
@@ -362,7 +427,16 @@ class SViT(nn.Module):
         if drop_scales is None:
             drop_scales = self.sample_drop_scales(x.shape[0], x.device, Tx=Tx)
         need_grad = torch.is_grad_enabled()
-        tokens = _Backbone.apply(self, x, drop_scales, need_grad, self._anchor)
+        try:
+            cut = self.frozen_cut() if need_grad else 0   # the flags are read at every pass that may be differentiated
+        except ValueError:      # nothing trainable: nothing to differentiate, as with any torch module (no optimizer exists)
+            need_grad, cut = False, 0
+        if not need_grad:
+            tokens = _Backbone.apply(self, x, drop_scales, False, None, 0)
+        elif cut > len(self.plan.blocks) + 1:     # the head alone is trainable: autograd never enters the backbone
+            tokens = _Adopt.apply(self, _Backbone.apply(self, x, drop_scales, False, None, cut), self._anchor, cut)
+        else:
+            tokens = _Backbone.apply(self, x, drop_scales, need_grad, self._anchor, cut)
         n_obj = Tx * self.O
         if self.training and self.fused_head:
             return self.head_train(tokens, Tx, dropout_keep)
@@ -378,6 +452,9 @@ def build_model(cfg, gpu_id=None):
     else:
         assert cfg.NUM_GPUS == 0, "Cuda is not available. Please set `NUM_GPUS: 0 for running on CPUs."
     model = MODEL_REGISTRY.get(cfg.MODEL.MODEL_NAME)(cfg)
+    # opt-in, not a key of the default tree (like SVIT.REPRODUCIBLE): freeze everything below a network position
+    if getattr(cfg.SVIT, "FREEZE_BELOW", 0):
+        model.freeze_below(cfg.SVIT.FREEZE_BELOW)
     if cfg.NUM_GPUS:
         cur_device = torch.cuda.current_device() if gpu_id is None else gpu_id
         model = model.cuda(device=cur_device)

@@ -243,6 +243,25 @@ def gemm_tn_grouped_slab(problems, ws=None, tag="tn_slab"):
         hip.call("svit_gemm_tn_grouped_slab", arr, n, ptr(ws), ws.numel(), meta=("flop", flop))
 
 
+def gemm_tn_grouped_slab_lead(problems, shapes_behind, tag="tn_slab"):
+    """gemm_tn_grouped_slab of `problems` planned as the head of a longer list (svit_gemm_tn_grouped_slab_lead):
+    shapes_behind = [(M, N, K, has_bias)] of the problems that would follow them in the same call.  Only their shapes
+    enter the plan; `problems` then get the row splits, and the bits, they have in the call over the whole list."""
+    n, m = len(problems), len(shapes_behind)
+    if m == 0:
+        return gemm_tn_grouped_slab(problems, tag=tag)
+    real, flop = _tn_problem_array(problems)
+    arr = (hip.TnProblem * (n + m))()
+    for i in range(n):
+        arr[i] = real[i]
+    for j, (M, N, K, has_bias) in enumerate(shapes_behind):      # (addresses that pass the checks and are never followed)
+        t = arr[n + j]
+        t.A, t.B, t.dW, t.dbias = 1 << 20, 2 << 20, 3 << 20, (4 << 20) if has_bias else None
+        t.lda, t.ldb, t.lddw, t.M, t.N, t.K = -(-N // 8) * 8, -(-K // 8) * 8, K, M, N, K
+    ws = _tn_slab_buffer(problems[0][2].device, tag, gemm_tn_slab_workspace(arr, n + m))
+    hip.call("svit_gemm_tn_grouped_slab_lead", arr, n + m, n, ptr(ws), ws.numel(), meta=("flop", flop))
+
+
 def reduce_defer(on):
     """queue (1) / run (0) the second-stage reduce launches of the backward kernels"""
     hip.call("svit_reduce_defer", int(on))
@@ -907,6 +926,36 @@ def adamw_step_guarded(p, g, m, v, n_decay, host_rec, dev_rec, beta1, beta2, eps
         raise hip.SvitHipError("adamw_step_guarded: p, g, m, v differ in size")
     hip.call("svit_adamw_step_guarded", ptr(p), ptr(g), ptr(m), ptr(v), n, n_decay, ptr(host_rec), ptr(dev_rec),
              beta1, beta2, eps)
+
+
+def _chk_segs(segs):
+    """the segment table of the `_seg` tail: a C-contiguous int64 numpy [S, 2] on the host (the library checks its contents)"""
+    import numpy as np
+    if not (isinstance(segs, np.ndarray) and segs.dtype == np.int64 and segs.ndim == 2 and segs.shape[1] == 2
+            and segs.flags["C_CONTIGUOUS"]):
+        raise hip.SvitHipError("the segment table is a C-contiguous int64 numpy array [S, 2]")
+    return segs.ctypes.data, segs.shape[0]
+
+
+def step_guard_seg(g, segs, host_rec, dev_rec, table, workspace):
+    """step_guard over the segments of g only (svit_step_guard_seg): what lies outside is neither read nor counted"""
+    _chk_dev(g, table, workspace)
+    _chk_step_records(host_rec, dev_rec, g.device)
+    sp, S = _chk_segs(segs)
+    hip.call("svit_step_guard_seg", ptr(g), g.numel(), sp, S, ptr(host_rec), ptr(dev_rec), ptr(table), table.shape[0],
+             ptr(workspace), workspace.numel())
+
+
+def adamw_step_guarded_seg(p, g, m, v, n_decay, segs, host_rec, dev_rec, beta1, beta2, eps):
+    """adamw_step_guarded on the elements inside the segments (svit_adamw_step_guarded_seg); nothing else is touched"""
+    _chk_dev(p, g, m, v)
+    _chk_step_records(host_rec, dev_rec, p.device)
+    n = p.numel()
+    if g.numel() != n or m.numel() != n or v.numel() != n:
+        raise hip.SvitHipError("adamw_step_guarded_seg: p, g, m, v differ in size")
+    sp, S = _chk_segs(segs)
+    hip.call("svit_adamw_step_guarded_seg", ptr(p), ptr(g), ptr(m), ptr(v), n, n_decay, sp, S, ptr(host_rec),
+             ptr(dev_rec), beta1, beta2, eps)
 
 
 # ---------------------------------------------------------------- head (K15) ----------------

@@ -14,7 +14,7 @@ import math
 import numpy as np
 import torch
 
-from . import hip, ops
+from . import freeze, hip, ops
 
 
 def get_lr_at_epoch(cfg, cur_epoch):
@@ -38,7 +38,11 @@ def get_lr_at_epoch(cfg, cur_epoch):
 
 class FusedClipAdamW:
     """torch.optim-like surface (`param_groups`, `zero_grad`, `step`, `state_dict`) over the
-    model's FlatParams.  Semantics = clip_grad_norm_(max_norm) + torch.optim.AdamW(eps=1e-8)."""
+    model's FlatParams.  Semantics = clip_grad_norm_(max_norm) + torch.optim.AdamW(eps=1e-8).
+
+    Parameters with `requires_grad = False` (read here, once: svit_amd/freeze.py) are left out as the reference leaves
+    them out (slowfast/models/optimizer.py:39-76): never decayed, no moments, not in the clip norm, not in
+    `state_dict()`.  The kernels then run on `segments`, the trainable ranges of the flat buffers."""
 
     def __init__(self, model, lr, weight_decay=1e-4, betas=(0.9, 0.999), eps=1e-8,
                  clip_grad_l2norm=None, grad_scale=1.0):
@@ -46,6 +50,10 @@ class FusedClipAdamW:
         self.model, self.flat = core, core.flat
         if self.flat is None:
             raise RuntimeError("FusedClipAdamW needs a finalized (on-GPU) SViT")
+        # the frozen set the flags describe: NotImplementedError for an unsupported pattern, ValueError for none trainable
+        # (a bare holder of flat buffers, as tools and tests build one, has no flags to read: nothing frozen)
+        self.cut = core.frozen_cut() if hasattr(core, "frozen_cut") else 0
+        self.segments = core.trainable_segments(self.cut) if self.cut else None
         self.betas, self.eps = betas, eps
         self.clip = clip_grad_l2norm
         self.grad_scale = grad_scale
@@ -72,14 +80,19 @@ class FusedClipAdamW:
         if self.clip is not None and self.clip > 0:
             self.sumsq.zero_()
             ops.sumsq(f.grad, self.sumsq)
-            sumsq = self.sumsq
-        for g in self.param_groups:
-            a, b = g["range"]
-            if b <= a:
-                continue
+            sumsq = self.sumsq      # (over the whole buffer also with frozen parameters: their gradients are zero)
+        for g, a, b in self._launches():
             ops.adamw_step(f.data[a:b], f.grad[a:b], self.exp_avg[a:b], self.exp_avg_sq[a:b], sumsq,
                            float(self.clip or 0.0), g["lr"], self.betas[0], self.betas[1], self.eps,
                            g["weight_decay"], self.step_count, self.grad_scale)
+
+    def _launches(self):
+        """(param group, begin, end) of the AdamW launches of a step: one per weight-decay group, or -- with frozen
+        parameters -- one per trainable segment (a segment never crosses the groups' boundary)"""
+        if self.segments is None:
+            return [(g,) + tuple(g["range"]) for g in self.param_groups if g["range"][1] > g["range"][0]]
+        nd = self.flat.n_decay
+        return [(self.param_groups[0 if a < nd else 1], int(a), int(b)) for a, b in self.segments]
 
     def grad_norm(self):
         """host value of the last clipped step's global grad norm (forces a sync; logging only)."""
@@ -90,6 +103,9 @@ class FusedClipAdamW:
         """state index -> parameter name: the reference's two groups (decayed, then 1-D / bias;
         slowfast/models/optimizer.py:39-72), each in named_parameters() order."""
         named = [(n, tuple(p.shape)) for n, p in self.model.named_parameters()]
+        if self.cut:        # the reference's optim_params: the trainable parameters alone
+            depth = len(self.model.plan.blocks)
+            named = [(n, s) for n, s in named if freeze.position(n, depth) >= self.cut]
         wd = self.model.weight_decayed       # same predicate that laid out the flat buffers
         dec = [n for n, s in named if wd(n, s)]
         return dec, [n for n, s in named if not wd(n, s)]
@@ -197,6 +213,11 @@ class GuardedClipAdamW(FusedClipAdamW):
         rec = torch.zeros(12, dtype=torch.int32, device=dev)
         ops.step_guard(z[1], self.host_rec, rec, self.bias_table, self._ws)
         ops.adamw_step_guarded(z[0], z[1], z[2], z[3], 2, self.host_rec, rec, self.betas[0], self.betas[1], self.eps)
+        if self.segments is not None:
+            seg = np.array([[0, 4]], dtype=np.int64)
+            ops.step_guard_seg(z[1], seg, self.host_rec, rec, self.bias_table, self._ws)
+            ops.adamw_step_guarded_seg(z[0], z[1], z[2], z[3], 4, seg, self.host_rec, rec, self.betas[0], self.betas[1],
+                                       self.eps)
 
     def _pack(self):
         g = self.param_groups
@@ -222,6 +243,11 @@ class GuardedClipAdamW(FusedClipAdamW):
     def enqueue(self):
         """the three launches; allocation-free and capturable"""
         f = self.flat
+        if self.segments is not None:       # frozen parameters: the same two steps over the trainable segments
+            ops.step_guard_seg(f.grad, self.segments, self.host_rec, self.dev_rec, self.bias_table, self._ws)
+            ops.adamw_step_guarded_seg(f.data, f.grad, self.exp_avg, self.exp_avg_sq, f.n_decay, self.segments,
+                                       self.host_rec, self.dev_rec, self.betas[0], self.betas[1], self.eps)
+            return
         ops.step_guard(f.grad, self.host_rec, self.dev_rec, self.bias_table, self._ws)
         ops.adamw_step_guarded(f.data, f.grad, self.exp_avg, self.exp_avg_sq, f.n_decay, self.host_rec, self.dev_rec,
                                self.betas[0], self.betas[1], self.eps)
