@@ -655,6 +655,21 @@ int svit_adamw_step_guarded_seg(float* p, const float* g, float* m, float* v, in
                                 const int64_t* segs, int64_t S, const svit_step_host* host_rec,
                                 const svit_step_dev* dev_rec, float beta1, float beta2, float eps, void* stream);
 
+/* svit_adamw_step_guarded_seg with a learning-rate scale per segment (layer-wise lr decay, per-range multipliers):
+ * `scales` = float [S] IN HOST MEMORY beside `segs`, every scale finite and > 0 (else SVIT_ERR_ARG).  Both are checked
+ * on the host before any HIP call -- the table by svit_adamw_step_guarded_seg's rules, with its error codes -- and travel
+ * in the kernel arguments (1.3 KB; a captured graph keeps its copy).  An element of segment s in weight-decay group w is
+ * stepped with lr_eff = lr[w] * scales[s], ONE fp32 multiply on the device, in every place svit_adamw_step_guarded uses
+ * lr[w] (the decay factor 1 - lr_eff * weight_decay[w] and the step lr_eff / bc1); the coefficient, the bias corrections
+ * and the guard's decision are not scaled.  The results are bit for bit those of svit_adamw_step_guarded_seg run over
+ * the segments of one scale with a record that holds the premultiplied lr_eff.  Segments that touch (begin == the
+ * previous end) and several segments inside one 1024-float window are the normal case.  The guard in front of it is
+ * svit_step_guard, or svit_step_guard_seg when part of the buffer is frozen.  ONE launch; no load or store of p, g, m
+ * or v outside the segments; returns early on a dropped step. */
+int svit_adamw_step_guarded_lr(float* p, const float* g, float* m, float* v, int64_t n, int64_t n_decay,
+                               const int64_t* segs, const float* scales, int64_t S, const svit_step_host* host_rec,
+                               const svit_step_dev* dev_rec, float beta1, float beta2, float eps, void* stream);
+
 /* ------------------------------------------------------------------ head (K15) ---------- */
 /* SViT head (slowfast/models/video_model_builder.py:408-551) in one launch each way, fp32: dropout factors
  * applied to the cls / object rows of the final norm's output, class logits from the cls row, box MLP +

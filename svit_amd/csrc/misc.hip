@@ -1,6 +1,7 @@
 // Memory-bound helpers: casts / transposes of the weight copies, DropPath backward scaling,
 // im2col for the patch-embedding conv, special-token rows, max-pool skip path, and the
 // optimiser tail (global grad norm + clip + AdamW) -- gfx950 only.
+#include <cstring>
 #include <mutex>
 #include <unordered_map>
 #include "common.h"
@@ -654,6 +655,71 @@ __global__ __launch_bounds__(256) void adamw_guarded_seg_kernel(float* __restric
   else adamw_guarded_seg_range<false>(p, g, m, v, n, n_decay, h, coef, bc1, bc2_sqrt, b1, b2, eps, t);
 }
 
+// ---- per-range learning-rate scales (layer-wise lr decay: svit_adamw_step_guarded_lr) -------------------------------
+// The segment table plus one fp32 scale per segment, both in the kernel arguments.  The walk is the `_seg` kernel's; what
+// it yields besides "inside" is the learning rate and weight decay of the segment the quad lies in (bounds are multiples
+// of 4 and no segment crosses n_decay: a quad has one of each).  A window of 1024 floats commonly meets several segments
+// here -- the loop over them is workgroup-uniform, a lane keeps the values of the one segment that holds its quad.
+struct LrTable {
+  SegTable t;
+  float scale[SVIT_MAX_SEGS];
+};
+// lr * scale as ONE fp32 multiply whose result the optimiser cannot see through: the build is -ffast-math, and a product
+// left transparent may be reassociated into `(lr * scale) * wd` or folded into `lr / bc1`.  Both factors are
+// workgroup-uniform, so reading the bits back through the first lane changes nothing and ends the expression there; what
+// adamw_guarded_update then gets is a plain value, as the `_seg` kernel gets h->lr[] from memory.
+__device__ __forceinline__ float lr_times_scale(float lr, float scale) {
+  return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(lr * scale)));
+}
+
+template <bool CLAMP>
+__device__ __forceinline__ void adamw_guarded_lr_range(float* __restrict__ p, const float* __restrict__ g,
+                                                       float* __restrict__ m, float* __restrict__ v, int64_t n,
+                                                       int64_t n_decay, const svit_step_host* __restrict__ h,
+                                                       float coef, float bc1, float bc2_sqrt, float b1, float b2,
+                                                       float eps, const LrTable& T) {
+  const SegTable& t = T.t;
+  const float cv = h->clip_value;
+  const float lr0 = h->lr[0], lr1 = h->lr[1], wd0 = h->weight_decay[0], wd1 = h->weight_decay[1];
+  const int64_t window = (int64_t)blockDim.x * 4, stride = (int64_t)gridDim.x * window;
+  int k = 0;
+  for (int64_t lo = (int64_t)blockIdx.x * window; lo < n; lo += stride) {
+    const int64_t i = lo + (int64_t)threadIdx.x * 4, hi = lo + window;
+    while (k < t.S && t.v[k][1] <= lo) ++k;
+    bool in = false;
+    float lr = 0.f, wd = 0.f;
+    for (int j = k; j < t.S && t.v[j][0] < hi; ++j) {
+      const bool dec = t.v[j][0] < n_decay;                                // the whole segment: none crosses n_decay
+      const float le = lr_times_scale(dec ? lr0 : lr1, T.scale[j]);
+      const bool here = (i >= t.v[j][0]) & (i < t.v[j][1]);
+      in |= here;
+      lr = here ? le : lr;
+      wd = here ? (dec ? wd0 : wd1) : wd;
+    }
+    if (!in) continue;
+    const int64_t q = i >> 2;
+    float4 P = ((const float4*)p)[q], M = ((const float4*)m)[q], V = ((const float4*)v)[q];
+    const float4 G = ((const float4*)g)[q];
+    adamw_guarded_update<CLAMP>(P.x, G.x, M.x, V.x, coef, cv, lr, wd, b1, b2, eps, bc1, bc2_sqrt);
+    adamw_guarded_update<CLAMP>(P.y, G.y, M.y, V.y, coef, cv, lr, wd, b1, b2, eps, bc1, bc2_sqrt);
+    adamw_guarded_update<CLAMP>(P.z, G.z, M.z, V.z, coef, cv, lr, wd, b1, b2, eps, bc1, bc2_sqrt);
+    adamw_guarded_update<CLAMP>(P.w, G.w, M.w, V.w, coef, cv, lr, wd, b1, b2, eps, bc1, bc2_sqrt);
+    ((float4*)p)[q] = P; ((float4*)m)[q] = M; ((float4*)v)[q] = V;
+  }
+}
+
+// adamw_guarded_seg_kernel with the learning rate of a quad = fp32(lr of its group) * fp32(scale of its segment)
+__global__ __launch_bounds__(256) void adamw_guarded_lr_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                               float* __restrict__ m, float* __restrict__ v, int64_t n,
+                                                               int64_t n_decay, const svit_step_host* __restrict__ h,
+                                                               const svit_step_dev* __restrict__ d, float b1, float b2,
+                                                               float eps, const LrTable T) {
+  if (d->apply == 0) return;
+  const float coef = d->coef, bc1 = d->bc1, bc2_sqrt = d->bc2_sqrt;
+  if (h->clip_value > 0.f) adamw_guarded_lr_range<true>(p, g, m, v, n, n_decay, h, coef, bc1, bc2_sqrt, b1, b2, eps, T);
+  else adamw_guarded_lr_range<false>(p, g, m, v, n, n_decay, h, coef, bc1, bc2_sqrt, b1, b2, eps, T);
+}
+
 // host side of both: the table's checks (before any HIP call) and its copy into the kernel-argument form.
 // n_decay < 0: no weight-decay boundary to respect (the guard).
 static int seg_table_take(const int64_t* segs, int64_t S, int64_t n, int64_t n_decay, SegTable* out) {
@@ -1101,6 +1167,30 @@ extern "C" int svit_adamw_step_guarded_seg(float* p, const float* g, float* m, f
   const int64_t span = t.v[S - 1][1];
   hipLaunchKernelGGL(adamw_guarded_seg_kernel, dim3(grid_for(span >> 2, 256, 4096)), dim3(256), 0, (hipStream_t)stream,
                      p, g, m, v, span, n_decay, host_rec, dev_rec, beta1, beta2, eps, t);
+  SVIT_LAUNCH_CHECK();
+  return SVIT_OK;
+}
+
+extern "C" int svit_adamw_step_guarded_lr(float* p, const float* g, float* m, float* v, int64_t n, int64_t n_decay,
+                                          const int64_t* segs, const float* scales, int64_t S,
+                                          const svit_step_host* host_rec, const svit_step_dev* dev_rec, float beta1,
+                                          float beta2, float eps, void* stream) {
+  if (!p || !g || !m || !v || !host_rec || !dev_rec || n <= 0 || n_decay < 0 || n_decay > n) return SVIT_ERR_ARG;
+  LrTable T;
+  if (int rc = seg_table_take(segs, S, n, n_decay, &T.t)) return rc;
+  if (!scales) return SVIT_ERR_ARG;
+  for (int64_t s = 0; s < SVIT_MAX_SEGS; ++s) {
+    uint32_t bits = 0;
+    if (s < S) memcpy(&bits, scales + s, sizeof bits);
+    // finite and > 0, by the bits (the build is -ffast-math: no reliance on what it makes of isfinite)
+    if (s < S && ((bits & 0x7f800000u) == 0x7f800000u || (bits >> 31) || (bits & 0x7fffffffu) == 0)) return SVIT_ERR_ARG;
+    T.scale[s] = s < S ? scales[s] : 0.f;
+  }
+  if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) return SVIT_ERR_ALIGN;
+  if (((uintptr_t)host_rec | (uintptr_t)dev_rec) & 7) return SVIT_ERR_ALIGN;
+  const int64_t span = T.t.v[S - 1][1];       // the grid of svit_adamw_step_guarded_seg: the segments' extent
+  hipLaunchKernelGGL(adamw_guarded_lr_kernel, dim3(grid_for(span >> 2, 256, 4096)), dim3(256), 0, (hipStream_t)stream,
+                     p, g, m, v, span, n_decay, host_rec, dev_rec, beta1, beta2, eps, T);
   SVIT_LAUNCH_CHECK();
   return SVIT_OK;
 }

@@ -958,6 +958,23 @@ def adamw_step_guarded_seg(p, g, m, v, n_decay, segs, host_rec, dev_rec, beta1, 
              ptr(dev_rec), beta1, beta2, eps)
 
 
+def adamw_step_guarded_lr(p, g, m, v, n_decay, segs, scales, host_rec, dev_rec, beta1, beta2, eps):
+    """adamw_step_guarded_seg with the learning rate of segment s multiplied by scales[s], a C-contiguous float32 numpy
+    [S] on the host (svit_adamw_step_guarded_lr; the library checks the contents of both tables before it launches)"""
+    import numpy as np
+    _chk_dev(p, g, m, v)
+    _chk_step_records(host_rec, dev_rec, p.device)
+    n = p.numel()
+    if g.numel() != n or m.numel() != n or v.numel() != n:
+        raise hip.SvitHipError("adamw_step_guarded_lr: p, g, m, v differ in size")
+    sp, S = _chk_segs(segs)
+    if not (isinstance(scales, np.ndarray) and scales.dtype == np.float32 and scales.shape == (S,)
+            and scales.flags["C_CONTIGUOUS"]):
+        raise hip.SvitHipError("the scales are a C-contiguous float32 numpy array [S], one per segment")
+    hip.call("svit_adamw_step_guarded_lr", ptr(p), ptr(g), ptr(m), ptr(v), n, n_decay, sp, scales.ctypes.data, S,
+             ptr(host_rec), ptr(dev_rec), beta1, beta2, eps)
+
+
 # ---------------------------------------------------------------- head (K15) ----------------
 def _head_args(tokens, T, O, keep, head_params, outs):
     a = hip.HeadArgs()

@@ -14,7 +14,8 @@ import math
 import numpy as np
 import torch
 
-from . import freeze, hip, ops
+from . import freeze, hip, lrscale, ops
+from .lrscale import lr_scale_from_cfg  # noqa: F401  (construct_optimizer's source of `lr_scale`)
 
 
 def get_lr_at_epoch(cfg, cur_epoch):
@@ -42,10 +43,15 @@ class FusedClipAdamW:
 
     Parameters with `requires_grad = False` (read here, once: svit_amd/freeze.py) are left out as the reference leaves
     them out (slowfast/models/optimizer.py:39-76): never decayed, no moments, not in the clip norm, not in
-    `state_dict()`.  The kernels then run on `segments`, the trainable ranges of the flat buffers."""
+    `state_dict()`.  The kernels then run on `segments`, the trainable ranges of the flat buffers.
+
+    lr_scale: a callable name -> float (svit_amd/lrscale.py: layer-wise lr decay, per-prefix multipliers).  An element
+    is stepped with float32(lr of its group) * float32(scale of its parameter); `param_groups` stays the two entries
+    `set_lr` writes, the scales live in `lr_segments` int64 [S, 2] / `lr_scales` float32 [S], fixed here.  None, or 1.0
+    for every trainable parameter: no table, and the optimizer is the one it was without the argument."""
 
     def __init__(self, model, lr, weight_decay=1e-4, betas=(0.9, 0.999), eps=1e-8,
-                 clip_grad_l2norm=None, grad_scale=1.0):
+                 clip_grad_l2norm=None, grad_scale=1.0, lr_scale=None):
         core = model.module if hasattr(model, "module") else model
         self.model, self.flat = core, core.flat
         if self.flat is None:
@@ -54,6 +60,13 @@ class FusedClipAdamW:
         # (a bare holder of flat buffers, as tools and tests build one, has no flags to read: nothing frozen)
         self.cut = core.frozen_cut() if hasattr(core, "frozen_cut") else 0
         self.segments = core.trainable_segments(self.cut) if self.cut else None
+        self.lr_segments = self.lr_scales = self._name_scale = None
+        if lr_scale is not None:
+            scales = lrscale.name_scales(self.flat.slots, lr_scale)
+            tab = lrscale.table(self.flat.slots, self.flat.n_decay, scales, self.segments)
+            if tab is not None:
+                self.lr_segments, self.lr_scales = tab
+                self._name_scale = scales
         self.betas, self.eps = betas, eps
         self.clip = clip_grad_l2norm
         self.grad_scale = grad_scale
@@ -88,7 +101,14 @@ class FusedClipAdamW:
 
     def _launches(self):
         """(param group, begin, end) of the AdamW launches of a step: one per weight-decay group, or -- with frozen
-        parameters -- one per trainable segment (a segment never crosses the groups' boundary)"""
+        parameters -- one per trainable segment (a segment never crosses the groups' boundary), or -- with learning-rate
+        scales -- one per range of the table, the group's lr replaced by the fp32 product the guarded tail forms"""
+        if self.lr_segments is not None:
+            nd, out = self.flat.n_decay, []
+            for (a, b), c in zip(self.lr_segments, self.lr_scales):
+                g = self.param_groups[0 if a < nd else 1]
+                out.append((dict(g, lr=float(np.float32(g["lr"]) * c)), int(a), int(b)))
+            return out
         if self.segments is None:
             return [(g,) + tuple(g["range"]) for g in self.param_groups if g["range"][1] > g["range"][0]]
         nd = self.flat.n_decay
@@ -125,15 +145,28 @@ class FusedClipAdamW:
         for g, names in zip(self.param_groups, (dec, rest)):
             if not names:
                 continue
-            groups.append({"lr": g["lr"], "betas": tuple(self.betas), "eps": self.eps,
-                           "weight_decay": g["weight_decay"], "amsgrad": False, "maximize": False,
-                           "foreach": None, "capturable": False, "differentiable": False,
-                           "fused": None, "decoupled_weight_decay": True,
-                           "params": list(range(base, base + len(names)))})
+            # with learning-rate scales each group splits by distinct scale, in order of first appearance, into
+            # torch-shaped groups: "lr" is the effective rate, "layer_decay" the scale
+            split = {}
+            for j, n in enumerate(names, base):
+                split.setdefault(None if self._name_scale is None else self._name_scale[n], []).append(j)
+            for c, idx in split.items():
+                grp = {"lr": g["lr"] if c is None else float(np.float32(g["lr"]) * c),
+                       "betas": tuple(self.betas), "eps": self.eps,
+                       "weight_decay": g["weight_decay"], "amsgrad": False, "maximize": False,
+                       "foreach": None, "capturable": False, "differentiable": False,
+                       "fused": None, "decoupled_weight_decay": True,
+                       "params": idx}
+                if c is not None:
+                    grp["layer_decay"] = float(c)
+                groups.append(grp)
             base += len(names)
         return {"state": state, "param_groups": groups}
 
     def load_state_dict(self, sd):
+        """either form of `param_groups` -- the reference's two groups or groups split by "layer_decay" -- whatever this
+        optimizer's own scales are: moments go by index, the base lr of a weight-decay group is `lr / layer_decay` of its
+        first subgroup"""
         dec, rest = self._order()
         order = dec + rest
         n_listed = sum(len(g["params"]) for g in sd["param_groups"])
@@ -157,8 +190,14 @@ class FusedClipAdamW:
             self.flat.view(self.exp_avg_sq, n).copy_(ent["exp_avg_sq"])
             step = max(step, int(ent["step"]))
         self.step_count = step
-        for g, src in zip(self.param_groups, sd["param_groups"]):
-            g["lr"] = src["lr"]
+        seen = set()
+        for src in sd["param_groups"]:
+            if not src["params"]:
+                continue
+            which = 0 if int(src["params"][0]) < len(dec) else 1
+            if which not in seen:
+                seen.add(which)
+                self.param_groups[which]["lr"] = src["lr"] / src.get("layer_decay", 1.0)
 
 
 def pack_step_host(lr, weight_decay, max_norm, clip_value, grad_scale):
@@ -184,9 +223,9 @@ class GuardedClipAdamW(FusedClipAdamW):
     RING = 16
 
     def __init__(self, model, lr, weight_decay=1e-4, betas=(0.9, 0.999), eps=1e-8, clip_grad_l2norm=None,
-                 grad_scale=1.0, clip_grad_value=None, max_consecutive_skips=None):
+                 grad_scale=1.0, clip_grad_value=None, max_consecutive_skips=None, lr_scale=None):
         super().__init__(model, lr, weight_decay=weight_decay, betas=betas, eps=eps,
-                         clip_grad_l2norm=clip_grad_l2norm, grad_scale=grad_scale)
+                         clip_grad_l2norm=clip_grad_l2norm, grad_scale=grad_scale, lr_scale=lr_scale)
         self.clip_value = clip_grad_value
         self.max_consecutive_skips = max_consecutive_skips
         dev = self.flat.data.device
@@ -218,6 +257,10 @@ class GuardedClipAdamW(FusedClipAdamW):
             ops.step_guard_seg(z[1], seg, self.host_rec, rec, self.bias_table, self._ws)
             ops.adamw_step_guarded_seg(z[0], z[1], z[2], z[3], 4, seg, self.host_rec, rec, self.betas[0], self.betas[1],
                                        self.eps)
+        if self.lr_segments is not None:
+            ops.adamw_step_guarded_lr(z[0], z[1], z[2], z[3], 4, np.array([[0, 4]], dtype=np.int64),
+                                      np.ones(1, dtype=np.float32), self.host_rec, rec, self.betas[0], self.betas[1],
+                                      self.eps)
 
     def _pack(self):
         g = self.param_groups
@@ -243,6 +286,14 @@ class GuardedClipAdamW(FusedClipAdamW):
     def enqueue(self):
         """the three launches; allocation-free and capturable"""
         f = self.flat
+        if self.lr_segments is not None:    # learning-rate scales: today's guard, then AdamW over the scaled ranges
+            if self.segments is not None:
+                ops.step_guard_seg(f.grad, self.segments, self.host_rec, self.dev_rec, self.bias_table, self._ws)
+            else:
+                ops.step_guard(f.grad, self.host_rec, self.dev_rec, self.bias_table, self._ws)
+            ops.adamw_step_guarded_lr(f.data, f.grad, self.exp_avg, self.exp_avg_sq, f.n_decay, self.lr_segments,
+                                      self.lr_scales, self.host_rec, self.dev_rec, self.betas[0], self.betas[1], self.eps)
+            return
         if self.segments is not None:       # frozen parameters: the same two steps over the trainable segments
             ops.step_guard_seg(f.grad, self.segments, self.host_rec, self.dev_rec, self.bias_table, self._ws)
             ops.adamw_step_guarded_seg(f.data, f.grad, self.exp_avg, self.exp_avg_sq, f.n_decay, self.segments,
@@ -293,12 +344,14 @@ def construct_optimizer(model, cfg):
     opt-in SVIT.GUARDED_STEP (not a key of the default tree, like SVIT.REPRODUCIBLE), selects the guarded tail."""
     if cfg.SOLVER.OPTIMIZING_METHOD != "adamw" or not cfg.SOLVER.ZERO_WD_1D_PARAM:
         raise NotImplementedError("svit_amd fuses the configs/ssv2.yaml solver (adamw, ZERO_WD_1D_PARAM)")
+    lr_scale = lr_scale_from_cfg(cfg)       # SOLVER.LAYER_DECAY / SVIT.LR_MULT (svit_amd/lrscale.py); None without them
     if getattr(cfg.SVIT, "GUARDED_STEP", False) or cfg.SOLVER.CLIP_GRAD_VAL:
         return GuardedClipAdamW(model, lr=cfg.SOLVER.BASE_LR, weight_decay=cfg.SOLVER.WEIGHT_DECAY,
                                 clip_grad_l2norm=cfg.SOLVER.CLIP_GRAD_L2NORM, clip_grad_value=cfg.SOLVER.CLIP_GRAD_VAL,
-                                max_consecutive_skips=getattr(cfg.SVIT, "MAX_CONSECUTIVE_SKIPS", None))
+                                max_consecutive_skips=getattr(cfg.SVIT, "MAX_CONSECUTIVE_SKIPS", None),
+                                lr_scale=lr_scale)
     return FusedClipAdamW(model, lr=cfg.SOLVER.BASE_LR, weight_decay=cfg.SOLVER.WEIGHT_DECAY,
-                          clip_grad_l2norm=cfg.SOLVER.CLIP_GRAD_L2NORM)
+                          clip_grad_l2norm=cfg.SOLVER.CLIP_GRAD_L2NORM, lr_scale=lr_scale)
 
 
 def set_lr(optimizer, new_lr):
