@@ -670,6 +670,37 @@ int svit_adamw_step_guarded_lr(float* p, const float* g, float* m, float* v, int
                                const int64_t* segs, const float* scales, int64_t S, const svit_step_host* host_rec,
                                const svit_step_dev* dev_rec, float beta1, float beta2, float eps, void* stream);
 
+/* The reference's other two solvers (slowfast/models/optimizer.py:86-101: torch.optim.SGD, torch.optim.Adam) on the
+ * guarded tail: the guard in front is svit_step_guard / svit_step_guard_seg, unchanged, and the record it leaves is
+ * read here as svit_adamw_step_guarded_lr reads it.  `segs` / `scales` / S are that entry point's tables IN HOST MEMORY,
+ * checked on the host before any HIP call by its rules and with its error codes, and carried in the kernel arguments;
+ * scales == NULL: every scale is 1.0.  An element of range s in weight-decay group w has lr_eff = lr[w] * scales[s] (ONE
+ * fp32 multiply) and wd = weight_decay[w].  ONE launch; 16-byte accesses; no load or store outside the ranges; every
+ * workgroup returns before its first load on a dropped step.  Every fp32 operation is rounded once, in the order
+ * written (no contraction, correctly rounded sqrtf and divisions): the results equal the NumPy float32 restatements
+ * svit_amd/optim.py sgd_step_host / adam_step_host bit for bit.  With gi = g * coef, clamped to +-clip_value when
+ * clip_value > 0, then gi = gi + p * wd when wd != 0 (coupled L2):
+ *
+ * svit_sgd_step_guarded, p, g, buf f32 [n]:
+ *     if momentum != 0:  buf = first ? gi : buf * momentum + gi * (1 - dampening)
+ *                        gi  = nesterov ? gi + buf * momentum : buf
+ *     p = p - gi * lr_eff
+ *   `first` is dev_rec->applied == 1, read on the device: the first APPLIED step copies gi into the buffer, as
+ *   torch.optim.SGD does for a momentum_buffer of None (a dropped step does not advance `applied`).  1 - dampening is
+ *   formed once on the host in fp32.  With momentum == 0 buf may be NULL and is never touched (12 B per parameter
+ *   against 20).  The guard takes a bias table of 0 entries.  SVIT_ERR_ARG besides the tables': nesterov != 0 with
+ *   momentum <= 0 or dampening != 0; momentum != 0 with buf == NULL.
+ * svit_adam_step_guarded, p, g, m, v f32 [n] (28 B per parameter):
+ *     m = m * beta1 + gi * (1 - beta1);  v = v * beta2 + (gi * gi) * (1 - beta2)
+ *     p = p - (lr_eff / bc1) * (m / (sqrtf(v) / bc2_sqrt + eps))
+ *   with (bc1, bc2_sqrt) the pair the guard looked up in svit_adamw_bias_table(beta1, beta2). */
+int svit_sgd_step_guarded(float* p, const float* g, float* buf, int64_t n, int64_t n_decay, const int64_t* segs,
+                          const float* scales, int64_t S, const svit_step_host* host_rec, const svit_step_dev* dev_rec,
+                          float momentum, float dampening, int nesterov, void* stream);
+int svit_adam_step_guarded(float* p, const float* g, float* m, float* v, int64_t n, int64_t n_decay,
+                           const int64_t* segs, const float* scales, int64_t S, const svit_step_host* host_rec,
+                           const svit_step_dev* dev_rec, float beta1, float beta2, float eps, void* stream);
+
 /* ------------------------------------------------------------------ head (K15) ---------- */
 /* SViT head (slowfast/models/video_model_builder.py:408-551) in one launch each way, fp32: dropout factors
  * applied to the cls / object rows of the final norm's output, class logits from the cls row, box MLP +

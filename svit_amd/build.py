@@ -17,7 +17,7 @@ CSRC = os.path.join(HERE, "csrc")
 OUT_DIR = os.path.join(HERE, "lib")
 LIB = os.path.join(OUT_DIR, "libsvit_hip.so")
 SOURCES = ["gemm_nt.hip", "gemm_tn.hip", "norm.hip", "misc.hip", "pool.hip", "attn_fwd.hip", "attn_bwd.hip",
-           "loss.hip", "meter.hip", "input.hip", "head.hip", "randaug.hip", "feed.hip", "head_eval.hip"]
+           "loss.hip", "meter.hip", "input.hip", "head.hip", "randaug.hip", "feed.hip", "head_eval.hip", "solver.hip"]
 HEADERS = ["common.h", "attn_common.h", "gemm_epilogue.h", os.path.join("..", "..", "include", "svit_hip.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -fno-slp-vectorize: hipcc's SLP pass packs adjacent fp32 multiplies / adds into v_pk_*_f32.  The
@@ -33,6 +33,8 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-ffast-math",
          "-fno-finite-math-only", "-fno-slp-vectorize", "-Wno-unused-result"]
 # per-source changes to FLAGS.  randaug.hip must give PIL's bytes: its fp32 / fp64 products and sums are rounded one by
 # one, and under -ffast-math the backend fuses them whatever the source says (csrc/input.hip, mix_blend).
+# (solver.hip, whose bar is a NumPy fp32 restatement, takes the common flags: its arithmetic goes through helpers that
+# round each operation once whatever the flags say -- randaug.hip stays the one source built differently.)
 SOURCE_FLAGS = {"randaug.hip": {"remove": ["-ffast-math"], "add": ["-ffp-contract=off"]}}
 TMP_DIR = os.path.join(OUT_DIR, "tmp")
 

@@ -5,7 +5,8 @@ A file written here loads with the reference's `cu.load_checkpoint` and vice ver
 dict {"epoch", "model_state", "optimizer_state", "cfg", "scaler_state"} whose model_state has the
 reference's 405 names in registration order and whose optimizer_state is the
 torch.optim.AdamW.state_dict() of the reference's two param groups (svit_amd.optim.FusedClipAdamW
-reads and writes that layout from its flat moment buffers).  Layout pinned by
+reads and writes that layout from its flat moment buffers; under SOLVER.OPTIMIZING_METHOD sgd /
+adam it is torch.optim.SGD's / Adam's, from optim.GuardedClipSGD / GuardedClipAdam).  Layout pinned by
 tests/golden/layout.json, recorded from the reference's own save_checkpoint.
 """
 import os

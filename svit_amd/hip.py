@@ -210,6 +210,8 @@ _SIGS = {
     "svit_step_guard_seg": (i32, [vp, i64, vp, i64, vp, vp, vp, i64, vp, i64, vp]),
     "svit_adamw_step_guarded_seg": (i32, [vp, vp, vp, vp, i64, i64, vp, i64, vp, vp, f32, f32, f32, vp]),
     "svit_adamw_step_guarded_lr": (i32, [vp, vp, vp, vp, i64, i64, vp, vp, i64, vp, vp, f32, f32, f32, vp]),
+    "svit_sgd_step_guarded": (i32, [vp, vp, vp, i64, i64, vp, vp, i64, vp, vp, f32, f32, i32, vp]),
+    "svit_adam_step_guarded": (i32, [vp, vp, vp, vp, i64, i64, vp, vp, i64, vp, vp, f32, f32, f32, vp]),
     "svit_head_fwd": (i32, [C.POINTER(HeadArgs), vp]),
     "svit_head_bwd": (i32, [C.POINTER(HeadBwdArgs), vp]),
     "svit_head_eval": (i32, [C.POINTER(HeadArgs), i32, vp]),

@@ -975,6 +975,36 @@ def adamw_step_guarded_lr(p, g, m, v, n_decay, segs, scales, host_rec, dev_rec, 
              ptr(host_rec), ptr(dev_rec), beta1, beta2, eps)
 
 
+def _chk_solver(what, segs, scales, host_rec, dev_rec, p, *others):
+    """operands of the SGD / Adam tails: equal-sized device buffers (None where there is none), the step record, the range
+    table and its scales -- None, or a C-contiguous float32 numpy [S] (the library checks the contents of both)"""
+    import numpy as np
+    _chk_dev(p, *others)
+    _chk_step_records(host_rec, dev_rec, p.device)
+    if any(t is not None and t.numel() != p.numel() for t in others):
+        raise hip.SvitHipError("%s: the buffers differ in size" % what)
+    sp, S = _chk_segs(segs)
+    if scales is not None and not (isinstance(scales, np.ndarray) and scales.dtype == np.float32 and scales.shape == (S,)
+                                   and scales.flags["C_CONTIGUOUS"]):
+        raise hip.SvitHipError("the scales are None or a C-contiguous float32 numpy array [S], one per segment")
+    return sp, None if scales is None else scales.ctypes.data, S
+
+
+def sgd_step_guarded(p, g, buf, n_decay, segs, scales, host_rec, dev_rec, momentum, dampening, nesterov):
+    """torch.optim.SGD's update on the ranges of `segs` as the step record says, nothing on a dropped step
+    (svit_sgd_step_guarded); buf: the momentum buffer, None when momentum == 0; scales None: every scale 1.0"""
+    sp, cp, S = _chk_solver("sgd_step_guarded", segs, scales, host_rec, dev_rec, p, g, buf)
+    hip.call("svit_sgd_step_guarded", ptr(p), ptr(g), ptr(buf), p.numel(), n_decay, sp, cp, S, ptr(host_rec),
+             ptr(dev_rec), momentum, dampening, int(bool(nesterov)))
+
+
+def adam_step_guarded(p, g, m, v, n_decay, segs, scales, host_rec, dev_rec, beta1, beta2, eps):
+    """torch.optim.Adam's update (coupled weight decay) on the ranges of `segs` (svit_adam_step_guarded)"""
+    sp, cp, S = _chk_solver("adam_step_guarded", segs, scales, host_rec, dev_rec, p, g, m, v)
+    hip.call("svit_adam_step_guarded", ptr(p), ptr(g), ptr(m), ptr(v), p.numel(), n_decay, sp, cp, S, ptr(host_rec),
+             ptr(dev_rec), beta1, beta2, eps)
+
+
 # ---------------------------------------------------------------- head (K15) ----------------
 def _head_args(tokens, T, O, keep, head_params, outs):
     a = hip.HeadArgs()

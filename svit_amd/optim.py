@@ -19,7 +19,8 @@ from .lrscale import lr_scale_from_cfg  # noqa: F401  (construct_optimizer's sou
 
 
 def get_lr_at_epoch(cfg, cur_epoch):
-    """slowfast/utils/lr_policy.py:9-66 (cosine policy with optional linear warm-up)."""
+    """slowfast/utils/lr_policy.py:9-96: the `cosine` and `steps_with_relative_lrs` policies with optional linear
+    warm-up."""
     s = cfg.SOLVER
 
     def cosine(ep):
@@ -27,11 +28,21 @@ def get_lr_at_epoch(cfg, cur_epoch):
         assert s.COSINE_END_LR < s.BASE_LR
         return s.COSINE_END_LR + (s.BASE_LR - s.COSINE_END_LR) * (
             math.cos(math.pi * (ep - offset) / (s.MAX_EPOCH - offset)) + 1.0) * 0.5
-    if s.LR_POLICY != "cosine":
-        raise NotImplementedError("svit_amd implements SOLVER.LR_POLICY == 'cosine'")
-    lr = cosine(cur_epoch)
+
+    def steps_with_relative_lrs(ep):
+        """LRS[i] * BASE_LR from epoch STEPS[i] on (lr_policy.py:69-96; past MAX_EPOCH the last entry of LRS)"""
+        for ind, step in enumerate(list(s.STEPS) + [s.MAX_EPOCH]):
+            if ep < step:
+                break
+        return s.LRS[ind - 1] * s.BASE_LR
+    policies = {"cosine": cosine, "steps_with_relative_lrs": steps_with_relative_lrs}
+    if s.LR_POLICY not in policies:
+        raise NotImplementedError("svit_amd implements SOLVER.LR_POLICY 'cosine' and 'steps_with_relative_lrs', got %r"
+                                  % (s.LR_POLICY,))
+    policy = policies[s.LR_POLICY]
+    lr = policy(cur_epoch)
     if cur_epoch < s.WARMUP_EPOCHS:
-        lr_end = cosine(s.WARMUP_EPOCHS)
+        lr_end = policy(s.WARMUP_EPOCHS)
         alpha = (lr_end - s.WARMUP_START_LR) / s.WARMUP_EPOCHS
         lr = cur_epoch * alpha + s.WARMUP_START_LR
     return {"lr": lr}
@@ -49,6 +60,10 @@ class FusedClipAdamW:
     is stepped with float32(lr of its group) * float32(scale of its parameter); `param_groups` stays the two entries
     `set_lr` writes, the scales live in `lr_segments` int64 [S, 2] / `lr_scales` float32 [S], fixed here.  None, or 1.0
     for every trainable parameter: no table, and the optimizer is the one it was without the argument."""
+
+    # what a solver keeps per parameter, as its torch twin's checkpoint names it = the flat buffers of these names
+    STATE = ("exp_avg", "exp_avg_sq")
+    STEP_IN_STATE = True        # every state entry carries the solver's step counter
 
     def __init__(self, model, lr, weight_decay=1e-4, betas=(0.9, 0.999), eps=1e-8,
                  clip_grad_l2norm=None, grad_scale=1.0, lr_scale=None):
@@ -72,8 +87,8 @@ class FusedClipAdamW:
         self.grad_scale = grad_scale
         n = self.flat.total
         dev = self.flat.data.device
-        self.exp_avg = torch.zeros(n, device=dev)
-        self.exp_avg_sq = torch.zeros(n, device=dev)
+        for key in self.STATE:
+            setattr(self, key, torch.zeros(n, device=dev))
         self.sumsq = torch.zeros(1, device=dev)
         self.step_count = 0
         nd = self.flat.n_decay
@@ -136,11 +151,11 @@ class FusedClipAdamW:
         (views of the flat moment buffers) and two param groups of indices."""
         dec, rest = self._order()
         state = {}
-        if self.step_count > 0:
+        if self.step_count > 0 and self.STATE:
             for j, n in enumerate(dec + rest):
-                state[j] = {"step": torch.tensor(float(self.step_count)),
-                            "exp_avg": self.flat.view(self.exp_avg, n),
-                            "exp_avg_sq": self.flat.view(self.exp_avg_sq, n)}
+                state[j] = {"step": torch.tensor(float(self.step_count))} if self.STEP_IN_STATE else {}
+                for key in self.STATE:
+                    state[j][key] = self.flat.view(getattr(self, key), n)
         groups, base = [], 0
         for g, names in zip(self.param_groups, (dec, rest)):
             if not names:
@@ -151,17 +166,19 @@ class FusedClipAdamW:
             for j, n in enumerate(names, base):
                 split.setdefault(None if self._name_scale is None else self._name_scale[n], []).append(j)
             for c, idx in split.items():
-                grp = {"lr": g["lr"] if c is None else float(np.float32(g["lr"]) * c),
-                       "betas": tuple(self.betas), "eps": self.eps,
-                       "weight_decay": g["weight_decay"], "amsgrad": False, "maximize": False,
-                       "foreach": None, "capturable": False, "differentiable": False,
-                       "fused": None, "decoupled_weight_decay": True,
-                       "params": idx}
+                grp = self._group(g["lr"] if c is None else float(np.float32(g["lr"]) * c), g["weight_decay"])
+                grp["params"] = idx
                 if c is not None:
                     grp["layer_decay"] = float(c)
                 groups.append(grp)
             base += len(names)
         return {"state": state, "param_groups": groups}
+
+    def _group(self, lr, weight_decay):
+        """a param group of torch.optim.AdamW.state_dict() but for "params", keys in torch's order"""
+        return {"lr": lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": weight_decay, "amsgrad": False,
+                "maximize": False, "foreach": None, "capturable": False, "differentiable": False, "fused": None,
+                "decoupled_weight_decay": True}
 
     def load_state_dict(self, sd):
         """either form of `param_groups` -- the reference's two groups or groups split by "layer_decay" -- whatever this
@@ -173,23 +190,32 @@ class FusedClipAdamW:
         if n_listed != len(order):
             raise ValueError("optimizer state lists %d parameters, the model has %d" % (n_listed, len(order)))
         state = sd["state"]
-        self.exp_avg.zero_()
-        self.exp_avg_sq.zero_()
-        step = 0
+        for key in self.STATE:
+            getattr(self, key).zero_()
+        step, found = 0, False
         for j, n in enumerate(order):
             ent = state.get(j, state.get(str(j)))
             if ent is None:
                 continue
             want = self.flat.slots[n][2]
-            for key in ("exp_avg", "exp_avg_sq"):     # copy_ would silently broadcast [96] -> [1,1,96]
-                if tuple(ent[key].shape) != tuple(want):
+            for key in self.STATE:
+                if key not in ent:
+                    raise ValueError("optimizer state %d (%s) holds %s and no %s: it was written by another solver"
+                                     % (j, n, sorted(ent), key))
+                if tuple(ent[key].shape) != tuple(want):      # copy_ would silently broadcast [96] -> [1,1,96]
                     raise ValueError("optimizer state %d (%s): %s has shape %s, the parameter %s -- the "
                                      "checkpoint's parameter order / decay groups differ from this model's"
                                      % (j, n, key, tuple(ent[key].shape), tuple(want)))
-            self.flat.view(self.exp_avg, n).copy_(ent["exp_avg"])
-            self.flat.view(self.exp_avg_sq, n).copy_(ent["exp_avg_sq"])
-            step = max(step, int(ent["step"]))
-        self.step_count = step
+                self.flat.view(getattr(self, key), n).copy_(ent[key])
+            found = bool(self.STATE)
+            if self.STEP_IN_STATE:
+                step = max(step, int(ent["step"]))
+        if self.STEP_IN_STATE:
+            self.step_count = step
+        elif found:             # loaded momentum buffers: the next step is not the one that initialises them
+            self.step_count = max(self.step_count, 1)
+        elif self.STATE:        # a state without buffers (torch: momentum_buffer None): zeroed above, the next step is "first"
+            self.step_count = 0
         seen = set()
         for src in sd["param_groups"]:
             if not src["params"]:
@@ -232,11 +258,14 @@ class GuardedClipAdamW(FusedClipAdamW):
         self._records()
         self.host_rec = torch.from_numpy(self._pack()).to(dev)
         # bias corrections of steps 1, 2, ...: tabulated once on the host, by the code the classic step runs per call
-        self.bias_table = torch.from_numpy(ops.adamw_bias_table(betas[0], betas[1])).to(dev)
+        self.bias_table = torch.from_numpy(self._bias_pairs()).to(dev)
         self._ws = torch.zeros(1024, device=dev)
         self._slots, self._events, self._next = None, [None] * self.RING, 0
         if dev.type == "cuda":
             self._warm()
+
+    def _bias_pairs(self):
+        return ops.adamw_bias_table(self.betas[0], self.betas[1])
 
     def _records(self):
         """svit_step_dev as int32 [12] (created on first use: the base constructor already assigns step_count)"""
@@ -286,22 +315,33 @@ class GuardedClipAdamW(FusedClipAdamW):
     def enqueue(self):
         """the three launches; allocation-free and capturable"""
         f = self.flat
-        if self.lr_segments is not None:    # learning-rate scales: today's guard, then AdamW over the scaled ranges
-            if self.segments is not None:
-                ops.step_guard_seg(f.grad, self.segments, self.host_rec, self.dev_rec, self.bias_table, self._ws)
-            else:
-                ops.step_guard(f.grad, self.host_rec, self.dev_rec, self.bias_table, self._ws)
+        self._guard()
+        if self.lr_segments is not None:    # learning-rate scales: AdamW over the scaled ranges
             ops.adamw_step_guarded_lr(f.data, f.grad, self.exp_avg, self.exp_avg_sq, f.n_decay, self.lr_segments,
                                       self.lr_scales, self.host_rec, self.dev_rec, self.betas[0], self.betas[1], self.eps)
-            return
-        if self.segments is not None:       # frozen parameters: the same two steps over the trainable segments
-            ops.step_guard_seg(f.grad, self.segments, self.host_rec, self.dev_rec, self.bias_table, self._ws)
+        elif self.segments is not None:     # frozen parameters: over the trainable segments
             ops.adamw_step_guarded_seg(f.data, f.grad, self.exp_avg, self.exp_avg_sq, f.n_decay, self.segments,
                                        self.host_rec, self.dev_rec, self.betas[0], self.betas[1], self.eps)
-            return
-        ops.step_guard(f.grad, self.host_rec, self.dev_rec, self.bias_table, self._ws)
-        ops.adamw_step_guarded(f.data, f.grad, self.exp_avg, self.exp_avg_sq, f.n_decay, self.host_rec, self.dev_rec,
-                               self.betas[0], self.betas[1], self.eps)
+        else:
+            ops.adamw_step_guarded(f.data, f.grad, self.exp_avg, self.exp_avg_sq, f.n_decay, self.host_rec,
+                                   self.dev_rec, self.betas[0], self.betas[1], self.eps)
+
+    def _guard(self):
+        """the sum of squares and the step's decision, over the trainable segments when part of the buffer is frozen"""
+        if self.segments is not None:
+            ops.step_guard_seg(self.flat.grad, self.segments, self.host_rec, self.dev_rec, self.bias_table, self._ws)
+        else:
+            ops.step_guard(self.flat.grad, self.host_rec, self.dev_rec, self.bias_table, self._ws)
+
+    def _ranges(self):
+        """(segs int64 [S, 2], scales float32 [S] or None) for the solvers that always walk a table: the scaled ranges,
+        else the trainable segments, else the extent of each weight-decay group"""
+        if self.lr_segments is not None:
+            return self.lr_segments, self.lr_scales
+        if self.segments is not None:
+            return self.segments, None
+        nd, n = self.flat.n_decay, self.flat.total
+        return np.array([r for r in ((0, nd), (nd, n)) if r[1] > r[0]], dtype=np.int64).reshape(-1, 2), None
 
     @torch.no_grad()
     def step(self):
@@ -339,12 +379,137 @@ class GuardedClipAdamW(FusedClipAdamW):
                                   s["grad_norm"]))
 
 
+# ---- SGD and Adam on the guarded tail (csrc/solver.hip) -------------------------------------------------------------
+def _solver_grad(p, g, coef, wd, clip_value):
+    gi = g * np.float32(coef)
+    cv = np.float32(clip_value or 0.0)
+    if cv > 0:
+        gi = np.minimum(np.maximum(gi, -cv), cv)
+    wd = np.asarray(wd, dtype=np.float32)
+    return np.where(wd != 0, gi + p * wd, gi)
+
+
+def sgd_step_host(p, g, buf, coef, lr_eff, wd, momentum=0.0, dampening=0.0, nesterov=False, first=False,
+                  clip_value=0.0):
+    """svit_sgd_step_guarded restated in NumPy float32, the kernel's yardstick: the same formulas in the same order, each
+    operation rounded once.  p, g, buf: float32 arrays (buf None with momentum == 0); lr_eff, wd: float32 scalars or
+    per-element arrays; coef and `first` as the guard's record has them.  -> (p, buf), new arrays"""
+    p, g = np.asarray(p, dtype=np.float32), np.asarray(g, dtype=np.float32)
+    gi = _solver_grad(p, g, coef, wd, clip_value)
+    if momentum != 0:
+        mom, omd = np.float32(momentum), np.float32(1) - np.float32(dampening)
+        buf = gi.copy() if first else np.asarray(buf, dtype=np.float32) * mom + gi * omd
+        gi = gi + buf * mom if nesterov else buf
+    return p - gi * np.asarray(lr_eff, dtype=np.float32), buf
+
+
+def adam_step_host(p, g, m, v, coef, bc1, bc2_sqrt, lr_eff, wd, betas=(0.9, 0.999), eps=1e-8, clip_value=0.0):
+    """svit_adam_step_guarded restated in NumPy float32 (see sgd_step_host); bc1, bc2_sqrt: the pair of the step from
+    ops.adamw_bias_table, as the guard's record has it.  -> (p, m, v), new arrays"""
+    p, g = np.asarray(p, dtype=np.float32), np.asarray(g, dtype=np.float32)
+    b1, b2 = np.float32(betas[0]), np.float32(betas[1])
+    gi = _solver_grad(p, g, coef, wd, clip_value)
+    m = np.asarray(m, dtype=np.float32) * b1 + gi * (np.float32(1) - b1)
+    v = np.asarray(v, dtype=np.float32) * b2 + (gi * gi) * (np.float32(1) - b2)
+    denom = np.sqrt(v) / np.float32(bc2_sqrt) + np.float32(eps)
+    return p - (np.asarray(lr_eff, dtype=np.float32) / np.float32(bc1)) * (m / denom), m, v
+
+
+class _GuardedRangeSolver(GuardedClipAdamW):
+    """What GuardedClipAdam and GuardedClipSGD share: a step is the guard, then ONE launch (`_launch`, the subclass's) over
+    the range table of `_ranges()`.  Everything around the update -- the step record and its upload, the drop of a
+    non-finite step, `stats()`, `check()`, `grad_scale`, clipping, `lr_scale`, the frozen cut -- is GuardedClipAdamW's;
+    its own AdamW launches (`_warm`, `enqueue`) are replaced here."""
+
+    def _warm(self):
+        dev = self.flat.data.device
+        z = torch.zeros(4, 4, device=dev)
+        rec = torch.zeros(12, dtype=torch.int32, device=dev)
+        seg = np.array([[0, 4]], dtype=np.int64)
+        ops.step_guard(z[1], self.host_rec, rec, self.bias_table, self._ws)
+        if self.segments is not None:
+            ops.step_guard_seg(z[1], seg, self.host_rec, rec, self.bias_table, self._ws)
+        self._launch(z[0], z[1], [z[2], z[3]], 4, seg, None, rec)
+
+    def _launch(self, p, g, state, n_decay, segs, scales, rec):
+        """the solver's launch on p, g and `state` (one buffer per entry of STATE) with the step record `rec`"""
+        raise NotImplementedError
+
+    def enqueue(self):
+        """the guard's two launches and the solver's one; allocation-free and capturable"""
+        f = self.flat
+        self._guard()
+        segs, scales = self._ranges()
+        self._launch(f.data, f.grad, [getattr(self, key) for key in self.STATE], f.n_decay, segs, scales, self.dev_rec)
+
+
+class GuardedClipAdam(_GuardedRangeSolver):
+    """torch.optim.Adam (weight decay added to the gradient, no amsgrad) on the guarded tail: the guard, then ONE launch
+    of svit_adam_step_guarded over the range table."""
+
+    def _launch(self, p, g, state, n_decay, segs, scales, rec):
+        ops.adam_step_guarded(p, g, state[0], state[1], n_decay, segs, scales, self.host_rec, rec, self.betas[0],
+                              self.betas[1], self.eps)
+
+    def _group(self, lr, weight_decay):
+        """a param group of torch.optim.Adam.state_dict()"""
+        return dict(super()._group(lr, weight_decay), decoupled_weight_decay=False)
+
+
+class GuardedClipSGD(_GuardedRangeSolver):
+    """torch.optim.SGD (momentum, dampening, nesterov, weight decay added to the gradient) on the guarded tail: the guard,
+    then ONE launch of svit_sgd_step_guarded.  One state buffer, `momentum_buffer`, or none with momentum == 0.  The
+    first APPLIED step copies the gradient into the buffer (the device reads that off the step record), also after
+    dropped steps.  Loading a checkpoint's buffers makes the next step an ordinary one; loading a state without buffers
+    (torch's `momentum_buffer` of None) zeroes them and makes the next step "first" again.  No betas, no eps: both are
+    None."""
+
+    STEP_IN_STATE = False
+
+    def __init__(self, model, lr, momentum=0.0, dampening=0.0, nesterov=False, weight_decay=0.0, clip_grad_l2norm=None,
+                 grad_scale=1.0, clip_grad_value=None, max_consecutive_skips=None, lr_scale=None):
+        if momentum < 0.0:
+            raise ValueError("Invalid momentum value: %s" % (momentum,))
+        if nesterov and (momentum <= 0 or dampening != 0):          # torch.optim.SGD's refusal, in its words
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        self.momentum, self.dampening, self.nesterov = momentum, dampening, bool(nesterov)
+        self.STATE = ("momentum_buffer",) if momentum != 0 else ()
+        self.momentum_buffer = None
+        super().__init__(model, lr, weight_decay=weight_decay, betas=None, eps=None, clip_grad_l2norm=clip_grad_l2norm,
+                         grad_scale=grad_scale, clip_grad_value=clip_grad_value,
+                         max_consecutive_skips=max_consecutive_skips, lr_scale=lr_scale)
+
+    def _bias_pairs(self):
+        """no bias corrections: a table of 0 entries, the guard then records 1.0 for both"""
+        return np.zeros((0, 2), dtype=np.float32)
+
+    def _launch(self, p, g, state, n_decay, segs, scales, rec):
+        ops.sgd_step_guarded(p, g, state[0] if self.STATE else None, n_decay, segs, scales, self.host_rec, rec,
+                             self.momentum, self.dampening, self.nesterov)
+
+    def _group(self, lr, weight_decay):
+        """a param group of torch.optim.SGD.state_dict()"""
+        return {"lr": lr, "momentum": self.momentum, "dampening": self.dampening, "weight_decay": weight_decay,
+                "nesterov": self.nesterov, "maximize": False, "foreach": None, "differentiable": False, "fused": None}
+
+
 def construct_optimizer(model, cfg):
-    """slowfast/models/optimizer.py:15-112 for the configuration the SViT recipe uses.  SOLVER.CLIP_GRAD_VAL, or the
-    opt-in SVIT.GUARDED_STEP (not a key of the default tree, like SVIT.REPRODUCIBLE), selects the guarded tail."""
-    if cfg.SOLVER.OPTIMIZING_METHOD != "adamw" or not cfg.SOLVER.ZERO_WD_1D_PARAM:
-        raise NotImplementedError("svit_amd fuses the configs/ssv2.yaml solver (adamw, ZERO_WD_1D_PARAM)")
+    """slowfast/models/optimizer.py:15-112.  `adamw`: the fused tail, guarded with SOLVER.CLIP_GRAD_VAL or the opt-in
+    SVIT.GUARDED_STEP (not a key of the default tree, like SVIT.REPRODUCIBLE).  `sgd` and `adam`: always the guarded
+    tail (GuardedClipSGD / GuardedClipAdam)."""
+    s = cfg.SOLVER
+    if not s.ZERO_WD_1D_PARAM:
+        raise NotImplementedError("svit_amd lays its flat buffers out for SOLVER.ZERO_WD_1D_PARAM: True")
+    if s.OPTIMIZING_METHOD not in ("sgd", "adam", "adamw"):
+        raise NotImplementedError("Does not support {} optimizer".format(s.OPTIMIZING_METHOD))
     lr_scale = lr_scale_from_cfg(cfg)       # SOLVER.LAYER_DECAY / SVIT.LR_MULT (svit_amd/lrscale.py); None without them
+    if s.OPTIMIZING_METHOD != "adamw":
+        common = dict(lr=s.BASE_LR, weight_decay=s.WEIGHT_DECAY, clip_grad_l2norm=s.CLIP_GRAD_L2NORM,
+                      clip_grad_value=s.CLIP_GRAD_VAL, lr_scale=lr_scale,
+                      max_consecutive_skips=getattr(cfg.SVIT, "MAX_CONSECUTIVE_SKIPS", None))
+        if s.OPTIMIZING_METHOD == "sgd":
+            return GuardedClipSGD(model, momentum=s.MOMENTUM, dampening=s.DAMPENING, nesterov=s.NESTEROV, **common)
+        return GuardedClipAdam(model, betas=(0.9, 0.999), eps=1e-8, **common)
     if getattr(cfg.SVIT, "GUARDED_STEP", False) or cfg.SOLVER.CLIP_GRAD_VAL:
         return GuardedClipAdamW(model, lr=cfg.SOLVER.BASE_LR, weight_decay=cfg.SOLVER.WEIGHT_DECAY,
                                 clip_grad_l2norm=cfg.SOLVER.CLIP_GRAD_L2NORM, clip_grad_value=cfg.SOLVER.CLIP_GRAD_VAL,
