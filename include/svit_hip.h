@@ -701,6 +701,37 @@ int svit_adam_step_guarded(float* p, const float* g, float* m, float* v, int64_t
                            const int64_t* segs, const float* scales, int64_t S, const svit_step_host* host_rec,
                            const svit_step_dev* dev_rec, float beta1, float beta2, float eps, void* stream);
 
+/* Exponential moving average of the weights behind a guarded solver (timm's ModelEma, in the captured step): ema, p f32
+ * [n], 16-byte aligned (else SVIT_ERR_ALIGN),
+ *     ema = ema * d + p * (1 - d)
+ * on the elements inside the ranges of `segs` (the table of svit_adamw_step_guarded_seg IN HOST MEMORY, checked on the
+ * host before any HIP call by its rules and with its error codes -- there is no weight-decay boundary here -- and
+ * carried in the kernel arguments).  ONE launch on svit_sgd_step_guarded's walk; 16-byte accesses; no load or store of
+ * ema or p outside the ranges; every workgroup returns before its first load of p or ema when dev_rec->apply == 0, so
+ * a dropped step leaves the average bit for bit as it was.  Nothing but ema is written: no counter, no record.
+ *   update number  k = max(dev_rec->applied + ema_rec[0], 1), read on the device.  `ema_rec` = int64 [2] in device memory,
+ *                  {offset, reserved}, 8-byte aligned, written by the host alone (when the average is created, reset or
+ *                  loaded from a checkpoint): the count is DERIVED from the guard's counter, which the guard in front
+ *                  has already advanced, so no workgroup advances anything another reads; the offset keeps the count
+ *                  across a resume of a solver that does not checkpoint `applied`.
+ *   decay          d = k <= table_entries ? decay_table[k - 1] : decay.  decay_table = float [table_entries] in device
+ *                  memory (svit_ema_decay_table's warm-up), NULL with 0 entries for a constant decay; `decay` travels as
+ *                  a kernel argument and is fixed for the life of a captured graph.
+ *   arithmetic     1 - d, e * d, p * (1 - d) and their sum are each rounded once, in that order, whatever the build's
+ *                  floating-point flags: the result equals svit_amd/ema.py ema_step_host bit for bit.
+ * SVIT_ERR_ARG besides the table's: decay not in (0, 1); table_entries < 0 or above 2^20; a NULL table with entries > 0;
+ * a NULL ema, p, ema_rec or dev_rec.  All checked before any HIP call.
+ *
+ * svit_ema_decay_table, HOST ONLY (no stream, no launch), the contract of svit_adamw_bias_table: entry k-1 =
+ * (float) min((double) decay, (1.0 + k) / (10.0 + k)) for updates k = 1, 2, ... up to and including the first k whose
+ * entry equals `decay` (89 949 entries at 0.9999, 8 990 at 0.999); past the table the decay is `decay`.  *n_entries receives that
+ * length; table (room for `capacity` floats) may be NULL to ask for the length alone.  SVIT_ERR_ARG: n_entries NULL, a
+ * table shorter than the length, decay not in (0, 1), or a length above 2^20. */
+int svit_ema_decay_table(float decay, float* table, int64_t capacity, int64_t* n_entries);
+int svit_ema_step_guarded(float* ema, const float* p, int64_t n, const int64_t* segs, int64_t S,
+                          const float* decay_table, int64_t table_entries, float decay, const int64_t* ema_rec,
+                          const svit_step_dev* dev_rec, void* stream);
+
 /* ------------------------------------------------------------------ head (K15) ---------- */
 /* SViT head (slowfast/models/video_model_builder.py:408-551) in one launch each way, fp32: dropout factors
  * applied to the cls / object rows of the final norm's output, class logits from the cls row, box MLP +

@@ -68,9 +68,11 @@ DEFAULT_SCALER_STATE = {"scale": 65536.0, "growth_factor": 2.0, "backoff_factor"
                         "growth_interval": 2000, "_growth_tracker": 0}
 
 
-def save_checkpoint(path_to_job, model, optimizer, epoch, cfg, scaler=None):
+def save_checkpoint(path_to_job, model, optimizer, epoch, cfg, scaler=None, ema=None):
     """checkpoint.py:124-156.  Tensors are copied off the flat device buffers (independent CPU
-    tensors, as the reference writes them)."""
+    tensors, as the reference writes them).
+    ema: an ema.WeightEMA -- its state_dict() goes under the key "ema_state" (the reference's loader ignores it; its
+    "model_state" entry has the model's names and shapes).  None: the reference's five keys and nothing else."""
     if not _is_master(cfg):
         return None
     os.makedirs(get_checkpoint_dir(path_to_job), exist_ok=True)
@@ -85,6 +87,8 @@ def save_checkpoint(path_to_job, model, optimizer, epoch, cfg, scaler=None):
         # dict: the bf16 path needs no loss scaling, so write a fresh scaler's state
         "scaler_state": scaler.state_dict() if scaler is not None else dict(DEFAULT_SCALER_STATE),
     }
+    if ema is not None:
+        checkpoint["ema_state"] = _to_cpu(ema.state_dict())
     path = get_path_to_checkpoint(path_to_job, epoch + 1)
     with open(path, "wb") as f:
         torch.save(checkpoint, f)
@@ -93,17 +97,24 @@ def save_checkpoint(path_to_job, model, optimizer, epoch, cfg, scaler=None):
 
 def load_checkpoint(path_to_checkpoint, model, data_parallel=True, optimizer=None, scaler=None,
                     inflation=False, convert_from_caffe2=False, epoch_reset=False,
-                    clear_name_pattern=(), replace_name_pattern=(), should_split_qkv=False):
+                    clear_name_pattern=(), replace_name_pattern=(), should_split_qkv=False, ema=None, use_ema=False):
     """checkpoint.py:198-385 for PyTorch checkpoints: optional renaming, then every tensor whose
     name AND shape match the model is loaded (the rest keeps its initialisation), then -- unless
-    `epoch_reset` -- the optimizer moments.  Returns the checkpoint's epoch, or -1."""
+    `epoch_reset` -- the optimizer moments.  Returns the checkpoint's epoch, or -1.
+    ema: an ema.WeightEMA over `model` -- after weights and optimizer, the file's "ema_state" is loaded into it (the count
+    of updates continues); a file without the key (a pretrained checkpoint, a run without EMA) makes it start over from
+    the loaded weights (`ema.reset()`).
+    use_ema: the MODEL takes the averaged weights, ema_state["model_state"], in place of "model_state" (testing a
+    checkpoint with its average); KeyError naming the file when it holds none."""
     assert os.path.exists(path_to_checkpoint), "Checkpoint '{}' not found".format(path_to_checkpoint)
     if inflation or convert_from_caffe2 or should_split_qkv:
         raise NotImplementedError("2-D inflation / caffe2 / split-qkv conversions are outside the SViT path")
     ms = model.module if data_parallel else model
     with open(path_to_checkpoint, "rb") as f:
         checkpoint = torch.load(f, map_location="cpu", weights_only=False)
-    pre = checkpoint["model_state"]
+    if use_ema and "ema_state" not in checkpoint:
+        raise KeyError("use_ema=True: '%s' holds no \"ema_state\" (it was saved without an EMA)" % path_to_checkpoint)
+    pre = checkpoint["ema_state"]["model_state"] if use_ema else checkpoint["model_state"]
     for item in clear_name_pattern:
         pre = OrderedDict((k.replace(item, "") if item in k else k, v) for k, v in pre.items())
     if len(replace_name_pattern) > 0:
@@ -126,4 +137,9 @@ def load_checkpoint(path_to_checkpoint, model, data_parallel=True, optimizer=Non
             optimizer.load_state_dict(checkpoint["optimizer_state"])
         if scaler:
             scaler.load_state_dict(checkpoint["scaler_state"])
+    if ema is not None:         # (behind the optimizer: the offset is taken against its count of applied steps)
+        if "ema_state" in checkpoint:
+            ema.load_state_dict(checkpoint["ema_state"])
+        else:
+            ema.reset()
     return epoch

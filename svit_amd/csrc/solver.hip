@@ -20,6 +20,9 @@
 // finds the ranges a window meets, the loop over them is workgroup-uniform and a lane keeps the values of the one range
 // that holds its quad.  Bounds are multiples of 4 and no range crosses n_decay: a quad is inside one range whole or
 // outside all, and has one learning rate and one weight decay.  Nothing outside the ranges is loaded or stored.
+//
+// svit_ema_step_guarded is the third kernel on that walk: the exponential moving average of the weights, launched
+// behind whichever solver stepped them (AdamW's included), bit for bit svit_amd/ema.py's ema_step_host.
 #include <cstring>
 
 #include "common.h"
@@ -188,7 +191,62 @@ __global__ __launch_bounds__(256) void adam_guarded_kernel(float* __restrict__ p
   }
 }
 
+// ---- exponential moving average of the weights behind a solver (svit_ema_step_guarded) --------------------------------
+// is the quad at float index i of the window [lo, hi) inside a range?  range_rates without the rates
+__device__ __forceinline__ bool range_holds(const RangeTable& T, int& k, int64_t lo, int64_t hi, int64_t i) {
+  while (k < T.S && T.v[k][1] <= lo) ++k;
+  bool in = false;
+  for (int j = k; j < T.S && T.v[j][0] < hi; ++j) in |= (i >= T.v[j][0]) & (i < T.v[j][1]);
+  return in;
+}
+
+__device__ __forceinline__ float ema_update(float e, float pw, float d, float omd) {
+  return add_rn(mul_rn(e, d), mul_rn(pw, omd));
+}
+
+// 12 B per parameter: p read, ema read and written.  The update number is the guard's counter plus the host's offset:
+// no workgroup writes anything its neighbours read.  Record, offset and table entry sit at workgroup-uniform addresses.
+__global__ __launch_bounds__(256) void ema_guarded_kernel(float* __restrict__ ema, const float* __restrict__ p, int64_t n,
+                                                          const float* __restrict__ table, int64_t entries, float decay,
+                                                          const int64_t* __restrict__ er,
+                                                          const svit_step_dev* __restrict__ d, const RangeTable T) {
+  if (d->apply == 0) return;
+  int64_t upd = d->applied + er[0];
+  upd = upd < 1 ? 1 : upd;
+  const float dk = upd <= entries ? table[upd - 1] : decay;
+  const float omd = sub_rn(1.0f, dk);
+  const int64_t window = (int64_t)blockDim.x * 4, stride = (int64_t)gridDim.x * window;
+  int k = 0;
+  for (int64_t lo = (int64_t)blockIdx.x * window; lo < n; lo += stride) {
+    const int64_t i = lo + (int64_t)threadIdx.x * 4;
+    if (!range_holds(T, k, lo, lo + window, i)) continue;
+    const int64_t q = i >> 2;
+    float4 E = ((const float4*)ema)[q];
+    const float4 P = ((const float4*)p)[q];
+    E.x = ema_update(E.x, P.x, dk, omd);
+    E.y = ema_update(E.y, P.y, dk, omd);
+    E.z = ema_update(E.z, P.z, dk, omd);
+    E.w = ema_update(E.w, P.w, dk, omd);
+    ((float4*)ema)[q] = E;
+  }
+}
+
+// 0 < decay < 1, by the bits (positive floats order as their bit patterns; a NaN, an inf and every negative lie above 1.0)
+inline bool ema_decay_ok(float decay) {
+  uint32_t bits;
+  memcpy(&bits, &decay, sizeof bits);
+  return bits > 0u && bits < 0x3f800000u;
+}
+
+// entry k - 1 of the warm-up table, on the HOST in IEEE double arithmetic whatever the build's flags
+inline float ema_warmup_decay(float decay, int64_t k) {
+#pragma float_control(precise, on)
+  const double w = (1.0 + (double)k) / (10.0 + (double)k), dd = (double)decay;
+  return (float)(dd < w ? dd : w);
+}
+
 // the checks of svit_adamw_step_guarded_lr, with its error codes, before any HIP call; the tables in kernel-argument form
+// (n_decay < 0: no weight-decay boundary to respect)
 int range_table_take(const int64_t* segs, const float* scales, int64_t S, int64_t n, int64_t n_decay, RangeTable* out) {
   if (!segs || S < 1 || S > SVIT_MAX_SEGS) return SVIT_ERR_ARG;
   int64_t prev = 0;
@@ -239,6 +297,39 @@ extern "C" int svit_sgd_step_guarded(float* p, const float* g, float* buf, int64
   else
     hipLaunchKernelGGL(sgd_guarded_kernel<false>, dim3(solver_grid(span)), dim3(256), 0, (hipStream_t)stream, p, g,
                        (float*)nullptr, span, n_decay, host_rec, dev_rec, momentum, omd, nesterov, T);
+  SVIT_LAUNCH_CHECK();
+  return SVIT_OK;
+}
+
+extern "C" int svit_ema_decay_table(float decay, float* table, int64_t capacity, int64_t* n_entries) {
+  if (!n_entries || (table && capacity < 0) || !ema_decay_ok(decay)) return SVIT_ERR_ARG;
+  constexpr int64_t kMax = 1ll << 20;
+  for (int64_t k = 1; k <= kMax; ++k) {
+    const float e = ema_warmup_decay(decay, k);
+    if (table) {
+      if (k > capacity) return SVIT_ERR_ARG;
+      table[k - 1] = e;
+    }
+    if (e == decay) {
+      *n_entries = k;
+      return SVIT_OK;
+    }
+  }
+  return SVIT_ERR_ARG;
+}
+
+extern "C" int svit_ema_step_guarded(float* ema, const float* p, int64_t n, const int64_t* segs, int64_t S,
+                                     const float* decay_table, int64_t table_entries, float decay,
+                                     const int64_t* ema_rec, const svit_step_dev* dev_rec, void* stream) {
+  if (!ema || !p || !ema_rec || !dev_rec || n <= 0 || !ema_decay_ok(decay)) return SVIT_ERR_ARG;
+  if (table_entries < 0 || table_entries > (1ll << 20) || (table_entries > 0 && !decay_table)) return SVIT_ERR_ARG;
+  RangeTable T;
+  if (int rc = range_table_take(segs, nullptr, S, n, -1, &T)) return rc;
+  if (((uintptr_t)ema | (uintptr_t)p) & 15) return SVIT_ERR_ALIGN;
+  if (((uintptr_t)ema_rec | (uintptr_t)dev_rec) & 7 || ((uintptr_t)decay_table & 3)) return SVIT_ERR_ALIGN;
+  const int64_t span = T.v[S - 1][1];
+  hipLaunchKernelGGL(ema_guarded_kernel, dim3(solver_grid(span)), dim3(256), 0, (hipStream_t)stream, ema, p, span,
+                     decay_table, table_entries, decay, ema_rec, dev_rec, T);
   SVIT_LAUNCH_CHECK();
   return SVIT_OK;
 }

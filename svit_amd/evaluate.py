@@ -289,7 +289,7 @@ _END = object()
 
 
 @torch.no_grad()
-def perform_test(test_loader, model, test_meter, cfg, dedupe=True, force_collectives=False, feeder=None):
+def perform_test(test_loader, model, test_meter, cfg, dedupe=True, force_collectives=False, feeder=None, ema=None):
     """tools/test_net.py:25-170, classification branch.  `test_loader` yields
     (inputs, labels, video_idx, meta) like the reference's loader; with `dedupe` it is expected to
     yield only the unique views (clip index = video * NUM_SPATIAL_CROPS + crop) and the meter is
@@ -297,7 +297,12 @@ def perform_test(test_loader, model, test_meter, cfg, dedupe=True, force_collect
     model: the model, or a graph.GraphedEvalStep built with `test_meter=` this meter and `repeat=` the fold count used
     here -- the loader then yields device-side (inputs, {"labels", "clip_ids"}, ...) and an iteration is one replay
     (`run_eval_step`); with `feeder` (a feeder.ClipFeeder over the step) it yields HOST batches (videos, records,
-    {"labels", "clip_ids"}, video_idx, meta) and uploads overlap the step."""
+    {"labels", "clip_ids"}, video_idx, meta) and uploads overlap the step.
+    ema: an ema.WeightEMA over this model -- the test runs inside `ema.average_weights()`, on the averaged weights."""
+    if ema is not None:
+        with ema.average_weights():
+            return perform_test(test_loader, model, test_meter, cfg, dedupe=dedupe, force_collectives=force_collectives,
+                                feeder=feeder)
     repeat = unique_views(cfg)[1] if dedupe else 1
     ks = (1, 5) if cfg.MODEL.NUM_CLASSES > 5 else (1, 1)
     from .graph import GraphedEvalStep

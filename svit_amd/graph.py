@@ -118,6 +118,8 @@ class GraphedTrainStep:
             raise hip.SvitHipError("GraphedTrainStep(optimizer=...): the optimizer was built when the parameters' "
                                    "requires_grad flags froze everything below position %d, now they say %d -- rebuild "
                                    "the optimizer" % (optimizer.cut, self.cut))
+        # the ema.WeightEMA attached to the optimizer NOW: its launch ends the captured tail (or none does)
+        self._ema = optimizer.ema if optimizer is not None else None
         self.loss_fun = loss_fun
         self.dp = model if hasattr(model, "_on_ready") and (getattr(model, "world_size", 1) > 1 or
                                                            getattr(model, "force_collectives", False)) else None
@@ -316,6 +318,8 @@ class GraphedTrainStep:
         if [p.requires_grad for p in self._flag_params] != self._flags:
             raise hip.SvitHipError("a parameter's requires_grad changed after this GraphedTrainStep was captured (it "
                                    "froze everything below position %d): rebuild the optimizer and the step" % self.cut)
+        if self.optimizer is not None:
+            _check_ema(self.optimizer, self._ema, "GraphedTrainStep")
 
     def check_batch(self, inputs):
         """refuse a batch the capture does not fit (before anything is enqueued)"""
@@ -456,6 +460,7 @@ class AccumulatedTrainStep:
                                        "optimizer with %d: rebuild them over the same requires_grad flags"
                                        % (i, ms.cut, optimizer.cut))
         self.optimizer = optimizer
+        self._ema = optimizer.ema           # (the tail is eager, but a step is built for one recipe: as the freeze flags)
         self.meter = meter
         if meter is not None:
             if getattr(meter, "virtual_ranks", None) != k:
@@ -474,6 +479,7 @@ class AccumulatedTrainStep:
         if len(batches) != self.k:
             raise hip.SvitHipError("AccumulatedTrainStep holds %d micro-steps, got %d batches" % (self.k, len(batches)))
         self.micro_steps[0].check_flags()       # (every micro-step holds the optimizer's cut)
+        _check_ema(self.optimizer, self._ema, "AccumulatedTrainStep")
         for i, (ms, b) in enumerate(zip(self.micro_steps, batches)):
             if _is_feeder(b):
                 if b.target is not ms.x:
@@ -713,6 +719,14 @@ class GraphedEvalStep:
     @property
     def static_labels(self):
         return self.labels
+
+
+def _check_ema(optimizer, ema, what):
+    """refuse a replay after another ema.WeightEMA (or none) was attached to the optimizer than the step was built with"""
+    if optimizer.ema is not ema:
+        raise hip.SvitHipError("the optimizer's attached WeightEMA changed after this %s was built (%s then, %s now): its "
+                               "tail holds the launches of then -- rebuild the step"
+                               % (what, "one" if ema is not None else "none", "one" if optimizer.ema is not None else "none"))
 
 
 def _is_feeder(batch):

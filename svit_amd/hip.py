@@ -212,6 +212,8 @@ _SIGS = {
     "svit_adamw_step_guarded_lr": (i32, [vp, vp, vp, vp, i64, i64, vp, vp, i64, vp, vp, f32, f32, f32, vp]),
     "svit_sgd_step_guarded": (i32, [vp, vp, vp, i64, i64, vp, vp, i64, vp, vp, f32, f32, i32, vp]),
     "svit_adam_step_guarded": (i32, [vp, vp, vp, vp, i64, i64, vp, vp, i64, vp, vp, f32, f32, f32, vp]),
+    "svit_ema_decay_table": (i32, [f32, vp, i64, C.POINTER(i64)]),             # host only: no stream argument
+    "svit_ema_step_guarded": (i32, [vp, vp, i64, vp, i64, vp, i64, f32, vp, vp, vp]),
     "svit_head_fwd": (i32, [C.POINTER(HeadArgs), vp]),
     "svit_head_bwd": (i32, [C.POINTER(HeadBwdArgs), vp]),
     "svit_head_eval": (i32, [C.POINTER(HeadArgs), i32, vp]),

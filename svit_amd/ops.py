@@ -1005,6 +1005,41 @@ def adam_step_guarded(p, g, m, v, n_decay, segs, scales, host_rec, dev_rec, beta
              ptr(dev_rec), beta1, beta2, eps)
 
 
+def ema_decay_table(decay):
+    """the warm-up decays of updates 1, 2, ...: min(decay, (1 + k) / (10 + k)) up to the first update that takes `decay`
+    itself, float32 numpy [entries] (svit_ema_decay_table; host only, needs no device)"""
+    import numpy as np
+    lib = hip.load()
+    n = C.c_int64(0)
+    hip.check(lib.svit_ema_decay_table(decay, None, 0, C.byref(n)), "svit_ema_decay_table (decay %r)" % (decay,))
+    buf = np.empty(n.value, dtype=np.float32)
+    hip.check(lib.svit_ema_decay_table(decay, buf.ctypes.data, n.value, C.byref(n)),
+              "svit_ema_decay_table (decay %r)" % (decay,))
+    return buf
+
+
+def ema_step_guarded(ema, p, segs, table, decay, ema_rec, dev_rec):
+    """ema = ema * d + p * (1 - d) on the ranges of `segs` when the step record says the step was applied, nothing on a
+    dropped step (svit_ema_step_guarded).  table: the warm-up decays as a float32 device tensor [entries], or None for
+    the constant `decay`; ema_rec: int64 [2] on the device, {offset, reserved}; dev_rec: the guard's int32 [12]"""
+    _chk_dev(ema, p, ema_rec, dev_rec)
+    dev = p.device
+    if ema.numel() != p.numel() or ema.dtype != F32 or p.dtype != F32 or ema.device != dev:
+        raise hip.SvitHipError("ema_step_guarded: ema and p are fp32 buffers of one size on one device")
+    if (ema_rec.dtype != torch.int64 or ema_rec.numel() != 2 or dev_rec.dtype != torch.int32 or dev_rec.numel() != 12
+            or ema_rec.device != dev or dev_rec.device != dev):
+        raise hip.SvitHipError("ema_step_guarded: the records are int64 [2] + int32 [12] on %s" % (dev,))
+    entries = 0
+    if table is not None:
+        _chk_dev(table)
+        if table.dtype != F32 or table.dim() != 1 or table.device != dev:
+            raise hip.SvitHipError("ema_step_guarded: the decay table is a float32 tensor [entries] on %s" % (dev,))
+        entries = table.numel()
+    sp, S = _chk_segs(segs)
+    hip.call("svit_ema_step_guarded", ptr(ema), ptr(p), p.numel(), sp, S, ptr(table) if entries else None, entries, decay,
+             ptr(ema_rec), ptr(dev_rec))
+
+
 # ---------------------------------------------------------------- head (K15) ----------------
 def _head_args(tokens, T, O, keep, head_params, outs):
     a = hip.HeadArgs()

@@ -247,6 +247,8 @@ class GuardedClipAdamW(FusedClipAdamW):
     reference's check_nan_losses (a NaN loss gives NaN gradients, thus a dropped step).  None: never raises."""
 
     RING = 16
+    ema = None          # the ema.WeightEMA `attach_ema` hung behind the step: every enqueue() ends with its launch
+    _averaged = None    # the ema.WeightEMA whose average stands in the weights' place (ema.average_weights()): no step
 
     def __init__(self, model, lr, weight_decay=1e-4, betas=(0.9, 0.999), eps=1e-8, clip_grad_l2norm=None,
                  grad_scale=1.0, clip_grad_value=None, max_consecutive_skips=None, lr_scale=None):
@@ -300,6 +302,10 @@ class GuardedClipAdamW(FusedClipAdamW):
     def upload(self):
         """send this step's lr / weight decay / clip bounds / grad scale, in stream order, without stalling the host:
         a ring of pinned slots, each guarded by the event of the copy that last read it"""
+        if self._averaged is not None:
+            raise RuntimeError("the weights hold their moving average (inside WeightEMA.average_weights()): an optimizer "
+                               "step or a replay of the training step here would train the average -- leave the context "
+                               "first")
         if self._slots is None:
             self._slots = torch.empty((self.RING, 8), dtype=torch.float32).pin_memory()
         i = self._next
@@ -312,8 +318,23 @@ class GuardedClipAdamW(FusedClipAdamW):
         ev.record(torch.cuda.current_stream(self.host_rec.device))
         self._events[i] = ev
 
+    def attach_ema(self, ema):
+        """ema: an ema.WeightEMA built over this optimizer -- every `enqueue()` from now on ends with its launch (one
+        more, behind the solver's), so the eager step, a GraphedTrainStep(optimizer=) captured AFTERWARDS and an
+        AccumulatedTrainStep carry the average along; a step captured before refuses its replay.  None: detach."""
+        if ema is not None and getattr(ema, "optimizer", None) is not self:
+            raise ValueError("attach_ema: the WeightEMA was built over another optimizer (its update count is derived "
+                             "from that optimizer's step record)")
+        self.ema = ema
+
     def enqueue(self):
-        """the three launches; allocation-free and capturable"""
+        """the three launches (and the attached average's one); allocation-free and capturable"""
+        self._solve()
+        if self.ema is not None:
+            self.ema.enqueue()
+
+    def _solve(self):
+        """the guard and the solver's launch"""
         f = self.flat
         self._guard()
         if self.lr_segments is not None:    # learning-rate scales: AdamW over the scaled ranges
@@ -435,7 +456,7 @@ class _GuardedRangeSolver(GuardedClipAdamW):
         """the solver's launch on p, g and `state` (one buffer per entry of STATE) with the step record `rec`"""
         raise NotImplementedError
 
-    def enqueue(self):
+    def _solve(self):
         """the guard's two launches and the solver's one; allocation-free and capturable"""
         f = self.flat
         self._guard()
@@ -494,9 +515,9 @@ class GuardedClipSGD(_GuardedRangeSolver):
 
 
 def construct_optimizer(model, cfg):
-    """slowfast/models/optimizer.py:15-112.  `adamw`: the fused tail, guarded with SOLVER.CLIP_GRAD_VAL or the opt-in
-    SVIT.GUARDED_STEP (not a key of the default tree, like SVIT.REPRODUCIBLE).  `sgd` and `adam`: always the guarded
-    tail (GuardedClipSGD / GuardedClipAdam)."""
+    """slowfast/models/optimizer.py:15-112.  `adamw`: the fused tail, guarded with SOLVER.CLIP_GRAD_VAL, the opt-in
+    SVIT.GUARDED_STEP or SVIT.EMA_DECAY (neither a key of the default tree, like SVIT.REPRODUCIBLE).  `sgd` and `adam`:
+    always the guarded tail (GuardedClipSGD / GuardedClipAdam)."""
     s = cfg.SOLVER
     if not s.ZERO_WD_1D_PARAM:
         raise NotImplementedError("svit_amd lays its flat buffers out for SOLVER.ZERO_WD_1D_PARAM: True")
@@ -510,7 +531,9 @@ def construct_optimizer(model, cfg):
         if s.OPTIMIZING_METHOD == "sgd":
             return GuardedClipSGD(model, momentum=s.MOMENTUM, dampening=s.DAMPENING, nesterov=s.NESTEROV, **common)
         return GuardedClipAdam(model, betas=(0.9, 0.999), eps=1e-8, **common)
-    if getattr(cfg.SVIT, "GUARDED_STEP", False) or cfg.SOLVER.CLIP_GRAD_VAL:
+    # (SVIT.EMA_DECAY: the moving average's update count is derived from the guarded tail's step record, svit_amd/ema.py)
+    if (getattr(cfg.SVIT, "GUARDED_STEP", False) or cfg.SOLVER.CLIP_GRAD_VAL
+            or getattr(cfg.SVIT, "EMA_DECAY", None) is not None):
         return GuardedClipAdamW(model, lr=cfg.SOLVER.BASE_LR, weight_decay=cfg.SOLVER.WEIGHT_DECAY,
                                 clip_grad_l2norm=cfg.SOLVER.CLIP_GRAD_L2NORM, clip_grad_value=cfg.SOLVER.CLIP_GRAD_VAL,
                                 max_consecutive_skips=getattr(cfg.SVIT, "MAX_CONSECUTIVE_SKIPS", None),

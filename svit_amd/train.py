@@ -249,13 +249,18 @@ def _eval_epoch_step(val_loader, step, val_meter, cur_epoch, cfg, feeder):
 
 
 @torch.no_grad()
-def eval_epoch(val_loader, model, val_meter, cur_epoch, cfg, feeder=None):
+def eval_epoch(val_loader, model, val_meter, cur_epoch, cfg, feeder=None, ema=None):
     """tools/train_net.py:181-368, classification branch: per iteration one forward and one meter push (top-k hits and
     the extra losses), no host read between periods.
+    ema: an ema.WeightEMA over this model -- the epoch runs inside `ema.average_weights()`, i.e. on the averaged weights
+    (the raw ones are back, bit for bit, when it returns).  None: the loop below on the weights as they are.
     model: the model, or a graph.GraphedEvalStep built with `cfg=`, `val_meter=` this meter and the frames pass
     cfg.TRAIN.FORWARD_VIDEO_FRAMES asks for -- the loader then yields device-side (inputs, labels, ...); with `feeder` (a
     feeder.ClipFeeder over the step's static AugClips) it yields HOST batches (videos, records, labels, video_idx,
     meta) and uploads overlap the step."""
+    if ema is not None:
+        with ema.average_weights():
+            return eval_epoch(val_loader, model, val_meter, cur_epoch, cfg, feeder=feeder)
     if isinstance(model, GraphedEvalStep):
         return _eval_epoch_step(val_loader, model, val_meter, cur_epoch, cfg, feeder)
     if feeder is not None:
