@@ -603,6 +603,67 @@ typedef struct {
   float coef, bc1, bc2_sqrt, sumsq, grad_norm, reserved;
 } svit_step_dev;
 
+/* Per-tensor statistics of the flat gradient and weight buffers, taken INSIDE the step (svit_amd/monitor.py): two
+ * launches between the guard and the solver's launch, so g and dev_rec are this step's and p still holds the weights the
+ * gradient was taken at.  They write one row of a ring in device memory; the host reads the ring once per logging period.
+ *
+ * The ring is plain memory, R rows of 16 + 32 * Tn bytes, 16-byte aligned; the HOST writes all of it when it is created
+ * and when it is reset (step = -1, n_bad = -1, first_bad = -1, everything else 0), the kernels write recorded rows.
+ *   row header, 16 bytes
+ *     offset  0  int64 step        the step the row holds, s below; -1: never written
+ *     offset  8  int32 apply       dev_rec->apply of that step: 1 applied, 0 dropped
+ *     offset 12  int32 reserved    0
+ *   entry of tensor t at offset 16 + 32 * t, 32 bytes
+ *     offset  0  double sumsq_g    sum of g^2 over the tensor's FINITE elements, accumulated in fp64
+ *     offset  8  double sumsq_p    sum of p^2 over the tensor, accumulated in fp64
+ *     offset 16  float absmax_g    largest |g| among the finite elements, 0 when there is none
+ *     offset 20  int32 n_bad       number of non-finite elements of g (NaN, +inf, -inf); -1: the tensor is frozen and the
+ *                                  entry has never been written
+ *     offset 24  int32 first_bad   smallest in-tensor offset of a non-finite element of g, -1 when there is none
+ *     offset 28  int32 reserved    0
+ * A finite gradient whose fp32 sum of squares overflows (the guard then drops the step) still has a finite sumsq_g.
+ *
+ * The tensor table: int64 [Tn][2] of (begin, end) float positions, one row per tensor, 1 <= Tn <= 4096, ascending and
+ * disjoint (begin >= the previous end), no empty tensor, fewer than 2^31 elements each, end <= n, every begin a multiple
+ * of 4 (the flat layout aligns slots to 8 floats; an end may be anything).  What lies between two tensors is alignment
+ * padding and is never counted.  svit_tensor_table_check, HOST ONLY (no stream, no launch), checks a table in host
+ * memory: SVIT_ERR_ARG for a NULL table, Tn or n out of range, an unsorted, overlapping, empty or oversized tensor or an
+ * end past n; SVIT_ERR_ALIGN for a begin that is not a multiple of 4.
+ *
+ * svit_tensor_stats: g, p f32 [n], 16-byte aligned.  table_dev is the table in DEVICE memory (405 pairs and more do not
+ * fit the kernel arguments), written once by the caller; table_host is the same table in host memory, checked here by
+ * svit_tensor_table_check before any HIP call and not kept.  segs / S: the optimizer's trainable segments IN HOST MEMORY
+ * (svit_adamw_step_guarded_seg's table, its rules and error codes, carried in the kernel arguments); S == 0, segs then
+ * ignored: the whole buffer.  A tensor whose begin lies in no segment is frozen: neither loaded nor written, its entry
+ * keeps what the host wrote.  EXACTLY two launches, no allocation, copy or synchronisation: capturable.
+ *   step index   s = dev_rec->applied + dev_rec->skipped - 1, read on the device from the record the guard in front has
+ *                already advanced: no kernel here advances a counter that its own workgroups read.
+ *   recorded     when s % every == 0 or dev_rec->apply == 0 (a dropped step is always recorded), into row s % R.
+ *                Otherwise every workgroup of both launches returns before its first load of g or p and the ring is
+ *                untouched.
+ *   stage 1      one workgroup per window of svit_tensor_stats_window() = 4096 floats, 16-byte loads (issued first, for
+ *                the quads inside a segment: segments hold whole tensors), then a workgroup-uniform walk of the table
+ *                from the first tensor that ends past the window's begin (found by bisection) with a cursor that only
+ *                moves forward.  Every (window, tensor) piece leaves ONE 32-byte partial in `workspace`
+ *                at slot window + tensor, which no other piece shares; svit_tensor_stats_workspace(n, Tn), HOST ONLY,
+ *                returns the bytes of the ceil(n / 4096) + Tn slots (SVIT_ERR_ARG, negative, for n or Tn out of range).
+ *   stage 2      one wave per tensor: lane l adds the partials of the tensor's windows l, l + 64, ... in ascending
+ *                order, the 64 lanes combine in a fixed butterfly, lane 0 writes the entry; the wave of tensor 0 also
+ *                writes the header.
+ * An element of g is non-finite when its exponent bits are all ones; such an element enters neither sumsq_g nor absmax_g.
+ * The maximum is taken on the integer image of |g|.  (double) x * (double) x is exact, only the fp64 additions round:
+ * against svit_amd/monitor.py stats_host both sums of squares agree to 2^-30 relative, everything else exactly.  No
+ * atomics and no ticket: the row is bit-identical from run to run and from the eager step to a replay.
+ * SVIT_ERR_ARG besides the tables': a NULL g, p, table_dev, dev_rec, ring or workspace; R < 1; every < 1; workspace_bytes
+ * below svit_tensor_stats_workspace(n, Tn).  SVIT_ERR_ALIGN: g, p, ring or workspace not 16-byte aligned, table_dev or
+ * dev_rec not 8-byte aligned.  All checked before any HIP call.  The ring's size is the caller's to get right. */
+int svit_tensor_stats_window(void);
+int svit_tensor_table_check(const int64_t* table, int64_t Tn, int64_t n);
+int64_t svit_tensor_stats_workspace(int64_t n, int64_t Tn);
+int svit_tensor_stats(const float* g, const float* p, int64_t n, const int64_t* table_dev, const int64_t* table_host,
+                      int64_t Tn, const int64_t* segs, int64_t S, const svit_step_dev* dev_rec, void* ring, int64_t R,
+                      int64_t every, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* HOST ONLY (no stream, no launch): the bias corrections svit_adamw_step derives from its `step` argument, by the very
  * same host code: pair k-1 = (1 - powf(beta1, k), sqrtf(1 - powf(beta2, k))) for steps k = 1, 2, ... up to and including
  * the first step at which both values are exactly 1.0f; past the table both are 1.0f.  *n_entries receives that length

@@ -120,6 +120,8 @@ class GraphedTrainStep:
                                    "the optimizer" % (optimizer.cut, self.cut))
         # the ema.WeightEMA attached to the optimizer NOW: its launch ends the captured tail (or none does)
         self._ema = optimizer.ema if optimizer is not None else None
+        # ... and the monitor.TensorMonitor attached NOW: its two launches sit between the guard and the solver's
+        self._monitor = optimizer.monitor if optimizer is not None else None
         self.loss_fun = loss_fun
         self.dp = model if hasattr(model, "_on_ready") and (getattr(model, "world_size", 1) > 1 or
                                                            getattr(model, "force_collectives", False)) else None
@@ -320,6 +322,7 @@ class GraphedTrainStep:
                                    "froze everything below position %d): rebuild the optimizer and the step" % self.cut)
         if self.optimizer is not None:
             _check_ema(self.optimizer, self._ema, "GraphedTrainStep")
+            _check_monitor(self.optimizer, self._monitor, "GraphedTrainStep")
 
     def check_batch(self, inputs):
         """refuse a batch the capture does not fit (before anything is enqueued)"""
@@ -461,6 +464,7 @@ class AccumulatedTrainStep:
                                        % (i, ms.cut, optimizer.cut))
         self.optimizer = optimizer
         self._ema = optimizer.ema           # (the tail is eager, but a step is built for one recipe: as the freeze flags)
+        self._monitor = optimizer.monitor
         self.meter = meter
         if meter is not None:
             if getattr(meter, "virtual_ranks", None) != k:
@@ -480,6 +484,7 @@ class AccumulatedTrainStep:
             raise hip.SvitHipError("AccumulatedTrainStep holds %d micro-steps, got %d batches" % (self.k, len(batches)))
         self.micro_steps[0].check_flags()       # (every micro-step holds the optimizer's cut)
         _check_ema(self.optimizer, self._ema, "AccumulatedTrainStep")
+        _check_monitor(self.optimizer, self._monitor, "AccumulatedTrainStep")
         for i, (ms, b) in enumerate(zip(self.micro_steps, batches)):
             if _is_feeder(b):
                 if b.target is not ms.x:
@@ -727,6 +732,16 @@ def _check_ema(optimizer, ema, what):
         raise hip.SvitHipError("the optimizer's attached WeightEMA changed after this %s was built (%s then, %s now): its "
                                "tail holds the launches of then -- rebuild the step"
                                % (what, "one" if ema is not None else "none", "one" if optimizer.ema is not None else "none"))
+
+
+def _check_monitor(optimizer, monitor, what):
+    """refuse a replay after another monitor.TensorMonitor (or none) was attached to the optimizer than the step was built
+    with"""
+    if optimizer.monitor is not monitor:
+        raise hip.SvitHipError("the optimizer's attached TensorMonitor changed after this %s was built (%s then, %s now): "
+                               "its tail holds the launches of then -- rebuild the step"
+                               % (what, "one" if monitor is not None else "none",
+                                  "one" if optimizer.monitor is not None else "none"))
 
 
 def _is_feeder(batch):

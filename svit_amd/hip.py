@@ -214,6 +214,10 @@ _SIGS = {
     "svit_adam_step_guarded": (i32, [vp, vp, vp, vp, i64, i64, vp, vp, i64, vp, vp, f32, f32, f32, vp]),
     "svit_ema_decay_table": (i32, [f32, vp, i64, C.POINTER(i64)]),             # host only: no stream argument
     "svit_ema_step_guarded": (i32, [vp, vp, i64, vp, i64, vp, i64, f32, vp, vp, vp]),
+    "svit_tensor_stats_window": (i32, []),                                     # host only, like the next two
+    "svit_tensor_table_check": (i32, [vp, i64, i64]),
+    "svit_tensor_stats_workspace": (i64, [i64, i64]),
+    "svit_tensor_stats": (i32, [vp, vp, i64, vp, vp, i64, vp, i64, vp, vp, i64, i64, vp, i64, vp]),
     "svit_head_fwd": (i32, [C.POINTER(HeadArgs), vp]),
     "svit_head_bwd": (i32, [C.POINTER(HeadBwdArgs), vp]),
     "svit_head_eval": (i32, [C.POINTER(HeadArgs), i32, vp]),

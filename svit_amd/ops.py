@@ -1040,6 +1040,56 @@ def ema_step_guarded(ema, p, segs, table, decay, ema_rec, dev_rec):
              ptr(ema_rec), ptr(dev_rec))
 
 
+def tensor_stats_window():
+    """floats per window of svit_tensor_stats' first stage (host only)"""
+    return int(hip.load().svit_tensor_stats_window())
+
+
+def _chk_tensor_table(table):
+    import numpy as np
+    if not (isinstance(table, np.ndarray) and table.dtype == np.int64 and table.ndim == 2 and table.shape[1] == 2
+            and table.flags["C_CONTIGUOUS"]):
+        raise hip.SvitHipError("the tensor table is a C-contiguous int64 numpy array [Tn, 2]")
+    return table.ctypes.data, table.shape[0]
+
+
+def tensor_table_check(table, n):
+    """svit_tensor_table_check: raises for a table the statistics kernels would refuse (host only, needs no device)"""
+    tp, Tn = _chk_tensor_table(table)
+    hip.check(hip.load().svit_tensor_table_check(tp, Tn, n), "svit_tensor_table_check (%d tensors, n = %d)" % (Tn, n))
+
+
+def tensor_stats_workspace(n, Tn):
+    """bytes of svit_tensor_stats' workspace for a buffer of n floats behind Tn tensors (host only)"""
+    b = int(hip.load().svit_tensor_stats_workspace(n, Tn))
+    if b < 0:
+        hip.check(b, "svit_tensor_stats_workspace (n = %d, %d tensors)" % (n, Tn))
+    return b
+
+
+def tensor_stats(g, p, table_dev, table_host, segs, dev_rec, ring, R, every, workspace):
+    """per-tensor sums of squares of g and p, max |g|, count and first offset of the non-finite elements of g into row
+    (step % R) of `ring`, when the step record says the step is due or was dropped (svit_tensor_stats; two launches).
+    table_dev: int64 [Tn, 2] on the device, table_host: the same as numpy; segs: the trainable segments as numpy or None;
+    ring: uint8 [R * (16 + 32 * Tn)] and workspace: uint8, both on the device"""
+    _chk_dev(g, p, table_dev, dev_rec, ring, workspace)
+    dev = g.device
+    tp, Tn = _chk_tensor_table(table_host)
+    if g.numel() != p.numel() or g.dtype != F32 or p.dtype != F32 or p.device != dev:
+        raise hip.SvitHipError("tensor_stats: g and p are fp32 buffers of one size on one device")
+    if table_dev.dtype != torch.int64 or tuple(table_dev.shape) != (Tn, 2) or table_dev.device != dev:
+        raise hip.SvitHipError("tensor_stats: the device table is int64 [%d, 2] on %s, as the host's" % (Tn, dev))
+    if dev_rec.dtype != torch.int32 or dev_rec.numel() != 12 or dev_rec.device != dev:
+        raise hip.SvitHipError("tensor_stats: the step record is int32 [12] on %s" % (dev,))
+    if (ring.dtype != torch.uint8 or workspace.dtype != torch.uint8 or ring.device != dev or workspace.device != dev
+            or R < 1 or ring.numel() != R * (16 + 32 * Tn)):
+        raise hip.SvitHipError("tensor_stats: the ring is uint8 [R * (16 + 32 * %d)] and the workspace uint8, on %s"
+                               % (Tn, dev))
+    sp, S = (None, 0) if segs is None else _chk_segs(segs)
+    hip.call("svit_tensor_stats", ptr(g), ptr(p), g.numel(), ptr(table_dev), tp, Tn, sp, S, ptr(dev_rec), ptr(ring), R,
+             every, ptr(workspace), workspace.numel())
+
+
 # ---------------------------------------------------------------- head (K15) ----------------
 def _head_args(tokens, T, O, keep, head_params, outs):
     a = hip.HeadArgs()

@@ -249,6 +249,7 @@ class GuardedClipAdamW(FusedClipAdamW):
     RING = 16
     ema = None          # the ema.WeightEMA `attach_ema` hung behind the step: every enqueue() ends with its launch
     _averaged = None    # the ema.WeightEMA whose average stands in the weights' place (ema.average_weights()): no step
+    monitor = None      # the monitor.TensorMonitor `attach_monitor` hung behind the guard: two launches before the solver's
 
     def __init__(self, model, lr, weight_decay=1e-4, betas=(0.9, 0.999), eps=1e-8, clip_grad_l2norm=None,
                  grad_scale=1.0, clip_grad_value=None, max_consecutive_skips=None, lr_scale=None):
@@ -327,16 +328,34 @@ class GuardedClipAdamW(FusedClipAdamW):
                              "from that optimizer's step record)")
         self.ema = ema
 
+    def attach_monitor(self, monitor):
+        """monitor: a monitor.TensorMonitor built over this optimizer -- every `enqueue()` from now on issues its two
+        launches between the guard and the solver's launch, so the eager step, a GraphedTrainStep(optimizer=) captured
+        AFTERWARDS and an AccumulatedTrainStep record the statistics; a step captured before refuses its replay.  None:
+        detach."""
+        if monitor is not None and getattr(monitor, "optimizer", None) is not self:
+            raise ValueError("attach_monitor: the TensorMonitor was built over another optimizer (its step index is "
+                             "derived from that optimizer's step record)")
+        self.monitor = monitor
+
     def enqueue(self):
-        """the three launches (and the attached average's one); allocation-free and capturable"""
+        """the three launches (with the attached monitor's two between the guard and the solver's, and the attached
+        average's one behind); allocation-free and capturable"""
         self._solve()
         if self.ema is not None:
             self.ema.enqueue()
 
+    def _watch(self):
+        """the attached monitor's launches: behind the guard, so the record is this step's, and in front of the solver, so
+        the weights are those the gradient was taken at"""
+        if self.monitor is not None:
+            self.monitor.enqueue()
+
     def _solve(self):
-        """the guard and the solver's launch"""
+        """the guard, the monitor's launches and the solver's launch"""
         f = self.flat
         self._guard()
+        self._watch()
         if self.lr_segments is not None:    # learning-rate scales: AdamW over the scaled ranges
             ops.adamw_step_guarded_lr(f.data, f.grad, self.exp_avg, self.exp_avg_sq, f.n_decay, self.lr_segments,
                                       self.lr_scales, self.host_rec, self.dev_rec, self.betas[0], self.betas[1], self.eps)
@@ -394,10 +413,11 @@ class GuardedClipAdamW(FusedClipAdamW):
             return
         s = self.stats()
         if s["consecutive_skipped"] >= self.max_consecutive_skips:
+            culprits = self.monitor.culprit_line() if self.monitor is not None else ""
             raise RuntimeError("the last %d optimizer steps were dropped for non-finite gradients (limit %d; %d applied, "
-                               "%d dropped in all, last finite grad norm %g)"
+                               "%d dropped in all, last finite grad norm %g)%s"
                                % (s["consecutive_skipped"], self.max_consecutive_skips, s["applied"], s["skipped"],
-                                  s["grad_norm"]))
+                                  s["grad_norm"], "\n" + culprits if culprits else ""))
 
 
 # ---- SGD and Adam on the guarded tail (csrc/solver.hip) -------------------------------------------------------------
@@ -460,6 +480,7 @@ class _GuardedRangeSolver(GuardedClipAdamW):
         """the guard's two launches and the solver's one; allocation-free and capturable"""
         f = self.flat
         self._guard()
+        self._watch()
         segs, scales = self._ranges()
         self._launch(f.data, f.grad, [getattr(self, key) for key in self.STATE], f.n_decay, segs, scales, self.dev_rec)
 
@@ -516,8 +537,8 @@ class GuardedClipSGD(_GuardedRangeSolver):
 
 def construct_optimizer(model, cfg):
     """slowfast/models/optimizer.py:15-112.  `adamw`: the fused tail, guarded with SOLVER.CLIP_GRAD_VAL, the opt-in
-    SVIT.GUARDED_STEP or SVIT.EMA_DECAY (neither a key of the default tree, like SVIT.REPRODUCIBLE).  `sgd` and `adam`:
-    always the guarded tail (GuardedClipSGD / GuardedClipAdam)."""
+    SVIT.GUARDED_STEP, SVIT.EMA_DECAY or SVIT.MONITOR (none a key of the default tree, like SVIT.REPRODUCIBLE).  `sgd`
+    and `adam`: always the guarded tail (GuardedClipSGD / GuardedClipAdam)."""
     s = cfg.SOLVER
     if not s.ZERO_WD_1D_PARAM:
         raise NotImplementedError("svit_amd lays its flat buffers out for SOLVER.ZERO_WD_1D_PARAM: True")
@@ -531,9 +552,10 @@ def construct_optimizer(model, cfg):
         if s.OPTIMIZING_METHOD == "sgd":
             return GuardedClipSGD(model, momentum=s.MOMENTUM, dampening=s.DAMPENING, nesterov=s.NESTEROV, **common)
         return GuardedClipAdam(model, betas=(0.9, 0.999), eps=1e-8, **common)
-    # (SVIT.EMA_DECAY: the moving average's update count is derived from the guarded tail's step record, svit_amd/ema.py)
+    # (SVIT.EMA_DECAY: the moving average's update count is derived from the guarded tail's step record, svit_amd/ema.py;
+    #  SVIT.MONITOR: so is the step index of the per-tensor statistics, svit_amd/monitor.py)
     if (getattr(cfg.SVIT, "GUARDED_STEP", False) or cfg.SOLVER.CLIP_GRAD_VAL
-            or getattr(cfg.SVIT, "EMA_DECAY", None) is not None):
+            or getattr(cfg.SVIT, "EMA_DECAY", None) is not None or getattr(cfg.SVIT, "MONITOR", False)):
         return GuardedClipAdamW(model, lr=cfg.SOLVER.BASE_LR, weight_decay=cfg.SOLVER.WEIGHT_DECAY,
                                 clip_grad_l2norm=cfg.SOLVER.CLIP_GRAD_L2NORM, clip_grad_value=cfg.SOLVER.CLIP_GRAD_VAL,
                                 max_consecutive_skips=getattr(cfg.SVIT, "MAX_CONSECUTIVE_SKIPS", None),

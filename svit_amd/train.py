@@ -13,6 +13,7 @@ import torch.distributed as dist
 
 from . import losses, optim
 from .graph import AccumulatedTrainStep, GraphedEvalStep, GraphedTrainStep
+from .meters import log_json_stats
 
 
 def _min_length(n):
@@ -105,6 +106,7 @@ def _train_epoch_accumulated(train_loader, step, optimizer, train_meter, cur_epo
         step(batches)                                # (host half of update_stats included)
         train_meter.iter_toc()
         train_meter.log_iter_stats(cur_epoch, cur_iter)
+        _log_tensor_stats(optimizer, cfg, cur_iter)
         train_meter.iter_tic()
     stats = train_meter.log_epoch_stats(cur_epoch)
     train_meter.reset()
@@ -149,11 +151,25 @@ def _train_epoch_fed(train_loader, step, optimizer, train_meter, cur_epoch, cfg,
             feeder.pump()
             train_meter.iter_toc()
             train_meter.log_iter_stats(cur_epoch, cur_iter)
+            _log_tensor_stats(optimizer, cfg, cur_iter)
             train_meter.iter_tic()
     finally:
         producer.stop()
     stats = train_meter.log_epoch_stats(cur_epoch)
     train_meter.reset()
+    return stats
+
+
+def _log_tensor_stats(optimizer, cfg, cur_iter):
+    """once per cfg.LOG_PERIOD, with a monitor.TensorMonitor attached to the optimizer: ONE read of its ring and one JSON
+    line {"_type": "train_tensor_stats", ...} -- norms per layer of the period's last recorded step, the culprits of its
+    dropped steps.  Nothing without a monitor."""
+    mon = getattr(optimizer, "monitor", None)
+    if mon is None or (cur_iter + 1) % cfg.LOG_PERIOD != 0:
+        return None
+    stats = mon.log_stats(mon.read())
+    if stats is not None:
+        log_json_stats(stats)
     return stats
 
 
@@ -207,6 +223,7 @@ def train_epoch(train_loader, step_or_model, optimizer, train_meter, cur_epoch, 
             train_meter.update_stats(lr, inputs[0].size(0) * world, dloss=loss_dict)
         train_meter.iter_toc()
         train_meter.log_iter_stats(cur_epoch, cur_iter)
+        _log_tensor_stats(optimizer, cfg, cur_iter)
         train_meter.iter_tic()
     stats = train_meter.log_epoch_stats(cur_epoch)
     train_meter.reset()
