@@ -664,6 +664,77 @@ int svit_tensor_stats(const float* g, const float* p, int64_t n, const int64_t* 
                       int64_t Tn, const int64_t* segs, int64_t S, const svit_step_dev* dev_rec, void* ring, int64_t R,
                       int64_t every, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* Per-block FORWARD statistics, read from what a training forward keeps for its backward and never from the activations
+ * (svit_amd/actmon.py): the per-row LayerNorm statistics in front of each block's attention branch, in front of its MLP
+ * and in front of the final norm, and the attention's log-sum-exp (log2 domain) per (sample, head, query).
+ * svit_layernorm_fwd forms `mean` as a plain sum and `rstd` from the two-pass variance without a clamp, so a non-finite
+ * element of a row shows in that row's mean or rstd, and for a finite row mean^2 + 1 / rstd^2 - eps is its mean square.
+ * Two launches at the end of a saving forward write one row of a ring in device memory.
+ *
+ * A site: one array pair (LayerNorm: a = mean, b = rstd, f32 [rows]) or one array (lse: a = lse2, b = NULL), 4-byte
+ * aligned, 1 <= rows <= 2^24.  `first_window` is filled in by the library in its own copy; the caller's value is
+ * ignored.  The table and `slots` (int32 [n_sites]: the ring slot of each site) are HOST memory and travel in the kernel
+ * arguments, so an eager pass may name fresh arrays every time and a capture bakes its pool's addresses:
+ * 1 <= n_sites <= SVIT_ACT_MAX_SITES, 1 <= n_slots <= 1024, slots distinct and inside [0, n_slots).
+ *
+ * The ring: R rows of SVIT_ACT_HEADER_BYTES + 32 * n_slots bytes, 16-byte aligned; the HOST writes all of it when it is
+ * created or reset (pass = -1, step = -1, arg = n_bad = first_bad = -1, everything else 0).
+ *   row header, 48 bytes
+ *     offset  0  int64 pass        the counter's value when the row was written, from 0; -1: never written
+ *     offset  8  int64 step        dev_rec->applied + dev_rec->skipped: the index of the optimizer step this pass feeds
+ *                                  (what svit_tensor_stats rows carry); -1 without a dev_rec
+ *     offset 16  int32 B, Tx, T0, H0, W0   the pass's geometry, copied from `geom` (host, int32 [5]): batch, frames of the
+ *                                  clip, and the token grid in front of block 0 -- what unravels a row index
+ *     offset 36  int32 n_sites     sites of this pass
+ *     offset 40  int32 reserved[2] 0
+ *   entry of slot k at offset 48 + 32 * k, 32 bytes
+ *     offset  0  double sum        LayerNorm: sum over the good rows of (double) mean * mean + 1 / ((double) rstd * rstd),
+ *                                  each term within 2^-40 relative; lse: sum of (double) lse2 over the good rows
+ *     offset  8  float ext         LayerNorm: the smallest rstd (the widest token); lse: the largest value
+ *     offset 12  float ext2        LayerNorm: the largest |mean|; lse: 0
+ *     offset 16  int32 arg         the row of `ext`, the smallest such row among ties
+ *     offset 20  int32 n_bad       bad rows; -1: no site of this pass named the slot (the rest of the entry is then the
+ *                                  empty entry: zeros, arg = first_bad = -1)
+ *     offset 24  int32 first_bad   smallest bad row, -1 when there is none
+ *     offset 28  int32 rows        the site's rows
+ * A LayerNorm row is bad when mean or rstd has all exponent bits set or rstd is zero or negative (sign bit set); an lse
+ * row when its exponent bits are all set.  Bad rows enter neither the sum nor the extrema; with no good row
+ * ext = ext2 = 0 and arg = -1.  Extrema are taken on integer keys monotone in the float order (-0.0 below +0.0).
+ *
+ *   stage 1   one workgroup of 256 threads per window of svit_act_stats_window() = 4096 rows of ONE site (found by
+ *             bisection over first_window in the arguments, workgroup-uniform); loads first, then a fixed-order
+ *             reduction; ONE 32-byte partial at slot `window` of the workspace.  svit_act_stats_workspace(windows),
+ *             HOST ONLY, returns the bytes (SVIT_ERR_ARG, negative, for windows < 1 or above 96 * 4096).
+ *   stage 2   ONE workgroup: folds every site's partials in window order, writes the entries and the empty entries of
+ *             ring row (pass % R) and the header, then advances the pass counter state[0] (int64, device memory, zeroed
+ *             by the host) -- svit_meter_push's contract: one workgroup reads it at entry and writes it at exit; stage 1
+ *             never reads it.
+ * EXACTLY two launches; no float atomics, no ticket, no allocation, copy or synchronisation: capturable, and a row is
+ * bit-identical from run to run and from the eager pass to a replay.  Nothing but the ring row, the workspace and state
+ * is written.  Against svit_amd/actmon.py acts_host: |sum - host| <= 2^-27 * sum |term| (a site sums at most 2^24 terms
+ * on either side, each sum within 2^-29 of sum |term|, each term within 2^-40); everything else exactly.
+ *
+ * svit_act_sites_check, HOST ONLY, and svit_act_stats before any HIP call: SVIT_ERR_ARG for a NULL table / slots,
+ * n_sites or n_slots out of range, a NULL `a`, rows outside 1..2^24, a slot outside [0, n_slots) or named twice;
+ * SVIT_ERR_ALIGN for an `a` or `b` not 4-byte aligned; *total_windows (may be NULL) receives the windows of the table.
+ * svit_act_stats besides: SVIT_ERR_ARG for a NULL geom, ring, state or workspace, R < 1, workspace_bytes below
+ * svit_act_stats_workspace(windows); SVIT_ERR_ALIGN for a ring or workspace not 16-byte aligned, state or dev_rec not
+ * 8-byte aligned.  dev_rec may be NULL.  The ring's size is the caller's to get right. */
+#define SVIT_ACT_MAX_SITES 96
+#define SVIT_ACT_HEADER_BYTES 48
+typedef struct {
+  const float* a;
+  const float* b;
+  int32_t rows, first_window;
+} svit_act_site;
+int svit_act_stats_window(void);
+int64_t svit_act_stats_workspace(int64_t total_windows);
+int svit_act_sites_check(const svit_act_site* sites, const int32_t* slots, int64_t n_sites, int64_t n_slots,
+                         int64_t* total_windows);
+int svit_act_stats(const svit_act_site* sites, const int32_t* slots, int64_t n_sites, int64_t n_slots,
+                   const int32_t* geom, const svit_step_dev* dev_rec, void* ring, int64_t R, int64_t* state,
+                   void* workspace, int64_t workspace_bytes, void* stream);
+
 /* HOST ONLY (no stream, no launch): the bias corrections svit_adamw_step derives from its `step` argument, by the very
  * same host code: pair k-1 = (1 - powf(beta1, k), sqrtf(1 - powf(beta2, k))) for steps k = 1, 2, ... up to and including
  * the first step at which both values are exactly 1.0f; past the table both are 1.0f.  *n_entries receives that length

@@ -246,6 +246,9 @@ class Engine:
         self.reproducible = False
         self._capture_fork = None   # set by svit_amd/graph.py while it captures: (fn) -> None
         self._capture_join = None
+        # the actmon.ActivationMonitor `model.attach_activation_monitor` hung behind every saving forward: two launches
+        # over the LayerNorm statistics and log-sum-exps the pass keeps for its backward anyway (None: not one launch more)
+        self.act_monitor = None
 
     # ------------------------------------------------------------------ helpers ----------
     def refresh_weights(self):
@@ -385,7 +388,9 @@ class Engine:
             hip.mark("fwd%d" % blk.index)
         y16, y32, mean, rstd = ops.layernorm_fwd(x, f.p("norm.weight"), f.p("norm.bias"),
                                                  want_f32=True, want_bf16=False, save_stats=save)
-        st.update(x_last=x if save else None, mean=mean, rstd=rstd, thw=thw)
+        st.update(x_last=x if save else None, mean=mean, rstd=rstd, thw=thw, thw0=(T, Ho, Wo))
+        if save and self.act_monitor is not None:
+            self.act_monitor.enqueue(st)
         # the batched interpolation results belong to THIS pass: a stand-alone _block_fwd afterwards (tests, tools) interpolates
         # its own tables.  The fp32 / bf16 buffers are cached per (geometry, save) and the saved `tabs` of a pass are views of
         # them: at most ONE saved forward per geometry may be awaiting its backward (the step's passes all differ in geometry

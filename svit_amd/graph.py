@@ -122,6 +122,8 @@ class GraphedTrainStep:
         self._ema = optimizer.ema if optimizer is not None else None
         # ... and the monitor.TensorMonitor attached NOW: its two launches sit between the guard and the solver's
         self._monitor = optimizer.monitor if optimizer is not None else None
+        # ... and the actmon.ActivationMonitor attached to the MODEL now: its two launches end the captured forward
+        self._act_monitor = self.core.engine.act_monitor
         self.loss_fun = loss_fun
         self.dp = model if hasattr(model, "_on_ready") and (getattr(model, "world_size", 1) > 1 or
                                                            getattr(model, "force_collectives", False)) else None
@@ -320,6 +322,7 @@ class GraphedTrainStep:
         if [p.requires_grad for p in self._flag_params] != self._flags:
             raise hip.SvitHipError("a parameter's requires_grad changed after this GraphedTrainStep was captured (it "
                                    "froze everything below position %d): rebuild the optimizer and the step" % self.cut)
+        _check_act_monitor(self.core, self._act_monitor, "GraphedTrainStep")
         if self.optimizer is not None:
             _check_ema(self.optimizer, self._ema, "GraphedTrainStep")
             _check_monitor(self.optimizer, self._monitor, "GraphedTrainStep")
@@ -465,6 +468,7 @@ class AccumulatedTrainStep:
         self.optimizer = optimizer
         self._ema = optimizer.ema           # (the tail is eager, but a step is built for one recipe: as the freeze flags)
         self._monitor = optimizer.monitor
+        self._act_monitor = core.engine.act_monitor
         self.meter = meter
         if meter is not None:
             if getattr(meter, "virtual_ranks", None) != k:
@@ -482,6 +486,7 @@ class AccumulatedTrainStep:
             raise RuntimeError("AccumulatedTrainStep runs the training step: call model.train() first")
         if len(batches) != self.k:
             raise hip.SvitHipError("AccumulatedTrainStep holds %d micro-steps, got %d batches" % (self.k, len(batches)))
+        _check_act_monitor(self.core, self._act_monitor, "AccumulatedTrainStep")
         self.micro_steps[0].check_flags()       # (every micro-step holds the optimizer's cut)
         _check_ema(self.optimizer, self._ema, "AccumulatedTrainStep")
         _check_monitor(self.optimizer, self._monitor, "AccumulatedTrainStep")
@@ -742,6 +747,16 @@ def _check_monitor(optimizer, monitor, what):
                                "its tail holds the launches of then -- rebuild the step"
                                % (what, "one" if monitor is not None else "none",
                                   "one" if optimizer.monitor is not None else "none"))
+
+
+def _check_act_monitor(core, monitor, what):
+    """refuse a replay after another actmon.ActivationMonitor (or none) was attached to the model than the step was built
+    with"""
+    if core.engine.act_monitor is not monitor:
+        raise hip.SvitHipError("the model's attached ActivationMonitor changed after this %s was built (%s then, %s now): "
+                               "its forward holds the launches of then -- rebuild the step"
+                               % (what, "one" if monitor is not None else "none",
+                                  "one" if core.engine.act_monitor is not None else "none"))
 
 
 def _is_feeder(batch):

@@ -130,6 +130,11 @@ class FeedArgs(C.Structure):
                 ("seg", FeedSeg * 8)]
 
 
+class ActSite(C.Structure):
+    """svit_act_site: one array pair (LayerNorm mean / rstd) or one array (lse, b NULL) the activation monitor reads"""
+    _fields_ = [("a", vp), ("b", vp), ("rows", i32), ("first_window", i32)]
+
+
 class StepHost(C.Structure):
     """svit_step_host: the part of the guarded optimiser's step record the host uploads before every step"""
     _fields_ = [("lr", f32 * 2), ("weight_decay", f32 * 2), ("max_norm", f32), ("clip_value", f32),
@@ -218,6 +223,10 @@ _SIGS = {
     "svit_tensor_table_check": (i32, [vp, i64, i64]),
     "svit_tensor_stats_workspace": (i64, [i64, i64]),
     "svit_tensor_stats": (i32, [vp, vp, i64, vp, vp, i64, vp, i64, vp, vp, i64, i64, vp, i64, vp]),
+    "svit_act_stats_window": (i32, []),                                        # host only, like the next two
+    "svit_act_stats_workspace": (i64, [i64]),
+    "svit_act_sites_check": (i32, [C.POINTER(ActSite), vp, i64, i64, C.POINTER(i64)]),
+    "svit_act_stats": (i32, [C.POINTER(ActSite), vp, i64, i64, vp, vp, vp, i64, vp, vp, i64, vp]),
     "svit_head_fwd": (i32, [C.POINTER(HeadArgs), vp]),
     "svit_head_bwd": (i32, [C.POINTER(HeadBwdArgs), vp]),
     "svit_head_eval": (i32, [C.POINTER(HeadArgs), i32, vp]),

@@ -292,6 +292,23 @@ class SViT(nn.Module):
         self._anchor = torch.zeros((), device=dev, requires_grad=True)
         return self
 
+    def attach_activation_monitor(self, monitor):
+        """monitor: an actmon.ActivationMonitor built over this model -- every saving `engine.forward` from now on ends
+        with its two launches, so the eager training forward, a GraphedTrainStep captured AFTERWARDS and every micro-step
+        of an accumulated step record the forward statistics; a step captured before refuses its replay.  The monitor's
+        optimizer (if it has one) names the origin of non-finite activations in its check().  None: detach."""
+        if self.engine is None:
+            raise hip.SvitHipError("attach_activation_monitor needs a finalized (on-GPU) SViT")
+        if monitor is not None and getattr(monitor, "model", None) is not self:
+            raise ValueError("attach_activation_monitor: the ActivationMonitor was built over another model (its slots "
+                             "and geometry are this model's plan)")
+        old = self.engine.act_monitor
+        if old is not None and old.optimizer is not None and old.optimizer.act_monitor is old:
+            old.optimizer.act_monitor = None
+        self.engine.act_monitor = monitor
+        if monitor is not None and monitor.optimizer is not None:
+            monitor.optimizer.act_monitor = monitor
+
     # -- frozen parameters (svit_amd/freeze.py) -----------------------------------------------------
     def freeze_below(self, cut):
         """Freeze every parameter at a network position below `cut` and unfreeze the rest: position 0 is the stem

@@ -1090,6 +1090,69 @@ def tensor_stats(g, p, table_dev, table_host, segs, dev_rec, ring, R, every, wor
              every, ptr(workspace), workspace.numel())
 
 
+def act_stats_window():
+    """rows per window of svit_act_stats' first stage (host only)"""
+    return int(hip.load().svit_act_stats_window())
+
+
+def act_stats_workspace(total_windows):
+    """bytes of svit_act_stats' workspace for a site table of that many windows (host only)"""
+    b = int(hip.load().svit_act_stats_workspace(total_windows))
+    if b < 0:
+        hip.check(b, "svit_act_stats_workspace (%d windows)" % total_windows)
+    return b
+
+
+def act_site_table(sites, slots):
+    """[(a, b or None, rows)] with a / b device addresses (ints) + the ring slot of each -> (svit_act_site array, int32
+    slots as numpy): what the two calls below take.  Nothing is checked here."""
+    import numpy as np
+    tab = (hip.ActSite * max(1, len(sites)))()
+    for i, (a, b, rows) in enumerate(sites):
+        tab[i].a, tab[i].b, tab[i].rows, tab[i].first_window = a, b, rows, 0
+    return tab, np.ascontiguousarray(np.asarray(slots, dtype=np.int32))
+
+
+def act_sites_check(sites, slots, n_slots):
+    """svit_act_sites_check: raises for a site table the statistics kernels would refuse (host only, needs no device)
+    -> the table's windows"""
+    import ctypes
+    tab, sl = act_site_table(sites, slots)
+    if len(sl) != len(sites):
+        raise hip.SvitHipError("act_sites_check: one slot per site")
+    windows = ctypes.c_int64(0)
+    hip.check(hip.load().svit_act_sites_check(tab, sl.ctypes.data, len(sites), n_slots, ctypes.byref(windows)),
+              "svit_act_sites_check (%d sites, %d slots)" % (len(sites), n_slots))
+    return int(windows.value)
+
+
+def act_stats(sites, slots, n_slots, geom, dev_rec, ring, R, state, workspace):
+    """the forward statistics of one pass into row (pass % R) of `ring` (svit_act_stats; two launches).  sites:
+    [(a, b or None, rows)] of device addresses, slots: their ring slots; geom: (B, Tx, T0, H0, W0); dev_rec: the guarded
+    optimizer's int32 [12] record or None; ring: uint8 [R * (48 + 32 * n_slots)], state: int64 [1], workspace: uint8"""
+    import numpy as np
+    _chk_dev(ring, state, workspace)
+    dev = ring.device
+    if len(slots) != len(sites):
+        raise hip.SvitHipError("act_stats: one slot per site")
+    if dev_rec is not None:
+        _chk_dev(dev_rec)
+        if dev_rec.dtype != torch.int32 or dev_rec.numel() != 12 or dev_rec.device != dev:
+            raise hip.SvitHipError("act_stats: the step record is int32 [12] on %s" % (dev,))
+    if state.dtype != torch.int64 or state.numel() != 1 or state.device != dev:
+        raise hip.SvitHipError("act_stats: the pass counter is int64 [1] on %s" % (dev,))
+    if (ring.dtype != torch.uint8 or workspace.dtype != torch.uint8 or workspace.device != dev or R < 1
+            or n_slots < 1 or ring.numel() != R * (48 + 32 * n_slots)):
+        raise hip.SvitHipError("act_stats: the ring is uint8 [R * (48 + 32 * %d)] and the workspace uint8, on %s"
+                               % (n_slots, dev))
+    g = np.ascontiguousarray(np.asarray(geom, dtype=np.int32))
+    if g.shape != (5,):
+        raise hip.SvitHipError("act_stats: geom is (B, Tx, T0, H0, W0)")
+    tab, sl = act_site_table(sites, slots)
+    hip.call("svit_act_stats", tab, sl.ctypes.data, len(sites), n_slots, g.ctypes.data, ptr(dev_rec), ptr(ring), R,
+             ptr(state), ptr(workspace), workspace.numel())
+
+
 # ---------------------------------------------------------------- head (K15) ----------------
 def _head_args(tokens, T, O, keep, head_params, outs):
     a = hip.HeadArgs()

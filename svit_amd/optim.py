@@ -250,6 +250,7 @@ class GuardedClipAdamW(FusedClipAdamW):
     ema = None          # the ema.WeightEMA `attach_ema` hung behind the step: every enqueue() ends with its launch
     _averaged = None    # the ema.WeightEMA whose average stands in the weights' place (ema.average_weights()): no step
     monitor = None      # the monitor.TensorMonitor `attach_monitor` hung behind the guard: two launches before the solver's
+    act_monitor = None  # the actmon.ActivationMonitor bound by model.attach_activation_monitor: check() asks it for the origin
 
     def __init__(self, model, lr, weight_decay=1e-4, betas=(0.9, 0.999), eps=1e-8, clip_grad_l2norm=None,
                  grad_scale=1.0, clip_grad_value=None, max_consecutive_skips=None, lr_scale=None):
@@ -414,6 +415,10 @@ class GuardedClipAdamW(FusedClipAdamW):
         s = self.stats()
         if s["consecutive_skipped"] >= self.max_consecutive_skips:
             culprits = self.monitor.culprit_line() if self.monitor is not None else ""
+            # (the step that was dropped last is the last step: its forward passes carry that index)
+            origin = (self.act_monitor.origin_line(s["applied"] + s["skipped"] - 1)
+                      if self.act_monitor is not None and s["consecutive_skipped"] > 0 else "")
+            culprits = "\n".join(x for x in (culprits, origin) if x)
             raise RuntimeError("the last %d optimizer steps were dropped for non-finite gradients (limit %d; %d applied, "
                                "%d dropped in all, last finite grad norm %g)%s"
                                % (s["consecutive_skipped"], self.max_consecutive_skips, s["applied"], s["skipped"],

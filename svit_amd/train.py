@@ -107,6 +107,7 @@ def _train_epoch_accumulated(train_loader, step, optimizer, train_meter, cur_epo
         train_meter.iter_toc()
         train_meter.log_iter_stats(cur_epoch, cur_iter)
         _log_tensor_stats(optimizer, cfg, cur_iter)
+        _log_activation_stats(step, cfg, cur_iter)
         train_meter.iter_tic()
     stats = train_meter.log_epoch_stats(cur_epoch)
     train_meter.reset()
@@ -152,6 +153,7 @@ def _train_epoch_fed(train_loader, step, optimizer, train_meter, cur_epoch, cfg,
             train_meter.iter_toc()
             train_meter.log_iter_stats(cur_epoch, cur_iter)
             _log_tensor_stats(optimizer, cfg, cur_iter)
+            _log_activation_stats(step, cfg, cur_iter)
             train_meter.iter_tic()
     finally:
         producer.stop()
@@ -165,6 +167,21 @@ def _log_tensor_stats(optimizer, cfg, cur_iter):
     line {"_type": "train_tensor_stats", ...} -- norms per layer of the period's last recorded step, the culprits of its
     dropped steps.  Nothing without a monitor."""
     mon = getattr(optimizer, "monitor", None)
+    if mon is None or (cur_iter + 1) % cfg.LOG_PERIOD != 0:
+        return None
+    stats = mon.log_stats(mon.read())
+    if stats is not None:
+        log_json_stats(stats)
+    return stats
+
+
+def _log_activation_stats(step_or_model, cfg, cur_iter):
+    """once per cfg.LOG_PERIOD, with an actmon.ActivationMonitor attached to the model (the step's, or the model itself):
+    ONE read of its ring and one JSON line {"_type": "train_activation_stats", ...} -- the residual-stream RMS, the widest
+    token's std and the largest attention log-sum-exp per block of the period's last pass, the origin of every pass with
+    non-finite activations.  Nothing without a monitor."""
+    core = getattr(step_or_model, "core", None) or getattr(step_or_model, "module", step_or_model)
+    mon = getattr(getattr(core, "engine", None), "act_monitor", None)
     if mon is None or (cur_iter + 1) % cfg.LOG_PERIOD != 0:
         return None
     stats = mon.log_stats(mon.read())
@@ -224,6 +241,7 @@ def train_epoch(train_loader, step_or_model, optimizer, train_meter, cur_epoch, 
         train_meter.iter_toc()
         train_meter.log_iter_stats(cur_epoch, cur_iter)
         _log_tensor_stats(optimizer, cfg, cur_iter)
+        _log_activation_stats(step_or_model, cfg, cur_iter)
         train_meter.iter_tic()
     stats = train_meter.log_epoch_stats(cur_epoch)
     train_meter.reset()
