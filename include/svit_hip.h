@@ -664,6 +664,71 @@ int svit_tensor_stats(const float* g, const float* p, int64_t n, const int64_t* 
                       int64_t Tn, const int64_t* segs, int64_t S, const svit_step_dev* dev_rec, void* ring, int64_t R,
                       int64_t every, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* What the solver did to every tensor, measured INSIDE the step (svit_amd/updmon.py): one launch in front of the solver's
+ * launch copies the weights into a shadow buffer, two launches behind it compare the weights with the shadow.  No update
+ * rule is restated: the numbers are those of whatever solver ran in between.  All three launches read the guard's record,
+ * which no solver kernel writes, and so agree on whether the step is due:
+ *   step index   s = dev_rec->applied + dev_rec->skipped - 1, svit_tensor_stats' index: rows of both rings join by step.
+ *   due          when dev_rec->apply == 1 and s % every == 0 (a dropped step moves nothing and is never recorded).
+ *                Otherwise every workgroup of the three launches returns before its first load; shadow, workspace and
+ *                ring keep their bytes.
+ *
+ * svit_update_snapshot: p, shadow f32 [n], 16-byte aligned.  ONE launch.  On a due step shadow = p over the trainable
+ * segments, 16 bytes at a time; segs / S: svit_adamw_step_guarded_seg's table IN HOST MEMORY with its rules and error
+ * codes, carried in the kernel arguments and walked with a workgroup-uniform cursor that only moves forward; S == 0, segs
+ * then ignored: the whole buffer (its last n % 4 elements one by one).  Nothing outside the segments is read or written.
+ * SVIT_ERR_ARG besides the table's: a NULL p, shadow or dev_rec, n <= 0, every < 1.  SVIT_ERR_ALIGN: p or shadow not
+ * 16-byte aligned, dev_rec not 8-byte aligned.
+ *
+ * svit_update_stats: p (the weights behind the solver), shadow (the weights in front of it), g f32 [n]; m, v f32 [n] or
+ * NULL (SGD: its momentum buffer or NULL for m, NULL for v), all 16-byte aligned.  table_dev / table_host / Tn: the
+ * tensor table of svit_tensor_stats, checked by svit_tensor_table_check; segs / S as above, segments hold whole tensors.
+ * A tensor whose begin lies in no segment is frozen: neither loaded nor written, its entry keeps what the host wrote.
+ * EXACTLY two launches, no atomics, no ticket, no allocation, copy or synchronisation: capturable, and a row is
+ * bit-identical from run to run and from the eager step to a replay.
+ *   stage 1      one workgroup per window of svit_tensor_stats_window() = 4096 floats, loads issued first, then the
+ *                bisection and the forward-only walk of svit_tensor_stats; ONE 64-byte partial per (window, tensor) piece
+ *                at slot window + tensor.  svit_update_stats_workspace(n, Tn), HOST ONLY, returns the bytes of the
+ *                ceil(n / 4096) + Tn slots (SVIT_ERR_ARG, negative, for n or Tn out of range).
+ *   stage 2      one wave per tensor: lane l adds the partials of the tensor's windows l, l + 64, ... in ascending
+ *                order, the 64 lanes combine in a fixed butterfly, lane 0 writes the entry; the wave of tensor 0 also
+ *                writes the header.
+ * The ring: R rows of 16 + 64 * Tn bytes, 16-byte aligned; the HOST writes all of it when it is created and when it is
+ * reset (step = -1, n_still = -1, everything else 0), the kernels write the rows of due steps, row s % R.
+ *   row header, 16 bytes
+ *     offset  0  int64 step        the step the row holds; -1: never written
+ *     offset  8  int32 flags       bit 0: m was present, bit 1: v was present
+ *     offset 12  int32 reserved    0
+ *   entry of tensor t at offset 16 + 64 * t, 64 bytes, with Delta = (double) p_new - (double) p_old per element
+ *     offset  0  double sumsq_d    sum of Delta^2
+ *     offset  8  double sumsq_p    sum of p_new^2
+ *     offset 16  double dot_dg     sum of Delta * g, signed
+ *     offset 24  double sumsq_g    sum of g^2
+ *     offset 32  double sumsq_m    sum of m^2; 0 without m
+ *     offset 40  double sum_v      sum of v; 0 without v
+ *     offset 48  float absmax_d    largest (float) |Delta|, the maximum taken on the integer image
+ *     offset 52  int32 n_still     elements whose 32 bits did not change; -1: the tensor is frozen and the entry has
+ *                                  never been written
+ *     offset 56  int32 n_one_ulp   elements that moved to an adjacent float: |key(new) - key(old)| == 1 in int64, with
+ *                                  key(i) = i ^ ((i >> 31) & 0x7fffffff) on the signed 32-bit image (+0.0 -> -0.0 is one)
+ *     offset 60  int32 reserved    0
+ * The counts compare integer images, never floats.  A due step was applied, so g is finite inside the segments.
+ * Non-finite p, m or v are NOT filtered: the sums, the maximum and n_one_ulp of such a tensor are unspecified; no address
+ * outside the buffers is touched for any input.  Against svit_amd/updmon.py update_host: Delta is one IEEE subtraction on
+ * both sides; a product may be fused into the following addition here (2^-53 relative per term); either side sums at
+ * most 2^22 terms per tensor: each of the six sums agrees within 2^-29 * sum |term|, everything else exactly.
+ * SVIT_ERR_ARG besides the tables': a NULL p, shadow, g, table_dev, dev_rec, ring or workspace; R < 1; every < 1;
+ * workspace_bytes below svit_update_stats_workspace(n, Tn).  SVIT_ERR_ALIGN: p, shadow, g, m, v, ring or workspace not
+ * 16-byte aligned, table_dev or dev_rec not 8-byte aligned.  All checked before any HIP call.  The ring's size is the
+ * caller's to get right. */
+int svit_update_snapshot(const float* p, float* shadow, int64_t n, const int64_t* segs, int64_t S,
+                         const svit_step_dev* dev_rec, int64_t every, void* stream);
+int64_t svit_update_stats_workspace(int64_t n, int64_t Tn);
+int svit_update_stats(const float* p, const float* shadow, const float* g, const float* m, const float* v, int64_t n,
+                      const int64_t* table_dev, const int64_t* table_host, int64_t Tn, const int64_t* segs, int64_t S,
+                      const svit_step_dev* dev_rec, void* ring, int64_t R, int64_t every, void* workspace,
+                      int64_t workspace_bytes, void* stream);
+
 /* Per-block FORWARD statistics, read from what a training forward keeps for its backward and never from the activations
  * (svit_amd/actmon.py): the per-row LayerNorm statistics in front of each block's attention branch, in front of its MLP
  * and in front of the final norm, and the attention's log-sum-exp (log2 domain) per (sample, head, query).

@@ -122,6 +122,8 @@ class GraphedTrainStep:
         self._ema = optimizer.ema if optimizer is not None else None
         # ... and the monitor.TensorMonitor attached NOW: its two launches sit between the guard and the solver's
         self._monitor = optimizer.monitor if optimizer is not None else None
+        # ... and the updmon.UpdateMonitor attached NOW: one launch in front of the solver's, two behind it
+        self._update_monitor = getattr(optimizer, "update_monitor", None)
         # ... and the actmon.ActivationMonitor attached to the MODEL now: its two launches end the captured forward
         self._act_monitor = self.core.engine.act_monitor
         self.loss_fun = loss_fun
@@ -326,6 +328,7 @@ class GraphedTrainStep:
         if self.optimizer is not None:
             _check_ema(self.optimizer, self._ema, "GraphedTrainStep")
             _check_monitor(self.optimizer, self._monitor, "GraphedTrainStep")
+            _check_update_monitor(self.optimizer, self._update_monitor, "GraphedTrainStep")
 
     def check_batch(self, inputs):
         """refuse a batch the capture does not fit (before anything is enqueued)"""
@@ -468,6 +471,7 @@ class AccumulatedTrainStep:
         self.optimizer = optimizer
         self._ema = optimizer.ema           # (the tail is eager, but a step is built for one recipe: as the freeze flags)
         self._monitor = optimizer.monitor
+        self._update_monitor = getattr(optimizer, "update_monitor", None)
         self._act_monitor = core.engine.act_monitor
         self.meter = meter
         if meter is not None:
@@ -490,6 +494,7 @@ class AccumulatedTrainStep:
         self.micro_steps[0].check_flags()       # (every micro-step holds the optimizer's cut)
         _check_ema(self.optimizer, self._ema, "AccumulatedTrainStep")
         _check_monitor(self.optimizer, self._monitor, "AccumulatedTrainStep")
+        _check_update_monitor(self.optimizer, self._update_monitor, "AccumulatedTrainStep")
         for i, (ms, b) in enumerate(zip(self.micro_steps, batches)):
             if _is_feeder(b):
                 if b.target is not ms.x:
@@ -747,6 +752,16 @@ def _check_monitor(optimizer, monitor, what):
                                "its tail holds the launches of then -- rebuild the step"
                                % (what, "one" if monitor is not None else "none",
                                   "one" if optimizer.monitor is not None else "none"))
+
+
+def _check_update_monitor(optimizer, monitor, what):
+    """refuse a replay after another updmon.UpdateMonitor (or none) was attached to the optimizer than the step was built
+    with"""
+    if getattr(optimizer, "update_monitor", None) is not monitor:
+        raise hip.SvitHipError("the optimizer's attached UpdateMonitor changed after this %s was built (%s then, %s now): "
+                               "its tail holds the launches of then -- rebuild the step"
+                               % (what, "one" if monitor is not None else "none",
+                                  "one" if getattr(optimizer, "update_monitor", None) is not None else "none"))
 
 
 def _check_act_monitor(core, monitor, what):

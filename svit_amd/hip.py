@@ -223,6 +223,9 @@ _SIGS = {
     "svit_tensor_table_check": (i32, [vp, i64, i64]),
     "svit_tensor_stats_workspace": (i64, [i64, i64]),
     "svit_tensor_stats": (i32, [vp, vp, i64, vp, vp, i64, vp, i64, vp, vp, i64, i64, vp, i64, vp]),
+    "svit_update_snapshot": (i32, [vp, vp, i64, vp, i64, vp, i64, vp]),
+    "svit_update_stats_workspace": (i64, [i64, i64]),                          # host only
+    "svit_update_stats": (i32, [vp, vp, vp, vp, vp, i64, vp, vp, i64, vp, i64, vp, vp, i64, i64, vp, i64, vp]),
     "svit_act_stats_window": (i32, []),                                        # host only, like the next two
     "svit_act_stats_workspace": (i64, [i64]),
     "svit_act_sites_check": (i32, [C.POINTER(ActSite), vp, i64, i64, C.POINTER(i64)]),

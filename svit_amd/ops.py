@@ -1090,6 +1090,52 @@ def tensor_stats(g, p, table_dev, table_host, segs, dev_rec, ring, R, every, wor
              every, ptr(workspace), workspace.numel())
 
 
+def _chk_step_dev(what, dev_rec, dev):
+    if dev_rec.dtype != torch.int32 or dev_rec.numel() != 12 or dev_rec.device != dev:
+        raise hip.SvitHipError("%s: the step record is int32 [12] on %s" % (what, dev))
+
+
+def update_snapshot(p, shadow, segs, dev_rec, every):
+    """shadow = p over the trainable segments (numpy or None: the whole buffer) when the step record says the step is due:
+    applied, and its index a multiple of `every` (svit_update_snapshot; one launch)"""
+    _chk_dev(p, shadow, dev_rec)
+    dev = p.device
+    if shadow.numel() != p.numel() or p.dtype != F32 or shadow.dtype != F32 or shadow.device != dev:
+        raise hip.SvitHipError("update_snapshot: p and shadow are fp32 buffers of one size on one device")
+    _chk_step_dev("update_snapshot", dev_rec, dev)
+    sp, S = (None, 0) if segs is None else _chk_segs(segs)
+    hip.call("svit_update_snapshot", ptr(p), ptr(shadow), p.numel(), sp, S, ptr(dev_rec), every)
+
+
+def update_stats_workspace(n, Tn):
+    """bytes of svit_update_stats' workspace for a buffer of n floats behind Tn tensors (host only)"""
+    b = int(hip.load().svit_update_stats_workspace(n, Tn))
+    if b < 0:
+        hip.check(b, "svit_update_stats_workspace (n = %d, %d tensors)" % (n, Tn))
+    return b
+
+
+def update_stats(p, shadow, g, m, v, table_dev, table_host, segs, dev_rec, ring, R, every, workspace):
+    """per-tensor statistics of the step p - shadow (and of p, g, m, v) into row (step % R) of `ring` when the step record
+    says the step is due (svit_update_stats; two launches).  m, v: the moments or None; the tables as tensor_stats takes
+    them; ring: uint8 [R * (16 + 64 * Tn)] and workspace: uint8, both on the device"""
+    _chk_dev(p, shadow, g, m, v, table_dev, dev_rec, ring, workspace)
+    dev = p.device
+    tp, Tn = _chk_tensor_table(table_host)
+    if any(t is not None and (t.numel() != p.numel() or t.dtype != F32 or t.device != dev) for t in (p, shadow, g, m, v)):
+        raise hip.SvitHipError("update_stats: p, shadow, g, m and v are fp32 buffers of one size on one device")
+    if table_dev.dtype != torch.int64 or tuple(table_dev.shape) != (Tn, 2) or table_dev.device != dev:
+        raise hip.SvitHipError("update_stats: the device table is int64 [%d, 2] on %s, as the host's" % (Tn, dev))
+    _chk_step_dev("update_stats", dev_rec, dev)
+    if (ring.dtype != torch.uint8 or workspace.dtype != torch.uint8 or ring.device != dev or workspace.device != dev
+            or R < 1 or ring.numel() != R * (16 + 64 * Tn)):
+        raise hip.SvitHipError("update_stats: the ring is uint8 [R * (16 + 64 * %d)] and the workspace uint8, on %s"
+                               % (Tn, dev))
+    sp, S = (None, 0) if segs is None else _chk_segs(segs)
+    hip.call("svit_update_stats", ptr(p), ptr(shadow), ptr(g), ptr(m), ptr(v), p.numel(), ptr(table_dev), tp, Tn, sp, S,
+             ptr(dev_rec), ptr(ring), R, every, ptr(workspace), workspace.numel())
+
+
 def act_stats_window():
     """rows per window of svit_act_stats' first stage (host only)"""
     return int(hip.load().svit_act_stats_window())

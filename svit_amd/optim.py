@@ -251,6 +251,8 @@ class GuardedClipAdamW(FusedClipAdamW):
     _averaged = None    # the ema.WeightEMA whose average stands in the weights' place (ema.average_weights()): no step
     monitor = None      # the monitor.TensorMonitor `attach_monitor` hung behind the guard: two launches before the solver's
     act_monitor = None  # the actmon.ActivationMonitor bound by model.attach_activation_monitor: check() asks it for the origin
+    update_monitor = None   # the updmon.UpdateMonitor `attach_update_monitor` hung around the solver's launch: one launch in
+    #                         front of it, two behind
 
     def __init__(self, model, lr, weight_decay=1e-4, betas=(0.9, 0.999), eps=1e-8, clip_grad_l2norm=None,
                  grad_scale=1.0, clip_grad_value=None, max_consecutive_skips=None, lr_scale=None):
@@ -339,9 +341,20 @@ class GuardedClipAdamW(FusedClipAdamW):
                              "derived from that optimizer's step record)")
         self.monitor = monitor
 
+    def attach_update_monitor(self, monitor):
+        """monitor: an updmon.UpdateMonitor built over this optimizer -- every `enqueue()` from now on issues its snapshot
+        in front of the solver's launch and its two statistics launches directly behind it (in front of the average's), so
+        the eager step, a GraphedTrainStep(optimizer=) captured AFTERWARDS and an AccumulatedTrainStep record what the
+        solver did; a step captured before refuses its replay.  None: detach."""
+        if monitor is not None and getattr(monitor, "optimizer", None) is not self:
+            raise ValueError("attach_update_monitor: the UpdateMonitor was built over another optimizer (its step index is "
+                             "derived from that optimizer's step record)")
+        self.update_monitor = monitor
+
     def enqueue(self):
-        """the three launches (with the attached monitor's two between the guard and the solver's, and the attached
-        average's one behind); allocation-free and capturable"""
+        """the three launches (with the attached monitor's two between the guard and the solver's, the attached update
+        monitor's one in front of the solver's and two behind it, and the attached average's one last); allocation-free
+        and capturable"""
         self._solve()
         if self.ema is not None:
             self.ema.enqueue()
@@ -352,11 +365,22 @@ class GuardedClipAdamW(FusedClipAdamW):
         if self.monitor is not None:
             self.monitor.enqueue()
 
+    def _snap(self):
+        """the attached update monitor's snapshot: the weights in front of the solver's launch"""
+        if self.update_monitor is not None:
+            self.update_monitor.snapshot()
+
+    def _measure(self):
+        """the attached update monitor's two launches: directly behind the solver's launch"""
+        if self.update_monitor is not None:
+            self.update_monitor.enqueue()
+
     def _solve(self):
-        """the guard, the monitor's launches and the solver's launch"""
+        """the guard, the monitors' launches and the solver's launch"""
         f = self.flat
         self._guard()
         self._watch()
+        self._snap()
         if self.lr_segments is not None:    # learning-rate scales: AdamW over the scaled ranges
             ops.adamw_step_guarded_lr(f.data, f.grad, self.exp_avg, self.exp_avg_sq, f.n_decay, self.lr_segments,
                                       self.lr_scales, self.host_rec, self.dev_rec, self.betas[0], self.betas[1], self.eps)
@@ -366,6 +390,7 @@ class GuardedClipAdamW(FusedClipAdamW):
         else:
             ops.adamw_step_guarded(f.data, f.grad, self.exp_avg, self.exp_avg_sq, f.n_decay, self.host_rec,
                                    self.dev_rec, self.betas[0], self.betas[1], self.eps)
+        self._measure()
 
     def _guard(self):
         """the sum of squares and the step's decision, over the trainable segments when part of the buffer is frozen"""
@@ -486,8 +511,10 @@ class _GuardedRangeSolver(GuardedClipAdamW):
         f = self.flat
         self._guard()
         self._watch()
+        self._snap()
         segs, scales = self._ranges()
         self._launch(f.data, f.grad, [getattr(self, key) for key in self.STATE], f.n_decay, segs, scales, self.dev_rec)
+        self._measure()
 
 
 class GuardedClipAdam(_GuardedRangeSolver):
@@ -542,7 +569,8 @@ class GuardedClipSGD(_GuardedRangeSolver):
 
 def construct_optimizer(model, cfg):
     """slowfast/models/optimizer.py:15-112.  `adamw`: the fused tail, guarded with SOLVER.CLIP_GRAD_VAL, the opt-in
-    SVIT.GUARDED_STEP, SVIT.EMA_DECAY or SVIT.MONITOR (none a key of the default tree, like SVIT.REPRODUCIBLE).  `sgd`
+    SVIT.GUARDED_STEP, SVIT.EMA_DECAY, SVIT.MONITOR or SVIT.UPDATE_MONITOR (none a key of the default tree, like
+    SVIT.REPRODUCIBLE).  `sgd`
     and `adam`: always the guarded tail (GuardedClipSGD / GuardedClipAdam)."""
     s = cfg.SOLVER
     if not s.ZERO_WD_1D_PARAM:
@@ -558,9 +586,11 @@ def construct_optimizer(model, cfg):
             return GuardedClipSGD(model, momentum=s.MOMENTUM, dampening=s.DAMPENING, nesterov=s.NESTEROV, **common)
         return GuardedClipAdam(model, betas=(0.9, 0.999), eps=1e-8, **common)
     # (SVIT.EMA_DECAY: the moving average's update count is derived from the guarded tail's step record, svit_amd/ema.py;
-    #  SVIT.MONITOR: so is the step index of the per-tensor statistics, svit_amd/monitor.py)
+    #  SVIT.MONITOR / SVIT.UPDATE_MONITOR: so is the step index of the per-tensor statistics, svit_amd/monitor.py and
+    #  svit_amd/updmon.py)
     if (getattr(cfg.SVIT, "GUARDED_STEP", False) or cfg.SOLVER.CLIP_GRAD_VAL
-            or getattr(cfg.SVIT, "EMA_DECAY", None) is not None or getattr(cfg.SVIT, "MONITOR", False)):
+            or getattr(cfg.SVIT, "EMA_DECAY", None) is not None or getattr(cfg.SVIT, "MONITOR", False)
+            or getattr(cfg.SVIT, "UPDATE_MONITOR", False)):
         return GuardedClipAdamW(model, lr=cfg.SOLVER.BASE_LR, weight_decay=cfg.SOLVER.WEIGHT_DECAY,
                                 clip_grad_l2norm=cfg.SOLVER.CLIP_GRAD_L2NORM, clip_grad_value=cfg.SOLVER.CLIP_GRAD_VAL,
                                 max_consecutive_skips=getattr(cfg.SVIT, "MAX_CONSECUTIVE_SKIPS", None),

@@ -107,6 +107,7 @@ def _train_epoch_accumulated(train_loader, step, optimizer, train_meter, cur_epo
         train_meter.iter_toc()
         train_meter.log_iter_stats(cur_epoch, cur_iter)
         _log_tensor_stats(optimizer, cfg, cur_iter)
+        _log_update_stats(optimizer, cfg, cur_iter)
         _log_activation_stats(step, cfg, cur_iter)
         train_meter.iter_tic()
     stats = train_meter.log_epoch_stats(cur_epoch)
@@ -153,6 +154,7 @@ def _train_epoch_fed(train_loader, step, optimizer, train_meter, cur_epoch, cfg,
             train_meter.iter_toc()
             train_meter.log_iter_stats(cur_epoch, cur_iter)
             _log_tensor_stats(optimizer, cfg, cur_iter)
+            _log_update_stats(optimizer, cfg, cur_iter)
             _log_activation_stats(step, cfg, cur_iter)
             train_meter.iter_tic()
     finally:
@@ -167,6 +169,19 @@ def _log_tensor_stats(optimizer, cfg, cur_iter):
     line {"_type": "train_tensor_stats", ...} -- norms per layer of the period's last recorded step, the culprits of its
     dropped steps.  Nothing without a monitor."""
     mon = getattr(optimizer, "monitor", None)
+    if mon is None or (cur_iter + 1) % cfg.LOG_PERIOD != 0:
+        return None
+    stats = mon.log_stats(mon.read())
+    if stats is not None:
+        log_json_stats(stats)
+    return stats
+
+
+def _log_update_stats(optimizer, cfg, cur_iter):
+    """once per cfg.LOG_PERIOD, with an updmon.UpdateMonitor attached to the optimizer: ONE read of its ring and one JSON
+    line {"_type": "train_update_stats", ...} -- the step's and the weights' norm per layer of the period's last recorded
+    step, the tensors most of whose elements did not move.  Nothing without a monitor."""
+    mon = getattr(optimizer, "update_monitor", None)
     if mon is None or (cur_iter + 1) % cfg.LOG_PERIOD != 0:
         return None
     stats = mon.log_stats(mon.read())
@@ -241,6 +256,7 @@ def train_epoch(train_loader, step_or_model, optimizer, train_meter, cur_epoch, 
         train_meter.iter_toc()
         train_meter.log_iter_stats(cur_epoch, cur_iter)
         _log_tensor_stats(optimizer, cfg, cur_iter)
+        _log_update_stats(optimizer, cfg, cur_iter)
         _log_activation_stats(step_or_model, cfg, cur_iter)
         train_meter.iter_tic()
     stats = train_meter.log_epoch_stats(cur_epoch)
