@@ -800,6 +800,104 @@ int svit_act_stats(const svit_act_site* sites, const int32_t* slots, int64_t n_s
                    const int32_t* geom, const svit_step_dev* dev_rec, void* ring, int64_t R, int64_t* state,
                    void* workspace, int64_t workspace_bytes, void* stream);
 
+/* Per-head ATTENTION statistics of chosen query rows, from the operands a saving forward keeps for its backward
+ * (svit_amd/attnmon.py): by the operand convention of svit_attn_fwd, qa . ka^T over columns [0, 96 + J) is the score in
+ * the log2 domain with the relative-position bias folded in, so
+ *     p[q, k] = exp2( sum_j qa[q, j] * ka[k, j] - lse2[q] )
+ * and no table, index map or interpolation is restated.  Two launches at the end of a saving forward write one row of a
+ * ring in device memory; the attention kernels are not touched.
+ *
+ * A site (one kept block; HOST memory, the table travels in the kernel arguments, 1 <= n_sites <= SVIT_ATTN_MAX_SITES):
+ *   qa bf16 [B,heads,Nq,DA], ka bf16 [B,heads,Nk,DA] (16-byte aligned), lse2 f32 [B,heads,Nq] (4-byte aligned),
+ *   maps f32 [maps_samples,heads,n_probe,Nk] or NULL (4-byte aligned); DA = 128 or 160; bias_cols = J, 0 = all DA - 96;
+ *   Lq / Lk: the patch tokens of the query / key grid, n_obj the object tokens: Nq = 1 + Lq + n_obj, Nk = 1 + Lk + n_obj
+ *   (token 0 is cls, tokens 1 .. L the patches, the rest the objects); slot: the site's ring slot, distinct, inside
+ *   [0, n_slots); ent_base: its first entry in a ring row -- it owns entries ent_base + head * n_groups + group, inside
+ *   [0, ent_slots), shared with no other site; first_wg is filled in by the library in its own copy.
+ * The probe (HOST memory): 1 <= n_groups <= 3 query groups of distinct kinds, in entry order --
+ *   SVIT_ATTN_CLS    row 0;
+ *   SVIT_ATTN_OBJ    rows 1 + Lq .. Nq - 1 (none when n_obj = 0);
+ *   SVIT_ATTN_PATCH  rows 1 + ((2 i + 1) * Lq) / (2 K) for i < K, integer division, or all Lq patch rows when Lq <= K
+ *                    (1 <= K <= 256);
+ * n_probe of a site is the sum of its groups' rows, and a map holds them in that order.  every >= 1; maps_samples >= 0
+ * (samples past B are not stored).
+ *
+ * Per probe row: s_k = sum over columns j < 96 + J of qa[q, j] * ka[k, j], accumulated in fp32 in column order over
+ * products that are exact (bf16 x bf16); d_k = s_k - lse2[q] in fp32; p_k = exp2(d_k) by the hardware's fp32 exp2
+ * (results below 2^-126 may be flushed to zero).  Columns >= 96 + J are never multiplied: what they hold, NaN included,
+ * changes nothing.  In fp64: sum_p = sum_k p_k, H = - sum_k p_k d_k (bits), m_cls = p_0, m_obj = sum_{k > Lk} p_k, and
+ * pmax = max_k p_k.  A row is BAD when lse2[q] or any s_k has all exponent bits set (integer images, never a float
+ * compare); bad rows enter no sum, and their map rows hold no meaning.
+ *
+ * The ring: R rows of SVIT_ATTN_HEADER_BYTES + 64 * ent_slots bytes, 16-byte aligned; the HOST writes all of it when it
+ * is created or reset (pass = step = -1, every entry the empty entry).
+ *   row header, 48 bytes
+ *     offset  0  int64 pass        the pass counter's value when the row was written, from 0; -1: never written
+ *     offset  8  int64 step        dev_rec->applied + dev_rec->skipped, the optimizer step this pass feeds; -1 without
+ *     offset 16  int32 B, Tx, T0, H0, W0, n_sites   as svit_act_stats' header
+ *     offset 40  int32 row         the rows-written counter's value when the row was written (it lies at row % R)
+ *     offset 44  int32 reserved    0
+ *   entry e at offset 48 + 64 * e, 64 bytes: the good probe rows of one (slot, head, group) over all samples
+ *     offset  0  double sum_H, sum_pmax, sum_cls, sum_obj, sum_p   sums of H, pmax, m_cls, m_obj and sum_p
+ *     offset 40  float  min_H      the smallest (float) H; 0 when there is no good row
+ *     offset 44  int32  min_row    its row code b * Nq + q, the smallest code among ties; -1 when there is none
+ *     offset 48  float  sum_dev    the largest (float) |sum_p - 1|: how far the probe's sum lies from svit_attn_fwd's lse2
+ *     offset 52  int32  rows       probe rows, good and bad
+ *     offset 56  int32  n_bad      bad rows; -1: no site of this pass owns the entry (the rest is then the empty entry:
+ *                                  zeros, min_row = first_bad = -1)
+ *     offset 60  int32  first_bad  the smallest row code b * Nq + q among the bad rows, -1 when there is none
+ * state: int64 [4] in device memory, written by the host when it is created or reset: [0] passes so far (0), [1] rows
+ * written so far (0), [2] the pass whose probabilities the maps hold (-1: none yet), [3] reserved (0).
+ *
+ * A pass is DUE when (dev_rec->applied + dev_rec->skipped) % every == 0, read on the device; without a dev_rec when
+ * pass % every == 0.
+ *   stage 1   one workgroup of 256 threads per (site, sample, head, group), found by bisection over first_wg in the
+ *             arguments (workgroup-uniform; the library's copy of the table is ordered by falling Nk * DA, ties in table
+ *             order, so that the long workgroups start first -- entries and slots do not depend on it); rows over its 4
+ *             waves, keys over lanes, 64 keys at a time staged in LDS; a fixed-order reduction and ONE 64-byte partial
+ *             at slot `workgroup` of the workspace; with a map pointer and sample < maps_samples also the
+ *             probabilities of its rows.  With a dev_rec whose step is not due it returns before any load of qa, ka or
+ *             lse2.  It never reads `state`: WITHOUT a dev_rec it therefore works on every pass, and `every` then only
+ *             thins the ring.  svit_attn_stats_workspace(workgroups), HOST ONLY, returns the bytes (SVIT_ERR_ARG,
+ *             negative, for workgroups < 1 or above 2^20).
+ *   stage 2   ONE workgroup under svit_meter_push's contract for the counters: due -- folds the partials of every entry
+ *             in sample order, writes the entries, the empty entries and the header of ring row state[1] % R, sets
+ *             state[2] = pass when a site has a map and advances state[1]; always -- advances state[0] (without a
+ *             dev_rec, a pass that is not due still sets state[2], since stage 1 stored its maps).
+ * EXACTLY two launches; no atomics, no ticket, no allocation, copy or synchronisation: capturable, and a row is
+ * bit-identical from run to run and from the eager pass to a replay.  Nothing but the ring row, the workspace, the maps
+ * and state is written.
+ *
+ * svit_attn_sites_check, HOST ONLY, and svit_attn_stats before any HIP call: SVIT_ERR_ARG for a NULL table or probe,
+ * n_sites, n_slots (1 .. 1024) or ent_slots (1 .. 1024) out of range, a probe with no or more than 3 groups, an unknown
+ * or repeated kind, K outside 1 .. 256, every < 1 or maps_samples < 0; per site a NULL qa, ka or lse2, B, heads, Lq or
+ * Lk < 1, n_obj < 0, DA not 128 or 160, bias_cols outside [0, DA - 96], 1 + Lq + n_obj != Nq, 1 + Lk + n_obj != Nk,
+ * B * heads * max(Nq, Nk) above 2^31 - 1, a slot outside [0, n_slots) or named twice, entries outside [0, ent_slots) or
+ * owned twice; SVIT_ERR_ALIGN for a qa or ka not 16-byte or an lse2 or maps not 4-byte aligned.  *total_wgs (may be
+ * NULL) receives the workgroups of stage 1.  svit_attn_stats besides: SVIT_ERR_ARG for a NULL geom, ring, state or
+ * workspace, R < 1, workspace_bytes below svit_attn_stats_workspace(workgroups); SVIT_ERR_ALIGN for a ring or workspace
+ * not 16-byte aligned, state or dev_rec not 8-byte aligned.  dev_rec may be NULL.  The sizes of the ring and of the maps
+ * are the caller's to get right. */
+#define SVIT_ATTN_MAX_SITES 32
+#define SVIT_ATTN_HEADER_BYTES 48
+#define SVIT_ATTN_ENTRY_BYTES 64
+#define SVIT_ATTN_CLS 0
+#define SVIT_ATTN_OBJ 1
+#define SVIT_ATTN_PATCH 2
+typedef struct {
+  const void* qa; const void* ka; const float* lse2; float* maps;
+  int32_t B, heads, Nq, Nk, DA, bias_cols, Lq, Lk, n_obj, slot, ent_base, first_wg;
+} svit_attn_site;
+typedef struct {
+  int32_t n_groups, kind[3], K, every, maps_samples, reserved;
+} svit_attn_probe;
+int64_t svit_attn_stats_workspace(int64_t total_wgs);
+int svit_attn_sites_check(const svit_attn_site* sites, int64_t n_sites, int64_t n_slots, int64_t ent_slots,
+                          const svit_attn_probe* probe, int64_t* total_wgs);
+int svit_attn_stats(const svit_attn_site* sites, int64_t n_sites, int64_t n_slots, int64_t ent_slots,
+                    const svit_attn_probe* probe, const int32_t* geom, const svit_step_dev* dev_rec, void* ring,
+                    int64_t R, int64_t* state, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* HOST ONLY (no stream, no launch): the bias corrections svit_adamw_step derives from its `step` argument, by the very
  * same host code: pair k-1 = (1 - powf(beta1, k), sqrtf(1 - powf(beta2, k))) for steps k = 1, 2, ... up to and including
  * the first step at which both values are exactly 1.0f; past the table both are 1.0f.  *n_entries receives that length

@@ -249,6 +249,8 @@ class Engine:
         # the actmon.ActivationMonitor `model.attach_activation_monitor` hung behind every saving forward: two launches
         # over the LayerNorm statistics and log-sum-exps the pass keeps for its backward anyway (None: not one launch more)
         self.act_monitor = None
+        # the attnmon.AttentionMonitor `model.attach_attention_monitor` hung behind it: two launches more
+        self.attn_monitor = None
 
     # ------------------------------------------------------------------ helpers ----------
     def refresh_weights(self):
@@ -391,6 +393,8 @@ class Engine:
         st.update(x_last=x if save else None, mean=mean, rstd=rstd, thw=thw, thw0=(T, Ho, Wo))
         if save and self.act_monitor is not None:
             self.act_monitor.enqueue(st)
+        if save and self.attn_monitor is not None:
+            self.attn_monitor.enqueue(st)
         # the batched interpolation results belong to THIS pass: a stand-alone _block_fwd afterwards (tests, tools) interpolates
         # its own tables.  The fp32 / bf16 buffers are cached per (geometry, save) and the saved `tabs` of a pass are views of
         # them: at most ONE saved forward per geometry may be awaiting its backward (the step's passes all differ in geometry

@@ -126,6 +126,8 @@ class GraphedTrainStep:
         self._update_monitor = getattr(optimizer, "update_monitor", None)
         # ... and the actmon.ActivationMonitor attached to the MODEL now: its two launches end the captured forward
         self._act_monitor = self.core.engine.act_monitor
+        # ... and the attnmon.AttentionMonitor: two more behind those
+        self._attn_monitor = getattr(self.core.engine, "attn_monitor", None)
         self.loss_fun = loss_fun
         self.dp = model if hasattr(model, "_on_ready") and (getattr(model, "world_size", 1) > 1 or
                                                            getattr(model, "force_collectives", False)) else None
@@ -325,6 +327,7 @@ class GraphedTrainStep:
             raise hip.SvitHipError("a parameter's requires_grad changed after this GraphedTrainStep was captured (it "
                                    "froze everything below position %d): rebuild the optimizer and the step" % self.cut)
         _check_act_monitor(self.core, self._act_monitor, "GraphedTrainStep")
+        _check_attn_monitor(self.core, self._attn_monitor, "GraphedTrainStep")
         if self.optimizer is not None:
             _check_ema(self.optimizer, self._ema, "GraphedTrainStep")
             _check_monitor(self.optimizer, self._monitor, "GraphedTrainStep")
@@ -473,6 +476,7 @@ class AccumulatedTrainStep:
         self._monitor = optimizer.monitor
         self._update_monitor = getattr(optimizer, "update_monitor", None)
         self._act_monitor = core.engine.act_monitor
+        self._attn_monitor = getattr(core.engine, "attn_monitor", None)
         self.meter = meter
         if meter is not None:
             if getattr(meter, "virtual_ranks", None) != k:
@@ -491,6 +495,7 @@ class AccumulatedTrainStep:
         if len(batches) != self.k:
             raise hip.SvitHipError("AccumulatedTrainStep holds %d micro-steps, got %d batches" % (self.k, len(batches)))
         _check_act_monitor(self.core, self._act_monitor, "AccumulatedTrainStep")
+        _check_attn_monitor(self.core, self._attn_monitor, "AccumulatedTrainStep")
         self.micro_steps[0].check_flags()       # (every micro-step holds the optimizer's cut)
         _check_ema(self.optimizer, self._ema, "AccumulatedTrainStep")
         _check_monitor(self.optimizer, self._monitor, "AccumulatedTrainStep")
@@ -772,6 +777,16 @@ def _check_act_monitor(core, monitor, what):
                                "its forward holds the launches of then -- rebuild the step"
                                % (what, "one" if monitor is not None else "none",
                                   "one" if core.engine.act_monitor is not None else "none"))
+
+
+def _check_attn_monitor(core, monitor, what):
+    """refuse a replay after another attnmon.AttentionMonitor (or none) was attached to the model than the step was
+    built with"""
+    now = getattr(core.engine, "attn_monitor", None)
+    if now is not monitor:
+        raise hip.SvitHipError("the model's attached AttentionMonitor changed after this %s was built (%s then, %s now): "
+                               "its forward holds the launches of then -- rebuild the step"
+                               % (what, "one" if monitor is not None else "none", "one" if now is not None else "none"))
 
 
 def _is_feeder(batch):

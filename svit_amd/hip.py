@@ -135,6 +135,19 @@ class ActSite(C.Structure):
     _fields_ = [("a", vp), ("b", vp), ("rows", i32), ("first_window", i32)]
 
 
+class AttnSite(C.Structure):
+    """svit_attn_site: the attention operands of one kept block the attention monitor probes"""
+    _fields_ = [("qa", vp), ("ka", vp), ("lse2", vp), ("maps", vp), ("B", i32), ("heads", i32), ("Nq", i32), ("Nk", i32),
+                ("DA", i32), ("bias_cols", i32), ("Lq", i32), ("Lk", i32), ("n_obj", i32), ("slot", i32),
+                ("ent_base", i32), ("first_wg", i32)]
+
+
+class AttnProbe(C.Structure):
+    """svit_attn_probe: the query groups (kinds 0 cls, 1 obj, 2 patch:K), the due period and the samples with maps"""
+    _fields_ = [("n_groups", i32), ("kind", i32 * 3), ("K", i32), ("every", i32), ("maps_samples", i32),
+                ("reserved", i32)]
+
+
 class StepHost(C.Structure):
     """svit_step_host: the part of the guarded optimiser's step record the host uploads before every step"""
     _fields_ = [("lr", f32 * 2), ("weight_decay", f32 * 2), ("max_norm", f32), ("clip_value", f32),
@@ -230,6 +243,9 @@ _SIGS = {
     "svit_act_stats_workspace": (i64, [i64]),
     "svit_act_sites_check": (i32, [C.POINTER(ActSite), vp, i64, i64, C.POINTER(i64)]),
     "svit_act_stats": (i32, [C.POINTER(ActSite), vp, i64, i64, vp, vp, vp, i64, vp, vp, i64, vp]),
+    "svit_attn_stats_workspace": (i64, [i64]),                                 # host only, like the next one
+    "svit_attn_sites_check": (i32, [C.POINTER(AttnSite), i64, i64, i64, C.POINTER(AttnProbe), C.POINTER(i64)]),
+    "svit_attn_stats": (i32, [C.POINTER(AttnSite), i64, i64, i64, C.POINTER(AttnProbe), vp, vp, vp, i64, vp, vp, i64, vp]),
     "svit_head_fwd": (i32, [C.POINTER(HeadArgs), vp]),
     "svit_head_bwd": (i32, [C.POINTER(HeadBwdArgs), vp]),
     "svit_head_eval": (i32, [C.POINTER(HeadArgs), i32, vp]),

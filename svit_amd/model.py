@@ -309,6 +309,18 @@ class SViT(nn.Module):
         if monitor is not None and monitor.optimizer is not None:
             monitor.optimizer.act_monitor = monitor
 
+    def attach_attention_monitor(self, monitor):
+        """monitor: an attnmon.AttentionMonitor built over this model -- every saving `engine.forward` from now on ends
+        with its two launches (behind the activation monitor's), so the eager training forward, a GraphedTrainStep
+        captured AFTERWARDS and every micro-step of an accumulated step record the attention statistics; a step captured
+        before refuses its replay.  None: detach."""
+        if self.engine is None:
+            raise hip.SvitHipError("attach_attention_monitor needs a finalized (on-GPU) SViT")
+        if monitor is not None and getattr(monitor, "model", None) is not self:
+            raise ValueError("attach_attention_monitor: the AttentionMonitor was built over another model (its entries "
+                             "and geometry are this model's plan)")
+        self.engine.attn_monitor = monitor
+
     # -- frozen parameters (svit_amd/freeze.py) -----------------------------------------------------
     def freeze_below(self, cut):
         """Freeze every parameter at a network position below `cut` and unfreeze the rest: position 0 is the stem

@@ -1199,6 +1199,76 @@ def act_stats(sites, slots, n_slots, geom, dev_rec, ring, R, state, workspace):
              ptr(state), ptr(workspace), workspace.numel())
 
 
+ATTN_GROUP_KINDS = {"cls": 0, "obj": 1, "patch": 2}
+
+
+def attn_stats_workspace(total_wgs):
+    """bytes of svit_attn_stats' workspace for a site table of that many stage-1 workgroups (host only)"""
+    b = int(hip.load().svit_attn_stats_workspace(total_wgs))
+    if b < 0:
+        hip.check(b, "svit_attn_stats_workspace (%d workgroups)" % total_wgs)
+    return b
+
+
+def attn_site_table(sites, groups, K, every, maps_samples):
+    """sites: [dict(qa, ka, lse2, maps (device addresses, maps may be None), B, heads, Nq, Nk, DA, bias_cols, Lq, Lk,
+    n_obj, slot, ent_base)]; groups: kinds in entry order (0 cls, 1 obj, 2 patch) -> (svit_attn_site array,
+    svit_attn_probe): what the two calls below take.  Nothing is checked here beyond the number of groups."""
+    tab = (hip.AttnSite * max(1, len(sites)))()
+    for i, s in enumerate(sites):
+        t = tab[i]
+        t.qa, t.ka, t.lse2, t.maps = s["qa"], s["ka"], s["lse2"], s.get("maps")
+        for k in ("B", "heads", "Nq", "Nk", "DA", "bias_cols", "Lq", "Lk", "n_obj", "slot", "ent_base"):
+            setattr(t, k, s[k])
+        t.first_wg = 0
+    probe = hip.AttnProbe()
+    if len(groups) > 3:
+        raise hip.SvitHipError("attn_site_table: at most 3 query groups, got %d" % len(groups))
+    probe.n_groups = len(groups)
+    for i, k in enumerate(groups):
+        probe.kind[i] = k
+    probe.K, probe.every, probe.maps_samples, probe.reserved = K, every, maps_samples, 0
+    return tab, probe
+
+
+def attn_sites_check(sites, n_slots, ent_slots, groups, K=32, every=1, maps_samples=0):
+    """svit_attn_sites_check: raises for a site table or a probe the attention statistics would refuse (host only, needs
+    no device) -> the workgroups of stage 1"""
+    import ctypes
+    tab, probe = attn_site_table(sites, groups, K, every, maps_samples)
+    wgs = ctypes.c_int64(0)
+    hip.check(hip.load().svit_attn_sites_check(tab, len(sites), n_slots, ent_slots, ctypes.byref(probe),
+                                               ctypes.byref(wgs)),
+              "svit_attn_sites_check (%d sites, %d slots, %d entries)" % (len(sites), n_slots, ent_slots))
+    return int(wgs.value)
+
+
+def attn_stats(sites, n_slots, ent_slots, groups, K, every, maps_samples, geom, dev_rec, ring, R, state, workspace):
+    """the attention statistics of one pass into row (rows written % R) of `ring` when the pass is due (svit_attn_stats;
+    two launches).  sites, groups: as attn_site_table takes them; geom: (B, Tx, T0, H0, W0); dev_rec: the guarded
+    optimizer's int32 [12] record or None; ring: uint8 [R * (48 + 64 * ent_slots)], state: int64 [4], workspace: uint8"""
+    import ctypes
+    import numpy as np
+    _chk_dev(ring, state, workspace)
+    dev = ring.device
+    if dev_rec is not None:
+        _chk_dev(dev_rec)
+        if dev_rec.dtype != torch.int32 or dev_rec.numel() != 12 or dev_rec.device != dev:
+            raise hip.SvitHipError("attn_stats: the step record is int32 [12] on %s" % (dev,))
+    if state.dtype != torch.int64 or state.numel() != 4 or state.device != dev:
+        raise hip.SvitHipError("attn_stats: the counters are int64 [4] on %s" % (dev,))
+    if (ring.dtype != torch.uint8 or workspace.dtype != torch.uint8 or workspace.device != dev or R < 1
+            or ent_slots < 1 or ring.numel() != R * (48 + 64 * ent_slots)):
+        raise hip.SvitHipError("attn_stats: the ring is uint8 [R * (48 + 64 * %d)] and the workspace uint8, on %s"
+                               % (ent_slots, dev))
+    g = np.ascontiguousarray(np.asarray(geom, dtype=np.int32))
+    if g.shape != (5,):
+        raise hip.SvitHipError("attn_stats: geom is (B, Tx, T0, H0, W0)")
+    tab, probe = attn_site_table(sites, groups, K, every, maps_samples)
+    hip.call("svit_attn_stats", tab, len(sites), n_slots, ent_slots, ctypes.byref(probe), g.ctypes.data, ptr(dev_rec),
+             ptr(ring), R, ptr(state), ptr(workspace), workspace.numel())
+
+
 # ---------------------------------------------------------------- head (K15) ----------------
 def _head_args(tokens, T, O, keep, head_params, outs):
     a = hip.HeadArgs()

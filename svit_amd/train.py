@@ -109,6 +109,7 @@ def _train_epoch_accumulated(train_loader, step, optimizer, train_meter, cur_epo
         _log_tensor_stats(optimizer, cfg, cur_iter)
         _log_update_stats(optimizer, cfg, cur_iter)
         _log_activation_stats(step, cfg, cur_iter)
+        _log_attention_stats(step, cfg, cur_iter)
         train_meter.iter_tic()
     stats = train_meter.log_epoch_stats(cur_epoch)
     train_meter.reset()
@@ -156,6 +157,7 @@ def _train_epoch_fed(train_loader, step, optimizer, train_meter, cur_epoch, cfg,
             _log_tensor_stats(optimizer, cfg, cur_iter)
             _log_update_stats(optimizer, cfg, cur_iter)
             _log_activation_stats(step, cfg, cur_iter)
+            _log_attention_stats(step, cfg, cur_iter)
             train_meter.iter_tic()
     finally:
         producer.stop()
@@ -197,6 +199,21 @@ def _log_activation_stats(step_or_model, cfg, cur_iter):
     non-finite activations.  Nothing without a monitor."""
     core = getattr(step_or_model, "core", None) or getattr(step_or_model, "module", step_or_model)
     mon = getattr(getattr(core, "engine", None), "act_monitor", None)
+    if mon is None or (cur_iter + 1) % cfg.LOG_PERIOD != 0:
+        return None
+    stats = mon.log_stats(mon.read())
+    if stats is not None:
+        log_json_stats(stats)
+    return stats
+
+
+def _log_attention_stats(step_or_model, cfg, cur_iter):
+    """once per cfg.LOG_PERIOD, with an attnmon.AttentionMonitor attached to the model (the step's, or the model itself):
+    ONE read of its ring and one JSON line {"_type": "train_attention_stats", ...} -- per block and query group the
+    normalised entropy and the object-key mass of the period's last recorded pass, the head closest to collapse.
+    Nothing without a monitor."""
+    core = getattr(step_or_model, "core", None) or getattr(step_or_model, "module", step_or_model)
+    mon = getattr(getattr(core, "engine", None), "attn_monitor", None)
     if mon is None or (cur_iter + 1) % cfg.LOG_PERIOD != 0:
         return None
     stats = mon.log_stats(mon.read())
@@ -258,6 +275,7 @@ def train_epoch(train_loader, step_or_model, optimizer, train_meter, cur_epoch, 
         _log_tensor_stats(optimizer, cfg, cur_iter)
         _log_update_stats(optimizer, cfg, cur_iter)
         _log_activation_stats(step_or_model, cfg, cur_iter)
+        _log_attention_stats(step_or_model, cfg, cur_iter)
         train_meter.iter_tic()
     stats = train_meter.log_epoch_stats(cur_epoch)
     train_meter.reset()
