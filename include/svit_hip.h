@@ -175,6 +175,20 @@ int svit_layernorm_bwd(const void* dy /* f32, or bf16 when dy_is_bf16 */, int dy
 /* im2col for Conv3d(3->96, k(3,7,7), s(2,4,4), p(1,3,3)) (stem_helper.py:309-320):
  * video f32 [B,3,T,H,W] -> cols bf16 [B*T'*H'*W', 448] (441 taps, zero-padded to 448). */
 int svit_im2col_patch(const float* video, void* cols, int B, int T, int H, int W, void* stream);
+/* Data gradient of that convolution (csrc/dgrad.hip): the gradient of the loss with respect to the input clip, from the
+ * two bf16 operands the backward already holds.  With To = (T-1)/2 + 1, Ho = (H-1)/4 + 1, Wo = (W-1)/4 + 1:
+ *   dvideo[b,c,t,y,x] = sum over (to,kt), (yo,ky), (xo,kx) with t = 2to-1+kt, y = 4yo-3+ky, x = 4xo-3+kx, kt in [0,3),
+ *                       ky, kx in [0,7), (to,yo,xo) inside [0,To) x [0,Ho) x [0,Wo), of
+ *                       sum_{n<96} dtok[(b,to,yo,xo), n] * w16[n, ((c*3+kt)*7+ky)*7+kx]
+ * -- at most 2 x 2 x 2 output positions reach a pixel, so at most 768 products, each exact in fp32, summed in fp32 in
+ * a fixed order.  w16 is the forward GEMM's operand in svit_im2col_patch's column order; its pad columns 441..447 are
+ * never read.  Gather form: every element of dvideo is stored exactly once by the thread that owns it (no atomics,
+ * nothing to zero beforehand, nothing outside [B,3,T,H,W] touched), so the result is bit-identical from run to run and
+ * from an eager pass to a graph replay.  Any T, H, W >= 1 (T = 1: the stills, only kt = 1 exists).  Checked before any
+ * HIP call: a null pointer or a size < 1 is SVIT_ERR_ARG; dtok or w16 not 16-byte aligned, or dvideo not 4-byte
+ * aligned, SVIT_ERR_ALIGN; B*To*Ho*Wo >= 2^31 (or T*H >= 2^31) SVIT_ERR_SHAPE.  Element offsets are 64-bit. */
+int svit_patch_embed_dgrad(const void* dtok /* bf16 [B*To*Ho*Wo, 96] */, const void* w16 /* bf16 [96, 448] */,
+                           float* dvideo /* f32 [B,3,T,H,W] */, int B, int T, int H, int W, void* stream);
 /* The same operand straight from decoded uint8 frames: frames u8
  * [V,T,Hs,Ws,3] (T H W C per video, `frames_bytes` = size of the buffer), lut bf16 [3,256] =
  * bf16((u/255 - mean[c]) / std[c]) (datasets/utils.py:287-303), crops int32 [B,3] = (source video,

@@ -343,11 +343,23 @@ class Engine:
         return out
 
     # ------------------------------------------------------------------ forward ----------
-    def forward(self, video, drop_scales=None, save=True, cut=0):
+    def forward(self, video, drop_scales=None, save=True, cut=0, input_grad=False):
         """video f32 [B,3,Tx,S,S] (or U8Clips / AugClips / FramesView) -> (normed tokens f32 [B,N_last,C_last], saved-state dict).
         cut (svit_amd/freeze.py): the lowest trainable network position.  Block i saves its activations only when
         1 + i >= cut -- the backward stops above the frozen blocks -- and the stem's im2col operand is kept only for
-        cut 0.  What a pass computes does not depend on what it keeps."""
+        cut 0.  What a pass computes does not depend on what it keeps.
+        input_grad: the backward of this pass also leaves d loss / d clip in st["dvideo"], f32 [B,3,Tx,S,S] in the
+        coordinates of the S x S window the stem read (one launch more, svit_patch_embed_dgrad; needs save and cut 0).
+        False: the same launches as ever."""
+        if input_grad:
+            if cut > 0:
+                raise ValueError("input_grad=True under a frozen cut (cut %d): the backward stops above the frozen "
+                                 "blocks, which kept no activations -- unfreeze the model (freeze_below(0)) for an "
+                                 "input gradient" % cut)
+            if isinstance(video, FramesView):
+                raise ValueError("input_grad=True on a FramesView: the frames pass is a no-grad forward")
+            if not save:
+                raise ValueError("input_grad=True needs a saving forward (save=True)")
         plan, f = self.plan, self.flat
         if isinstance(video, U8Clips):       # decoded uint8 frames + crop table (svit_amd/input.py)
             cols, (To, Ho, Wo) = ops.im2col_patch_u8(video)
@@ -373,6 +385,9 @@ class Engine:
                                 f.p("pos_embed_temporal"), L, Tx, plan.objects, Tx > 1)
         st = {"B": B, "Tx": Tx, "n_obj": n_obj, "L0": L, "cols": cols if save and cut == 0 else None,
               "blocks": [], "cut": cut}
+        if input_grad:
+            st["input_grad"] = True
+            st["video_hw"] = tuple(video.shape[3:5])
         thw = (T, Ho, Wo)
         self._interp_tables(thw, save)
         hip.mark("stem")
@@ -561,6 +576,9 @@ class Engine:
         ops.special_token_grads(dx, f.g("cls_token"), f.g("object_queries"),
                                 f.g("pos_embed_temporal") if Tx > 1 else None, L, Tx, O, Tx > 1)
         dtok = ops.scale_cast(dx, gather=(L, 1))       # patch rows of every clip -> bf16 [B*L, C]
+        if st.get("input_grad"):    # d loss / d clip from the same operand, while it is certainly still this pass's
+            H, W = st["video_hw"]
+            st["dvideo"] = ops.patch_embed_dgrad(dtok, self.patch_w16, B, Tx, H, W)
         self._gemm_tn(dtok, st["cols"], f.g("patch_embed.proj.weight").view(C, 441), f.g("patch_embed.proj.bias"))
         self._flush_tn()
         self._join()

@@ -43,7 +43,7 @@ from . import hip, ops
 
 class GraphedTrainStep:
     def __init__(self, model, loss_fun, inputs, labels, warmup=2, frames_pass=False, mixup=None, optimizer=None,
-                 meter=None, accumulate=False):
+                 meter=None, accumulate=False, input_grad=False):
         """model: SViT or its DataParallel wrapper (train mode); loss_fun(preds, extra, labels) ->
         scalar; inputs: the reference's `inputs` list ([video f32 [B,3,T,S,S]]); labels: any
         tensor (or tuple/dict of tensors) `loss_fun` takes -- copied into static buffers.  The static input may be an
@@ -81,8 +81,14 @@ class GraphedTrainStep:
         accumulate: the step is a MICRO-step of an AccumulatedTrainStep (below) -- the captured body leaves out the bf16
         weight refresh and the gradient-buffer memset, so a replay ADDS this batch's gradients to what `flat.grad` holds;
         the owner issues both once per step, and the optimizer tail.  `optimizer=` and `meter=` are refused (the owner
-        holds them).  False: the same segments and launches as ever."""
+        holds them).  False: the same segments and launches as ever.
+        input_grad: the captured backward also computes d loss / d clip (one launch behind the stem's cast,
+        svit_patch_embed_dgrad) into `step.input_grad`, a static f32 [B,3,T,S,S] every replay refills -- for an fp32
+        clip, a U8Clips or an AugClips (in the coordinates of the S x S window; under `mixup`, with respect to the mixed
+        clip).  Refused under a frozen cut.  False: the same segments and launches as ever."""
         self.accumulate = bool(accumulate)
+        self.want_input_grad = bool(input_grad)
+        self.input_grad = None
         if self.accumulate and (optimizer is not None or meter is not None):
             raise hip.SvitHipError("GraphedTrainStep(accumulate=True) is a micro-step: the optimizer tail and the meter "
                                    "belong to the AccumulatedTrainStep that replays it, pass optimizer= / meter= there")
@@ -114,6 +120,8 @@ class GraphedTrainStep:
         self.cut = self.core.frozen_cut()
         self._flag_params = list(self.core.parameters())
         self._flags = [p.requires_grad for p in self._flag_params]
+        if self.want_input_grad:
+            _check_input_grad(self.cut)
         if optimizer is not None and optimizer.cut != self.cut:
             raise hip.SvitHipError("GraphedTrainStep(optimizer=...): the optimizer was built when the parameters' "
                                    "requires_grad flags froze everything below position %d, now they say %d -- rebuild "
@@ -198,7 +206,8 @@ class GraphedTrainStep:
         head_keep, core._head_keep = core._head_keep, None
         with torch.no_grad():
             # (the head alone trainable: nothing is kept, and backward() below only reports the ranks)
-            y, st = eng.forward(x, ds, save=self.cut <= len(core.plan.blocks) + 1, cut=self.cut)
+            y, st = eng.forward(x, ds, save=self.cut <= len(core.plan.blocks) + 1, cut=self.cut,
+                                input_grad=self.want_input_grad)
         n_obj = Tx * core.O
         frames_out = None
         if self.frames_pass and Tx > 1:
@@ -316,6 +325,8 @@ class GraphedTrainStep:
                     end()
         finally:
             eng._capture_fork = eng._capture_join = None
+        if self.want_input_grad:        # allocated inside the capture: the graph's pool keeps it, every replay refills it
+            self.input_grad = self._keepalive[0]["dvideo"]
         torch.cuda.current_stream(dev).wait_stream(cap)
         torch.cuda.synchronize(dev)
         self._side = torch.cuda.Stream(device=dev)
@@ -739,6 +750,14 @@ class GraphedEvalStep:
     @property
     def static_labels(self):
         return self.labels
+
+
+def _check_input_grad(cut):
+    """GraphedTrainStep(input_grad=True) under a frozen cut: the captured backward would stop above the stem"""
+    if cut > 0:
+        raise hip.SvitHipError("GraphedTrainStep(input_grad=True) under a frozen cut (the parameters' requires_grad "
+                               "flags freeze everything below position %d): the backward stops above the frozen blocks, "
+                               "which keep no activations -- unfreeze the model for an input gradient" % cut)
 
 
 def _check_ema(optimizer, ema, what):

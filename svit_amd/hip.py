@@ -185,6 +185,7 @@ _SIGS = {
     "svit_layernorm_bwd": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, i64, i32, vp,
                                  i64, vp]),
     "svit_im2col_patch": (i32, [vp, vp, i32, i32, i32, i32, vp]),
+    "svit_patch_embed_dgrad": (i32, [vp, vp, vp, i32, i32, i32, i32, vp]),
     "svit_im2col_patch_u8": (i32, [vp, i64, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     "svit_im2col_patch_u8_mix": (i32, [vp, i64, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     "svit_im2col_patch_u8_aug": (i32, [vp, i64, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),

@@ -128,6 +128,14 @@ class U8Clips(U8Input):
         self.extents = other.extents            # (host side: what the crop table was checked against)
         return self
 
+    def render(self):
+        """fp32 [B,3,T,S,S]: the normalised crops as a clip tensor (no mix) -- the values whose bf16 rounding the im2col
+        reads, and the coordinates of an input gradient (svit_amd/saliency.py); the identity records of the crop table
+        through augment.AugClips.render"""
+        from .augment import AugClips
+        return AugClips(self.frames, self.size, identity_records(self.crops, self.size), mean=self.mean, std=self.std,
+                        lut_f32=self.lut_f32).render()
+
 
 def identity_records(crops, size):
     """int32 [B,3] crop table (video, y0, x0) -> the int32 [B,16] augmentation records of the same integer crops

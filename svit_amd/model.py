@@ -55,13 +55,17 @@ def _trunc_normal_(t, std=0.02):
 
 class _Backbone(torch.autograd.Function):
     """video -> LayerNorm-ed tokens.  Parameter gradients are accumulated by the engine straight
-    into the flat grad buffer that every `param.grad` is a view of."""
+    into the flat grad buffer that every `param.grad` is a view of.  The gradient of `video` (svit_amd/saliency.py) is
+    computed when an fp32 clip tensor requires it and nothing is frozen, or when `input_grad` asks for it (inputs that
+    are not tensors: the gradient is then left in `model.last_input_grad`)."""
 
     @staticmethod
-    def forward(ctx, model, video, drop_scales, need_grad, anchor, cut):
+    def forward(ctx, model, video, drop_scales, need_grad, anchor, cut, input_grad):
+        wanted = bool(need_grad and cut == 0 and ctx.needs_input_grad[1] and video.dtype == torch.float32)
         with torch.no_grad():
-            y, st = model.engine.forward(video, drop_scales, save=need_grad, cut=cut)
+            y, st = model.engine.forward(video, drop_scales, save=need_grad, cut=cut, input_grad=wanted or input_grad)
         ctx.model, ctx.st, ctx.cut = model, (st if need_grad else None), cut
+        ctx.video_shape, ctx.keep_input_grad = (video.shape if wanted else None), bool(input_grad)
         return y
 
     @staticmethod
@@ -73,8 +77,15 @@ class _Backbone(torch.autograd.Function):
         with torch.no_grad():
             model.engine.backward(ctx.st, dy, on_ready=model._grad_ready_hook,
                                   ready_ranks=model._grad_ready_ranks)
+        dvideo = ctx.st.get("dvideo")
         ctx.st = None
-        return None, None, None, None, None, None
+        if ctx.keep_input_grad:
+            model.last_input_grad = dvideo
+        if ctx.video_shape is not None:
+            dvideo = dvideo.view(ctx.video_shape)
+        else:
+            dvideo = None
+        return None, dvideo, None, None, None, None, None
 
 
 class _Adopt(torch.autograd.Function):
@@ -224,6 +235,7 @@ class SViT(nn.Module):
         self._keep = None
         self._grad_views = None     # (cut, [(parameter, its view of the flat grad buffer)]) of the trainable parameters
         self._cut = 0               # svit_amd/freeze.py: lowest trainable network position, as the last pass read the flags
+        self.last_input_grad = None    # d loss / d clip of the last backward of a forward(..., input_grad=True)
         self._seg_cache = {}
 
     # -- parameters are registered under the reference's dotted names ---------------------------
@@ -444,10 +456,18 @@ class SViT(nn.Module):
                                                     act=0 if head.act_func == "softmax" else 1)
         return probs, {"obj_desc": xobj, "pred_bboxes": boxes, "pred_contact_state": contact}
 
-    def forward(self, x, metadata=None, bboxes=None, drop_scales=None, dropout_keep=None):
+    def forward(self, x, metadata=None, bboxes=None, drop_scales=None, dropout_keep=None, input_grad=False):
+        """input_grad: also compute d loss / d clip in the backward of this pass and leave it in
+        `self.last_input_grad` -- f32 [B,3,T,S,S] in the coordinates of the S x S window, i.e. with respect to
+        `clips.render()` for a U8Clips / AugClips (under cfg.MIXUP: to the mixed clip).  An fp32 clip tensor that
+        requires grad needs no request: its `.grad` is filled as by any torch module (svit_amd/saliency.py)."""
         if self.engine is None:
             raise hip.SvitHipError("SViT (svit_amd) has no CPU path: build it with "
                                    "build_model(cfg) / call .cuda() on an MI355X first")
+        if input_grad:
+            self.last_input_grad = None
+            if not torch.is_grad_enabled():
+                raise ValueError("input_grad=True in a no-grad pass: the input gradient comes out of the backward")
         x = x[0]
         if x.dim() == 4:  # image
             x = x.unsqueeze(2)
@@ -460,12 +480,14 @@ class SViT(nn.Module):
             cut = self.frozen_cut() if need_grad else 0   # the flags are read at every pass that may be differentiated
         except ValueError:      # nothing trainable: nothing to differentiate, as with any torch module (no optimizer exists)
             need_grad, cut = False, 0
-        if not need_grad:
-            tokens = _Backbone.apply(self, x, drop_scales, False, None, 0)
+        if input_grad:          # (refused under a frozen cut by the engine, by message)
+            tokens = _Backbone.apply(self, x, drop_scales, need_grad, self._anchor, cut, True)
+        elif not need_grad:
+            tokens = _Backbone.apply(self, x, drop_scales, False, None, 0, False)
         elif cut > len(self.plan.blocks) + 1:     # the head alone is trainable: autograd never enters the backbone
-            tokens = _Adopt.apply(self, _Backbone.apply(self, x, drop_scales, False, None, cut), self._anchor, cut)
+            tokens = _Adopt.apply(self, _Backbone.apply(self, x, drop_scales, False, None, cut, False), self._anchor, cut)
         else:
-            tokens = _Backbone.apply(self, x, drop_scales, need_grad, self._anchor, cut)
+            tokens = _Backbone.apply(self, x, drop_scales, need_grad, self._anchor, cut, False)
         n_obj = Tx * self.O
         if self.training and self.fused_head:
             return self.head_train(tokens, Tx, dropout_keep)

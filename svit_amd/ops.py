@@ -397,6 +397,26 @@ def im2col_patch(video):
     return cols, (To, Ho, Wo)
 
 
+def patch_embed_dgrad(dtok16, w16, B, T, H, W, out=None):
+    """The stem's data gradient (svit_patch_embed_dgrad): dtok16 bf16 [B*To*Ho*Wo, 96], the patch rows of block 0's dx,
+    and w16 bf16 [96, 448], the forward's weight operand -> f32 [B,3,T,H,W], every element stored."""
+    _chk_dev(dtok16, w16, out)
+    To, Ho, Wo = (T - 1) // 2 + 1, (H - 1) // 4 + 1, (W - 1) // 4 + 1
+    if dtok16.dtype != BF16 or tuple(dtok16.shape) != (B * To * Ho * Wo, HD):
+        raise hip.SvitHipError("patch_embed_dgrad: dtok must be bf16 [%d, %d] for a clip [%d,3,%d,%d,%d], got %s %s"
+                               % (B * To * Ho * Wo, HD, B, T, H, W, dtok16.dtype, tuple(dtok16.shape)))
+    if w16.dtype != BF16 or tuple(w16.shape) != (HD, 448):
+        raise hip.SvitHipError("patch_embed_dgrad: the weight operand must be bf16 [96, 448], got %s %s"
+                               % (w16.dtype, tuple(w16.shape)))
+    if out is None:
+        out = torch.empty((B, 3, T, H, W), device=dtok16.device, dtype=F32)
+    elif out.dtype != F32 or tuple(out.shape) != (B, 3, T, H, W):
+        raise hip.SvitHipError("patch_embed_dgrad: out must be f32 %s, got %s %s"
+                               % ((B, 3, T, H, W), out.dtype, tuple(out.shape)))
+    hip.call("svit_patch_embed_dgrad", ptr(dtok16), ptr(w16), ptr(out), B, T, H, W)
+    return out
+
+
 def _chk_extents(extents, fr):
     """the per-video extents of an AugClips -> the `_ext` suffix and the extra argument; None: the plain entry point"""
     if extents is None:
