@@ -19,7 +19,8 @@ LIB = os.path.join(OUT_DIR, "libsvit_hip.so")
 SOURCES = ["gemm_nt.hip", "gemm_tn.hip", "norm.hip", "misc.hip", "pool.hip", "attn_fwd.hip", "attn_bwd.hip",
            "loss.hip", "meter.hip", "input.hip", "head.hip", "randaug.hip", "feed.hip", "head_eval.hip", "solver.hip",
            "monitor.hip", "actmon.hip", "update.hip", "attnmon.hip", "dgrad.hip"]
-HEADERS = ["common.h", "attn_common.h", "gemm_epilogue.h", os.path.join("..", "..", "include", "svit_hip.h")]
+HEADERS = ["common.h", "attn_common.h", "gemm_epilogue.h", "seg_table.h", "tensor_walk.h",
+           os.path.join("..", "..", "include", "svit_hip.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -fno-slp-vectorize: hipcc's SLP pass packs adjacent fp32 multiplies / adds into v_pk_*_f32.  The
 # forms it emits that read a VGPR pair across its halves (op_sel / op_sel_hi), e.g.

@@ -5,6 +5,7 @@
 #include <mutex>
 #include <unordered_map>
 #include "common.h"
+#include "seg_table.h"
 #include "../../include/svit_hip.h"
 
 namespace {
@@ -584,18 +585,8 @@ __global__ __launch_bounds__(256) void adamw_guarded_kernel(float* __restrict__ 
 // looks a segment up.  Both kernels walk the buffer the way their plain twins do -- workgroup b takes the 1024 floats at
 // b * 1024 + pass * gridDim.x * 1024 -- and since windows and segments both ascend, a cursor that only moves forward finds
 // the segments a window meets: S scalar steps per workgroup for the whole buffer, and per 16-byte access one or two
-// compares (a window meets more than one segment only at a boundary).
-struct SegTable {
-  int64_t v[SVIT_MAX_SEGS][2];
-  int32_t S;
-};
-// is the quad at float index i, which lies in the window [lo, hi), inside a segment?  k: first segment that ends past lo
-__device__ __forceinline__ bool seg_inside(const SegTable& t, int& k, int64_t lo, int64_t hi, int64_t i) {
-  while (k < t.S && t.v[k][1] <= lo) ++k;
-  bool in = false;
-  for (int j = k; j < t.S && t.v[j][0] < hi; ++j) in |= (i >= t.v[j][0]) & (i < t.v[j][1]);
-  return in;
-}
+// compares (a window meets more than one segment only at a boundary).  SegTable and the cursor's test, seg_inside, are
+// csrc/seg_table.h's.
 
 // sumsq_kernel with the same element -> (workgroup, thread, pass) mapping: an element outside every segment adds nothing
 // and is not loaded, so the partials equal sumsq_kernel's on a buffer that holds zeros there (s >= 0: s + 0 is s).

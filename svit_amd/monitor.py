@@ -70,27 +70,27 @@ def stats_host(g, p, table, segs=None):
     return out
 
 
-class TensorMonitor:
-    """The statistics ring behind `optimizer`'s guard.
+class TensorRing:
+    """What TensorMonitor and updmon.UpdateMonitor share: the tensor table of `optimizer`'s flat buffer, a ring of `period`
+    rows in device memory that two launches per due step fill, and its reading.
 
-    optimizer: an optim.GuardedClipAdamW or one of its subclasses (AdamW plain, over segments or with learning-rate
-    scales; GuardedClipAdam; GuardedClipSGD).  period: rows of the ring, R -- cfg.LOG_PERIOD, the steps between two
-    `read()`s.  every: a step is recorded when its index (applied + dropped steps so far, from 0) is a multiple of it;
-    a dropped step is always recorded.
-
-    One tensor per parameter, in the order of the flat buffer: `names`, `shapes`, `table` int64 [Tn, 2].  Under a frozen
-    cut the optimizer's trainable segments decide which tensors are watched; the others come back masked.  Nothing is
-    attached by the constructor: `optimizer.attach_monitor(monitor)` (or `build_monitor`) does that."""
+    One tensor per parameter, in the order of the flat buffer: `names`, `shapes`, `numel`, `table` int64 [Tn, 2].  Under a
+    frozen cut the optimizer's trainable segments decide which tensors are watched (`frozen`); the others come back
+    masked.  A subclass names its config key (KEY), its module's row_dtype / empty_ring and its workspace query, and
+    supplies `_warm`, `enqueue`, `_dict` (rows -> what `read()` returns) and, where a row is not one due step,
+    `_due_rows`."""
+    KEY = row_dtype = empty_ring = workspace_bytes = None
 
     def __init__(self, optimizer, period, every=1):
         from .optim import GuardedClipAdamW
+        me = type(self).__name__
         if not isinstance(optimizer, GuardedClipAdamW):
-            raise TypeError("TensorMonitor needs an optim.GuardedClipAdamW or one of its subclasses, got %s: only the "
-                            "guarded tail keeps the step's decision and its step counters in device memory (set "
-                            "SVIT.GUARDED_STEP or SVIT.MONITOR before construct_optimizer)" % type(optimizer).__name__)
+            raise TypeError("%s needs an optim.GuardedClipAdamW or one of its subclasses, got %s: only the guarded tail "
+                            "keeps the step's decision and its step counters in device memory (set SVIT.GUARDED_STEP or "
+                            "SVIT.%s before construct_optimizer)" % (me, type(optimizer).__name__, self.KEY))
         for what, v in (("period", period), ("every", every)):
             if isinstance(v, bool) or not isinstance(v, int) or v < 1:
-                raise ValueError("TensorMonitor: %s is a positive int, got %r" % (what, v))
+                raise ValueError("%s: %s is a positive int, got %r" % (me, what, v))
         self.optimizer, self.flat = optimizer, optimizer.flat
         self.period, self.every = period, every
         flat = self.flat
@@ -99,23 +99,92 @@ class TensorMonitor:
         self.table = np.ascontiguousarray(
             np.array([[flat.slots[k][0], flat.slots[k][0] + flat.slots[k][1]] for k in self.names], dtype=np.int64))
         ops.tensor_table_check(self.table, flat.total)
+        self.numel = self.table[:, 1] - self.table[:, 0]
         self.segments = optimizer.segments              # None: nothing is frozen
         self.frozen = ~trainable_mask(self.table, self.segments)
         self.depth = flat.n_ranks - 2
         self.layer_ids = np.array([lrscale.layer_id(k, self.depth) for k in self.names], dtype=np.int64)
         dev = flat.data.device
-        Tn = len(self.names)
         self.table_dev = torch.from_numpy(self.table).to(dev)
-        self.workspace = torch.zeros(ops.tensor_stats_workspace(flat.total, Tn), dtype=torch.uint8, device=dev)
-        self.ring = torch.from_numpy(empty_ring(period, Tn).view(np.uint8).reshape(-1).copy()).to(dev)
+        self.workspace = torch.zeros(self.workspace_bytes(flat.total, len(self.names)), dtype=torch.uint8, device=dev)
+        self.ring = self._empty().to(dev)
         self.last_read = self._step_now()
         if dev.type == "cuda":
             self._warm()
+
+    def _empty(self):
+        return torch.from_numpy(self.empty_ring(self.period, len(self.names)).view(np.uint8).reshape(-1).copy())
 
     def _step_now(self):
         """index of the optimizer's last step (-1 before the first); synchronises"""
         s = self.optimizer.stats()
         return s["applied"] + s["skipped"] - 1
+
+    def reset(self):
+        """forget every row: the ring as it was created, the next `read()` starts behind the optimizer's last step"""
+        self.ring.copy_(self._empty())
+        self.last_read = self._step_now()
+
+    # ---- reading -----------------------------------------------------------------------------------------------------
+    def _rows(self, since):
+        """the ring's written rows of the steps after `since`, ordered by step (ONE device read)"""
+        ring = self.ring.cpu().numpy().view(self.row_dtype(len(self.names)))
+        rows = ring[ring["head"]["step"] > since]
+        return rows[np.argsort(rows["head"]["step"], kind="stable")]
+
+    def _masked(self, a):
+        """a [rows, Tn] with the frozen tensors masked"""
+        return np.ma.MaskedArray(a, mask=np.broadcast_to(self.frozen, a.shape).copy())
+
+    def _due_rows(self, rows):
+        """how many of the rows are steps that were due by `every`"""
+        return len(rows)
+
+    def read(self):
+        """the rows recorded since the last read, ordered by step, as the subclass's `read` lists them; `lost`: how many
+        multiples of `every` since the last read, up to the newest step the ring holds, have no row"""
+        rows = self._rows(self.last_read)
+        lost = 0
+        if len(rows):
+            now = int(rows["head"]["step"][-1])
+            due = now // self.every - self.last_read // self.every          # multiples of `every` in (last_read, now]
+            lost = due - self._due_rows(rows)
+            self.last_read = now
+        return self._dict(rows, lost)
+
+    def _layer_sums(self, *arrays):
+        """each [rows, Tn] array summed over lrscale's layer ids, frozen tensors left out: depth + 2 groups -- 0 the stem,
+        1 + i block i, depth + 1 the rest -> ([rows, depth + 2] per array, the mask of the groups whose tensors are all
+        frozen)"""
+        G = self.depth + 2
+        r = len(arrays[0])
+        sums = [np.zeros((r, G), dtype=np.float64 if a.dtype.kind == "f" else np.int64) for a in arrays]
+        seen = np.zeros(G, dtype=bool)
+        for t, lid in enumerate(self.layer_ids):
+            if self.frozen[t]:
+                continue
+            seen[lid] = True
+            for s, a in zip(sums, arrays):
+                s[:, lid] += a[:, t]
+        return sums, np.broadcast_to(~seen, (r, G)).copy()
+
+    @staticmethod
+    def _last(a):
+        """the last row of a by_layer array as log_stats prints it: six digits, None where masked or not finite"""
+        return [None if x is np.ma.masked or not np.isfinite(x) else float("%.6g" % x) for x in a[-1]]
+
+
+class TensorMonitor(TensorRing):
+    """The statistics ring behind `optimizer`'s guard.
+
+    optimizer: an optim.GuardedClipAdamW or one of its subclasses (AdamW plain, over segments or with learning-rate
+    scales; GuardedClipAdam; GuardedClipSGD).  period: rows of the ring, R -- cfg.LOG_PERIOD, the steps between two
+    `read()`s.  every: a step is recorded when its index (applied + dropped steps so far, from 0) is a multiple of it;
+    a dropped step is always recorded.  Nothing is attached by the constructor: `optimizer.attach_monitor(monitor)` (or
+    `build_monitor`) does that."""
+    KEY = "MONITOR"
+    row_dtype, empty_ring = staticmethod(row_dtype), staticmethod(empty_ring)
+    workspace_bytes = staticmethod(ops.tensor_stats_workspace)
 
     def _warm(self):
         """one call on four dummy elements, so that a later stream capture meets loaded code; neither the ring nor the
@@ -132,62 +201,31 @@ class TensorMonitor:
         ops.tensor_stats(self.flat.grad, self.flat.data, self.table_dev, self.table, self.segments,
                          self.optimizer.dev_rec, self.ring, self.period, self.every, self.workspace)
 
-    def reset(self):
-        """forget every row: the ring as it was created, the next `read()` starts behind the optimizer's last step"""
-        self.ring.copy_(torch.from_numpy(empty_ring(self.period, len(self.names)).view(np.uint8).reshape(-1).copy()))
-        self.last_read = self._step_now()
+    def _due_rows(self, rows):
+        """dropped steps are recorded too: only the multiples of `every` count (a dropped step between two due ones that
+        was overwritten leaves no trace and is not counted as lost)"""
+        return int((rows["head"]["step"] % self.every == 0).sum())
 
-    # ---- reading -----------------------------------------------------------------------------------------------------
-    def _rows(self, since):
-        """the ring's written rows of the steps after `since`, ordered by step (ONE device read)"""
-        ring = self.ring.cpu().numpy().view(row_dtype(len(self.names)))
-        rows = ring[ring["head"]["step"] > since]
-        return rows[np.argsort(rows["head"]["step"], kind="stable")]
+    def read(self):
+        """the rows recorded since the last read, ordered by step, as a dict of arrays [rows, Tn] (frozen tensors masked):
+        names, steps, applied, grad_norm = sqrt(sumsq_g) * optimizer.grad_scale, weight_norm, absmax, n_bad, first_bad,
+        the raw sumsq_g / sumsq_p, and `lost`: how many steps that were due by `every` since the last read the ring no
+        longer holds (R rows; an overrun is reported, not raised)"""
+        return super().read()
 
     def _dict(self, rows, lost):
-        m = np.broadcast_to(self.frozen, rows["entry"].shape)
-        e = rows["entry"]
-
-        def masked(a):
-            return np.ma.MaskedArray(a, mask=m.copy())
+        e, masked = rows["entry"], self._masked
         return {"names": list(self.names), "steps": rows["head"]["step"].copy(), "applied": rows["head"]["apply"] != 0,
                 "sumsq_g": masked(e["sumsq_g"].copy()), "sumsq_p": masked(e["sumsq_p"].copy()),
                 "grad_norm": masked(np.sqrt(e["sumsq_g"]) * float(self.optimizer.grad_scale)),
                 "weight_norm": masked(np.sqrt(e["sumsq_p"])), "absmax": masked(e["absmax_g"].copy()),
                 "n_bad": masked(e["n_bad"].copy()), "first_bad": masked(e["first_bad"].copy()), "lost": lost}
 
-    def read(self):
-        """the rows recorded since the last read, ordered by step, as a dict of arrays [rows, Tn] (frozen tensors masked):
-        names, steps, applied, grad_norm = sqrt(sumsq_g) * optimizer.grad_scale, weight_norm, absmax, n_bad, first_bad,
-        the raw sumsq_g / sumsq_p, and `lost`: how many steps that were due by `every` since the last read the ring no
-        longer holds (R rows; an overrun is reported, not raised -- a dropped step between two due ones that was
-        overwritten leaves no trace and is not counted).  `now` is the newest step the ring holds."""
-        rows = self._rows(self.last_read)
-        lost = 0
-        if len(rows):
-            now = int(rows["head"]["step"][-1])
-            due = now // self.every - self.last_read // self.every          # multiples of `every` in (last_read, now]
-            lost = due - int((rows["head"]["step"] % self.every == 0).sum())
-            out = self._dict(rows, lost)
-            self.last_read = now
-            return out
-        return self._dict(rows, lost)
-
     def by_layer(self, rows):
         """rows (what `read()` gave) summed over lrscale's layer ids: depth + 2 groups -- 0 the stem, 1 + i block i,
         depth + 1 the rest -- of grad_norm, weight_norm and ratio = grad_norm / weight_norm, each [rows, depth + 2]; a
         group whose tensors are all frozen is masked"""
-        G = self.depth + 2
-        r = len(rows["steps"])
-        sg, sp = np.zeros((r, G)), np.zeros((r, G))
-        seen = np.zeros(G, dtype=bool)
-        for t, lid in enumerate(self.layer_ids):
-            if self.frozen[t]:
-                continue
-            seen[lid] = True
-            sg[:, lid] += rows["sumsq_g"].data[:, t]
-            sp[:, lid] += rows["sumsq_p"].data[:, t]
-        mask = np.broadcast_to(~seen, (r, G)).copy()
+        (sg, sp), mask = self._layer_sums(rows["sumsq_g"].data, rows["sumsq_p"].data)
         gn = np.sqrt(sg) * float(self.optimizer.grad_scale)
         wn = np.sqrt(sp)
         with np.errstate(divide="ignore", invalid="ignore"):
@@ -228,10 +266,7 @@ class TensorMonitor:
         of its dropped steps; None when there is no row"""
         if not len(rows["steps"]):
             return None
-        layers = self.by_layer(rows)
-
-        def last(a):
-            return [None if x is np.ma.masked or not np.isfinite(x) else float("%.6g" % x) for x in a[-1]]
+        layers, last = self.by_layer(rows), self._last
         return {"_type": "train_tensor_stats", "step": int(rows["steps"][-1]), "applied": bool(rows["applied"][-1]),
                 "rows": int(len(rows["steps"])), "lost": int(rows["lost"]), "grad_norm": last(layers["grad_norm"]),
                 "weight_norm": last(layers["weight_norm"]), "ratio": last(layers["ratio"]),

@@ -1087,32 +1087,40 @@ def tensor_stats_workspace(n, Tn):
     return b
 
 
+def _chk_step_dev(what, dev_rec, dev):
+    if dev_rec.dtype != torch.int32 or dev_rec.numel() != 12 or dev_rec.device != dev:
+        raise hip.SvitHipError("%s: the step record is int32 [12] on %s" % (what, dev))
+
+
+def _chk_tensor_ring(what, names, bufs, table_dev, table_host, dev_rec, ring, R, entry_bytes, workspace):
+    """what tensor_stats and update_stats check alike: `bufs` (None: absent) are fp32 buffers of one size on one device, the
+    device table is the host's, the step record, a ring of R * (16 + entry_bytes * Tn) bytes and the workspace -> the host
+    table's address, Tn"""
+    _chk_dev(*bufs, table_dev, dev_rec, ring, workspace)
+    n, dev = bufs[0].numel(), bufs[0].device
+    tp, Tn = _chk_tensor_table(table_host)
+    for t in bufs:
+        if t is not None and (t.numel() != n or t.dtype != F32 or t.device != dev):
+            raise hip.SvitHipError("%s: %s are fp32 buffers of one size on one device" % (what, names))
+    if table_dev.dtype != torch.int64 or tuple(table_dev.shape) != (Tn, 2) or table_dev.device != dev:
+        raise hip.SvitHipError("%s: the device table is int64 [%d, 2] on %s, as the host's" % (what, Tn, dev))
+    _chk_step_dev(what, dev_rec, dev)
+    if (ring.dtype != torch.uint8 or workspace.dtype != torch.uint8 or ring.device != dev or workspace.device != dev
+            or R < 1 or ring.numel() != R * (16 + entry_bytes * Tn)):
+        raise hip.SvitHipError("%s: the ring is uint8 [R * (16 + %d * %d)] and the workspace uint8, on %s"
+                               % (what, entry_bytes, Tn, dev))
+    return tp, Tn
+
+
 def tensor_stats(g, p, table_dev, table_host, segs, dev_rec, ring, R, every, workspace):
     """per-tensor sums of squares of g and p, max |g|, count and first offset of the non-finite elements of g into row
     (step % R) of `ring`, when the step record says the step is due or was dropped (svit_tensor_stats; two launches).
     table_dev: int64 [Tn, 2] on the device, table_host: the same as numpy; segs: the trainable segments as numpy or None;
     ring: uint8 [R * (16 + 32 * Tn)] and workspace: uint8, both on the device"""
-    _chk_dev(g, p, table_dev, dev_rec, ring, workspace)
-    dev = g.device
-    tp, Tn = _chk_tensor_table(table_host)
-    if g.numel() != p.numel() or g.dtype != F32 or p.dtype != F32 or p.device != dev:
-        raise hip.SvitHipError("tensor_stats: g and p are fp32 buffers of one size on one device")
-    if table_dev.dtype != torch.int64 or tuple(table_dev.shape) != (Tn, 2) or table_dev.device != dev:
-        raise hip.SvitHipError("tensor_stats: the device table is int64 [%d, 2] on %s, as the host's" % (Tn, dev))
-    if dev_rec.dtype != torch.int32 or dev_rec.numel() != 12 or dev_rec.device != dev:
-        raise hip.SvitHipError("tensor_stats: the step record is int32 [12] on %s" % (dev,))
-    if (ring.dtype != torch.uint8 or workspace.dtype != torch.uint8 or ring.device != dev or workspace.device != dev
-            or R < 1 or ring.numel() != R * (16 + 32 * Tn)):
-        raise hip.SvitHipError("tensor_stats: the ring is uint8 [R * (16 + 32 * %d)] and the workspace uint8, on %s"
-                               % (Tn, dev))
+    tp, Tn = _chk_tensor_ring("tensor_stats", "g and p", (g, p), table_dev, table_host, dev_rec, ring, R, 32, workspace)
     sp, S = (None, 0) if segs is None else _chk_segs(segs)
     hip.call("svit_tensor_stats", ptr(g), ptr(p), g.numel(), ptr(table_dev), tp, Tn, sp, S, ptr(dev_rec), ptr(ring), R,
              every, ptr(workspace), workspace.numel())
-
-
-def _chk_step_dev(what, dev_rec, dev):
-    if dev_rec.dtype != torch.int32 or dev_rec.numel() != 12 or dev_rec.device != dev:
-        raise hip.SvitHipError("%s: the step record is int32 [12] on %s" % (what, dev))
 
 
 def update_snapshot(p, shadow, segs, dev_rec, every):
@@ -1139,18 +1147,8 @@ def update_stats(p, shadow, g, m, v, table_dev, table_host, segs, dev_rec, ring,
     """per-tensor statistics of the step p - shadow (and of p, g, m, v) into row (step % R) of `ring` when the step record
     says the step is due (svit_update_stats; two launches).  m, v: the moments or None; the tables as tensor_stats takes
     them; ring: uint8 [R * (16 + 64 * Tn)] and workspace: uint8, both on the device"""
-    _chk_dev(p, shadow, g, m, v, table_dev, dev_rec, ring, workspace)
-    dev = p.device
-    tp, Tn = _chk_tensor_table(table_host)
-    if any(t is not None and (t.numel() != p.numel() or t.dtype != F32 or t.device != dev) for t in (p, shadow, g, m, v)):
-        raise hip.SvitHipError("update_stats: p, shadow, g, m and v are fp32 buffers of one size on one device")
-    if table_dev.dtype != torch.int64 or tuple(table_dev.shape) != (Tn, 2) or table_dev.device != dev:
-        raise hip.SvitHipError("update_stats: the device table is int64 [%d, 2] on %s, as the host's" % (Tn, dev))
-    _chk_step_dev("update_stats", dev_rec, dev)
-    if (ring.dtype != torch.uint8 or workspace.dtype != torch.uint8 or ring.device != dev or workspace.device != dev
-            or R < 1 or ring.numel() != R * (16 + 64 * Tn)):
-        raise hip.SvitHipError("update_stats: the ring is uint8 [R * (16 + 64 * %d)] and the workspace uint8, on %s"
-                               % (Tn, dev))
+    tp, Tn = _chk_tensor_ring("update_stats", "p, shadow, g, m and v", (p, shadow, g, m, v), table_dev, table_host, dev_rec,
+                              ring, R, 64, workspace)
     sp, S = (None, 0) if segs is None else _chk_segs(segs)
     hip.call("svit_update_stats", ptr(p), ptr(shadow), ptr(g), ptr(m), ptr(v), p.numel(), ptr(table_dev), tp, Tn, sp, S,
              ptr(dev_rec), ptr(ring), R, every, ptr(workspace), workspace.numel())
@@ -1203,8 +1201,7 @@ def act_stats(sites, slots, n_slots, geom, dev_rec, ring, R, state, workspace):
         raise hip.SvitHipError("act_stats: one slot per site")
     if dev_rec is not None:
         _chk_dev(dev_rec)
-        if dev_rec.dtype != torch.int32 or dev_rec.numel() != 12 or dev_rec.device != dev:
-            raise hip.SvitHipError("act_stats: the step record is int32 [12] on %s" % (dev,))
+        _chk_step_dev("act_stats", dev_rec, dev)
     if state.dtype != torch.int64 or state.numel() != 1 or state.device != dev:
         raise hip.SvitHipError("act_stats: the pass counter is int64 [1] on %s" % (dev,))
     if (ring.dtype != torch.uint8 or workspace.dtype != torch.uint8 or workspace.device != dev or R < 1
@@ -1273,8 +1270,7 @@ def attn_stats(sites, n_slots, ent_slots, groups, K, every, maps_samples, geom, 
     dev = ring.device
     if dev_rec is not None:
         _chk_dev(dev_rec)
-        if dev_rec.dtype != torch.int32 or dev_rec.numel() != 12 or dev_rec.device != dev:
-            raise hip.SvitHipError("attn_stats: the step record is int32 [12] on %s" % (dev,))
+        _chk_step_dev("attn_stats", dev_rec, dev)
     if state.dtype != torch.int64 or state.numel() != 4 or state.device != dev:
         raise hip.SvitHipError("attn_stats: the counters are int64 [4] on %s" % (dev,))
     if (ring.dtype != torch.uint8 or workspace.dtype != torch.uint8 or workspace.device != dev or R < 1

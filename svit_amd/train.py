@@ -166,30 +166,29 @@ def _train_epoch_fed(train_loader, step, optimizer, train_meter, cur_epoch, cfg,
     return stats
 
 
-def _log_tensor_stats(optimizer, cfg, cur_iter):
-    """once per cfg.LOG_PERIOD, with a monitor.TensorMonitor attached to the optimizer: ONE read of its ring and one JSON
-    line {"_type": "train_tensor_stats", ...} -- norms per layer of the period's last recorded step, the culprits of its
-    dropped steps.  Nothing without a monitor."""
-    mon = getattr(optimizer, "monitor", None)
+def _log_monitor_stats(mon, cfg, cur_iter):
+    """what the four functions below do with their monitor, or None: at the end of a cfg.LOG_PERIOD ONE read of its ring
+    and, when that holds a row, one JSON line -> the line's dict or None"""
     if mon is None or (cur_iter + 1) % cfg.LOG_PERIOD != 0:
         return None
     stats = mon.log_stats(mon.read())
     if stats is not None:
         log_json_stats(stats)
     return stats
+
+
+def _log_tensor_stats(optimizer, cfg, cur_iter):
+    """once per cfg.LOG_PERIOD, with a monitor.TensorMonitor attached to the optimizer: ONE read of its ring and one JSON
+    line {"_type": "train_tensor_stats", ...} -- norms per layer of the period's last recorded step, the culprits of its
+    dropped steps.  Nothing without a monitor."""
+    return _log_monitor_stats(getattr(optimizer, "monitor", None), cfg, cur_iter)
 
 
 def _log_update_stats(optimizer, cfg, cur_iter):
     """once per cfg.LOG_PERIOD, with an updmon.UpdateMonitor attached to the optimizer: ONE read of its ring and one JSON
     line {"_type": "train_update_stats", ...} -- the step's and the weights' norm per layer of the period's last recorded
     step, the tensors most of whose elements did not move.  Nothing without a monitor."""
-    mon = getattr(optimizer, "update_monitor", None)
-    if mon is None or (cur_iter + 1) % cfg.LOG_PERIOD != 0:
-        return None
-    stats = mon.log_stats(mon.read())
-    if stats is not None:
-        log_json_stats(stats)
-    return stats
+    return _log_monitor_stats(getattr(optimizer, "update_monitor", None), cfg, cur_iter)
 
 
 def _log_activation_stats(step_or_model, cfg, cur_iter):
@@ -198,13 +197,7 @@ def _log_activation_stats(step_or_model, cfg, cur_iter):
     token's std and the largest attention log-sum-exp per block of the period's last pass, the origin of every pass with
     non-finite activations.  Nothing without a monitor."""
     core = getattr(step_or_model, "core", None) or getattr(step_or_model, "module", step_or_model)
-    mon = getattr(getattr(core, "engine", None), "act_monitor", None)
-    if mon is None or (cur_iter + 1) % cfg.LOG_PERIOD != 0:
-        return None
-    stats = mon.log_stats(mon.read())
-    if stats is not None:
-        log_json_stats(stats)
-    return stats
+    return _log_monitor_stats(getattr(getattr(core, "engine", None), "act_monitor", None), cfg, cur_iter)
 
 
 def _log_attention_stats(step_or_model, cfg, cur_iter):
@@ -213,13 +206,7 @@ def _log_attention_stats(step_or_model, cfg, cur_iter):
     normalised entropy and the object-key mass of the period's last recorded pass, the head closest to collapse.
     Nothing without a monitor."""
     core = getattr(step_or_model, "core", None) or getattr(step_or_model, "module", step_or_model)
-    mon = getattr(getattr(core, "engine", None), "attn_monitor", None)
-    if mon is None or (cur_iter + 1) % cfg.LOG_PERIOD != 0:
-        return None
-    stats = mon.log_stats(mon.read())
-    if stats is not None:
-        log_json_stats(stats)
-    return stats
+    return _log_monitor_stats(getattr(getattr(core, "engine", None), "attn_monitor", None), cfg, cur_iter)
 
 
 def train_epoch(train_loader, step_or_model, optimizer, train_meter, cur_epoch, cfg, feeder=None):

@@ -23,8 +23,8 @@ nothing in checkpoints.  The shadow buffer costs 4 bytes per parameter.
 import numpy as np
 import torch
 
-from . import lrscale, ops
-from .monitor import trainable_mask
+from . import ops
+from .monitor import TensorRing, trainable_mask
 
 HEADER = np.dtype([("step", "<i8"), ("flags", "<i4"), ("reserved", "<i4")])
 ENTRY = np.dtype([("sumsq_d", "<f8"), ("sumsq_p", "<f8"), ("dot_dg", "<f8"), ("sumsq_g", "<f8"), ("sumsq_m", "<f8"),
@@ -98,7 +98,7 @@ def abs_terms_host(p_old, p_new, g, m, v, table, segs=None):
     return out
 
 
-class UpdateMonitor:
+class UpdateMonitor(TensorRing):
     """The shadow buffer and the statistics ring around `optimizer`'s solver launch.
 
     optimizer: an optim.GuardedClipAdamW or one of its subclasses (AdamW plain, over segments or with learning-rate
@@ -106,53 +106,20 @@ class UpdateMonitor:
     `read()`s.  every: a step is recorded when the guard applied it and its index (applied + dropped steps so far, from
     0) is a multiple of it.
 
-    One tensor per parameter, in the order of the flat buffer: `names`, `shapes`, `numel`, `table` int64 [Tn, 2].  Under a
-    frozen cut the optimizer's trainable segments decide which tensors are watched; the others come back masked.  The
-    moments are the optimizer's STATE buffers: (exp_avg, exp_avg_sq), (momentum_buffer,) or none.  Nothing is attached by
-    the constructor: `optimizer.attach_update_monitor(monitor)` (or `build_update_monitor`) does that."""
+    The moments are the optimizer's STATE buffers: (exp_avg, exp_avg_sq), (momentum_buffer,) or none.  Nothing is
+    attached by the constructor: `optimizer.attach_update_monitor(monitor)` (or `build_update_monitor`) does that."""
+    KEY = "UPDATE_MONITOR"
+    row_dtype, empty_ring = staticmethod(row_dtype), staticmethod(empty_ring)
+    workspace_bytes = staticmethod(ops.update_stats_workspace)
 
     def __init__(self, optimizer, period, every=1):
-        from .optim import GuardedClipAdamW
-        if not isinstance(optimizer, GuardedClipAdamW):
-            raise TypeError("UpdateMonitor needs an optim.GuardedClipAdamW or one of its subclasses, got %s: only the "
-                            "guarded tail keeps the step's decision and its step counters in device memory (set "
-                            "SVIT.GUARDED_STEP or SVIT.UPDATE_MONITOR before construct_optimizer)"
-                            % type(optimizer).__name__)
-        for what, val in (("period", period), ("every", every)):
-            if isinstance(val, bool) or not isinstance(val, int) or val < 1:
-                raise ValueError("UpdateMonitor: %s is a positive int, got %r" % (what, val))
-        self.optimizer, self.flat = optimizer, optimizer.flat
-        self.period, self.every = period, every
-        flat = self.flat
-        self.names = sorted(flat.slots, key=lambda k: flat.slots[k][0])
-        self.shapes = [tuple(flat.slots[k][2]) for k in self.names]
-        self.table = np.ascontiguousarray(
-            np.array([[flat.slots[k][0], flat.slots[k][0] + flat.slots[k][1]] for k in self.names], dtype=np.int64))
-        ops.tensor_table_check(self.table, flat.total)
-        self.numel = self.table[:, 1] - self.table[:, 0]
-        self.segments = optimizer.segments              # None: nothing is frozen
-        self.frozen = ~trainable_mask(self.table, self.segments)
-        self.depth = flat.n_ranks - 2
-        self.layer_ids = np.array([lrscale.layer_id(k, self.depth) for k in self.names], dtype=np.int64)
-        dev = flat.data.device
-        Tn = len(self.names)
-        self.table_dev = torch.from_numpy(self.table).to(dev)
-        self.workspace = torch.zeros(ops.update_stats_workspace(flat.total, Tn), dtype=torch.uint8, device=dev)
-        self.ring = torch.from_numpy(empty_ring(period, Tn).view(np.uint8).reshape(-1).copy()).to(dev)
-        self.shadow = torch.zeros(flat.total, dtype=torch.float32, device=dev)
-        self.last_read = self._step_now()
-        if dev.type == "cuda":
-            self._warm()
+        super().__init__(optimizer, period, every)
+        self.shadow = torch.zeros(self.flat.total, dtype=torch.float32, device=self.flat.data.device)
 
     def _moments(self):
         """(m, v): the optimizer's first and second state buffer, None where it keeps none"""
         state = [getattr(self.optimizer, key) for key in self.optimizer.STATE]
         return (state + [None, None])[:2]
-
-    def _step_now(self):
-        """index of the optimizer's last step (-1 before the first); synchronises"""
-        s = self.optimizer.stats()
-        return s["applied"] + s["skipped"] - 1
 
     def _warm(self):
         """one call of each entry point on four dummy elements, so that a later stream capture meets loaded code; neither
@@ -177,24 +144,18 @@ class UpdateMonitor:
         ops.update_stats(self.flat.data, self.shadow, self.flat.grad, m, v, self.table_dev, self.table, self.segments,
                          self.optimizer.dev_rec, self.ring, self.period, self.every, self.workspace)
 
-    def reset(self):
-        """forget every row: the ring as it was created, the next `read()` starts behind the optimizer's last step"""
-        self.ring.copy_(torch.from_numpy(empty_ring(self.period, len(self.names)).view(np.uint8).reshape(-1).copy()))
-        self.last_read = self._step_now()
-
-    # ---- reading -----------------------------------------------------------------------------------------------------
-    def _rows(self, since):
-        """the ring's written rows of the steps after `since`, ordered by step (ONE device read)"""
-        ring = self.ring.cpu().numpy().view(row_dtype(len(self.names)))
-        rows = ring[ring["head"]["step"] > since]
-        return rows[np.argsort(rows["head"]["step"], kind="stable")]
+    def read(self):
+        """the rows recorded since the last read, ordered by step, as a dict of arrays [rows, Tn] (frozen tensors masked):
+        names, steps, flags, numel, update_norm = sqrt(sumsq_d), weight_norm = sqrt(sumsq_p), ratio = update_norm /
+        weight_norm, cos_grad = -dot_dg / (update_norm * |g|) (1 for plain gradient descent), m_rms = sqrt(sumsq_m /
+        numel), v_mean = sum_v / numel (both 0 without the moment: see flags), absmax, n_still, n_one_ulp, the six raw sums,
+        and `lost`: how many multiples of `every` since the last read, up to the newest step the ring holds, have no row
+        -- overwritten (R rows; an overrun is reported, not raised) or dropped by the guard, which a TensorMonitor's rows
+        tell apart"""
+        return super().read()
 
     def _dict(self, rows, lost):
-        mask = np.broadcast_to(self.frozen, rows["entry"].shape)
-        e = rows["entry"]
-
-        def masked(a):
-            return np.ma.MaskedArray(a, mask=mask.copy())
+        e, masked = rows["entry"], self._masked
         numel = self.numel.astype(np.float64)
         un, wn, gn = np.sqrt(e["sumsq_d"]), np.sqrt(e["sumsq_p"]), np.sqrt(e["sumsq_g"])
         with np.errstate(divide="ignore", invalid="ignore"):
@@ -208,41 +169,13 @@ class UpdateMonitor:
             out[key] = masked(e[key].copy())
         return out
 
-    def read(self):
-        """the rows recorded since the last read, ordered by step, as a dict of arrays [rows, Tn] (frozen tensors masked):
-        names, steps, flags, numel, update_norm = sqrt(sumsq_d), weight_norm = sqrt(sumsq_p), ratio = update_norm /
-        weight_norm, cos_grad = -dot_dg / (update_norm * |g|) (1 for plain gradient descent), m_rms = sqrt(sumsq_m /
-        numel), v_mean = sum_v / numel (both 0 without the moment: see flags), absmax, n_still, n_one_ulp, the six raw sums,
-        and `lost`: how many multiples of `every` since the last read, up to the newest step the ring holds, have no row
-        -- overwritten (R rows; an overrun is reported, not raised) or dropped by the guard, which a TensorMonitor's rows
-        tell apart."""
-        rows = self._rows(self.last_read)
-        lost = 0
-        if len(rows):
-            now = int(rows["head"]["step"][-1])
-            due = now // self.every - self.last_read // self.every          # multiples of `every` in (last_read, now]
-            lost = due - len(rows)
-            self.last_read = now
-        return self._dict(rows, lost)
-
     def by_layer(self, rows):
         """rows (what `read()` gave) summed over lrscale's layer ids: depth + 2 groups -- 0 the stem, 1 + i block i,
         depth + 1 the rest -- of update_norm, weight_norm and ratio = update_norm / weight_norm, n_still and numel, each
         [rows, depth + 2]; a group whose tensors are all frozen is masked"""
-        G = self.depth + 2
-        r = len(rows["steps"])
-        sd, sp = np.zeros((r, G)), np.zeros((r, G))
-        still, numel = np.zeros((r, G), dtype=np.int64), np.zeros((r, G), dtype=np.int64)
-        seen = np.zeros(G, dtype=bool)
-        for t, lid in enumerate(self.layer_ids):
-            if self.frozen[t]:
-                continue
-            seen[lid] = True
-            sd[:, lid] += rows["sumsq_d"].data[:, t]
-            sp[:, lid] += rows["sumsq_p"].data[:, t]
-            still[:, lid] += rows["n_still"].data[:, t]
-            numel[:, lid] += self.numel[t]
-        mask = np.broadcast_to(~seen, (r, G)).copy()
+        still = rows["n_still"].data
+        (sd, sp, still, numel), mask = self._layer_sums(rows["sumsq_d"].data, rows["sumsq_p"].data, still,
+                                                        np.broadcast_to(self.numel, still.shape))
         un, wn = np.sqrt(sd), np.sqrt(sp)
         with np.errstate(divide="ignore", invalid="ignore"):
             ratio = un / wn
@@ -266,10 +199,7 @@ class UpdateMonitor:
         is no row"""
         if not len(rows["steps"]):
             return None
-        layers = self.by_layer(rows)
-
-        def last(a):
-            return [None if x is np.ma.masked or not np.isfinite(x) else float("%.6g" % x) for x in a[-1]]
+        layers, last = self.by_layer(rows), self._last
         step = int(rows["steps"][-1])
         stalled = [s for s in self.stalled(rows) if s[0] == step]
         live = ~self.frozen
