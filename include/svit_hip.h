@@ -189,6 +189,35 @@ int svit_im2col_patch(const float* video, void* cols, int B, int T, int H, int W
  * aligned, SVIT_ERR_ALIGN; B*To*Ho*Wo >= 2^31 (or T*H >= 2^31) SVIT_ERR_SHAPE.  Element offsets are 64-bit. */
 int svit_patch_embed_dgrad(const void* dtok /* bf16 [B*To*Ho*Wo, 96] */, const void* w16 /* bf16 [96, 448] */,
                            float* dvideo /* f32 [B,3,T,H,W] */, int B, int T, int H, int W, void* stream);
+/* ------------------------------------------------------------ attribution passes (csrc/attrib.hip) - */
+/* SmoothGrad / integrated gradients (svit_amd/attribution.py) run one input-gradient pass per sample point; these two
+ * streaming kernels stand in front of and behind the pass.  Both read ONE 32-byte record from DEVICE memory at run time,
+ * so a captured pass body holds the same launches for every pass:
+ *   alpha   the point on the path base -> x (1 = the clip itself)      weight  what this pass's gradient is scaled by
+ *   seed    31-bit seed of this pass's noise field                     pass    0-based pass number; 0 STORES the sum
+ *   flags   bit 0: accumulate g*g instead of g                         pad     0
+ * Every fp32 operation named below is rounded once, on its own (helpers that keep the compiler from fusing them).
+ * svit_attr_perturb: x, out f32 [B,3,T,H,W] (out may not alias x or base); base the same shape or NULL (zeros); sigma f32
+ * [B] or NULL.  Per element  d = x - base;  p = base + alpha*d;  out = p + sigma[b]*n  -- the sigma term is SKIPPED for a
+ * NULL sigma (not multiplied by 0), and n = N(0,1) is the erasing noise of svit_u8_clips_render's pixel mode: Philox keyed
+ * by `seed`, counter (y*W + x, clip b, plane c*T + t), Box-Muller; |n| <= 5.77, a pure function of (seed, b, c, t, y, x).
+ * svit_attr_accumulate: g, acc f32 [n].  v = (flags & 1) ? g*g : g;  t = weight*v;  acc = (pass == 0) ? t : acc + t -- the
+ * first pass never reads acc, so nothing has to be zeroed.  With `scores` f32 [rows, B] the B values of `scores_in` f32
+ * [B] (this pass's per-sample scores) are copied bit for bit into row `pass`; a pass >= rows writes no score.
+ * Both: grid-stride over 16-byte vectors from the output's first 16-byte boundary, single elements in front and behind (any
+ * n, any 4-byte aligned pointers; inputs misaligned differently from the output are walked element by element), 64-bit
+ * offsets, no atomics, every output element stored exactly once, nothing outside the outputs touched.  Checked before any
+ * HIP call: a null x / rec / out (g / acc / rec), a size < 1, or scores without scores_in or with rows < 1 is
+ * SVIT_ERR_ARG; a pointer not 4-byte aligned SVIT_ERR_ALIGN; H*W or B*3*T of 2^31 or more SVIT_ERR_SHAPE. */
+typedef struct {
+  float alpha, weight;
+  uint32_t seed, pass, flags, pad[3];
+} svit_attr_pass;
+int svit_attr_perturb(const float* x, const float* base /* or NULL */, const float* sigma /* f32 [B] or NULL */,
+                      const void* rec /* svit_attr_pass, device */, float* out, int B, int T, int H, int W, void* stream);
+int svit_attr_accumulate(const float* g, float* acc, const void* rec /* svit_attr_pass, device */,
+                         const float* scores_in /* f32 [B] or NULL */, float* scores /* f32 [rows, B] or NULL */, int rows,
+                         int64_t n, int B, void* stream);
 /* The same operand straight from decoded uint8 frames: frames u8
  * [V,T,Hs,Ws,3] (T H W C per video, `frames_bytes` = size of the buffer), lut bf16 [3,256] =
  * bf16((u/255 - mean[c]) / std[c]) (datasets/utils.py:287-303), crops int32 [B,3] = (source video,

@@ -18,7 +18,7 @@ OUT_DIR = os.path.join(HERE, "lib")
 LIB = os.path.join(OUT_DIR, "libsvit_hip.so")
 SOURCES = ["gemm_nt.hip", "gemm_tn.hip", "norm.hip", "misc.hip", "pool.hip", "attn_fwd.hip", "attn_bwd.hip",
            "loss.hip", "meter.hip", "input.hip", "head.hip", "randaug.hip", "feed.hip", "head_eval.hip", "solver.hip",
-           "monitor.hip", "actmon.hip", "update.hip", "attnmon.hip", "dgrad.hip"]
+           "monitor.hip", "actmon.hip", "update.hip", "attnmon.hip", "dgrad.hip", "attrib.hip"]
 HEADERS = ["common.h", "attn_common.h", "gemm_epilogue.h", "seg_table.h", "tensor_walk.h",
            os.path.join("..", "..", "include", "svit_hip.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -36,7 +36,8 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-ffast-math",
 # per-source changes to FLAGS.  randaug.hip must give PIL's bytes: its fp32 / fp64 products and sums are rounded one by
 # one, and under -ffast-math the backend fuses them whatever the source says (csrc/input.hip, mix_blend).
 # (solver.hip, whose bar is a NumPy fp32 restatement, takes the common flags: its arithmetic goes through helpers that
-# round each operation once whatever the flags say -- randaug.hip stays the one source built differently.)
+# round each operation once whatever the flags say -- randaug.hip stays the one source built differently; attrib.hip,
+# whose bar is a torch-CPU fp32 restatement, goes the way of solver.hip.)
 SOURCE_FLAGS = {"randaug.hip": {"remove": ["-ffast-math"], "add": ["-ffp-contract=off"]}}
 TMP_DIR = os.path.join(OUT_DIR, "tmp")
 

@@ -174,6 +174,16 @@ __device__ __forceinline__ void philox4(uint64_t seed, uint64_t draw, uint32_t i
   for (int i = 0; i < 4; ++i) u[i] = (float)(c[i] >> 8) * (1.0f / 16777216.0f);      // [0, 1) on a 2^-24 grid
 }
 
+// N(0,1) of the erasing noise: Philox keyed by the record's seed, counter = (idx, clip b, plane c*T + t), Box-Muller on
+// the first two uniforms; v_log / v_sqrt / v_cos (input in revolutions) directly, so every caller gets the same bits.
+// 1 - u is in [2^-24, 1]: |z| <= 5.77.
+__device__ __forceinline__ float aug_noise(uint32_t seed, int b, int plane, uint32_t idx) {
+  float u[4];
+  philox4((uint64_t)seed, ((uint64_t)(uint32_t)b << 32) | (uint32_t)plane, idx, u);
+  const float r = __builtin_amdgcn_sqrtf(-1.3862943611198906f * __builtin_amdgcn_logf(1.f - u[0]));   // sqrt(-2 ln(1 - u0))
+  return r * __builtin_amdgcn_cosf(u[1]);
+}
+
 // Second stage of the two-stage parameter-gradient reductions: every block of the producing
 // kernel stores its partial sums as one row of `partial` [nblocks][n] with plain stores, then
 // this kernel adds the column sums into up to six destination vectors (segments of n).

@@ -340,15 +340,7 @@ __device__ __forceinline__ void aug_axis(int dst, int in, float scale, int& i0, 
   __asm__("" : "+v"(l1));
 }
 
-// N(0,1) of the erasing noise: Philox keyed by the record's seed, counter = (idx, clip b, plane c*T + t), Box-Muller on
-// the first two uniforms; v_log / v_sqrt / v_cos (input in revolutions) directly, so every caller gets the same bits.
-// 1 - u is in [2^-24, 1]: |z| <= 5.77.
-__device__ __forceinline__ float aug_noise(uint32_t seed, int b, int plane, uint32_t idx) {
-  float u[4];
-  philox4((uint64_t)seed, ((uint64_t)(uint32_t)b << 32) | (uint32_t)plane, idx, u);
-  const float r = __builtin_amdgcn_sqrtf(-1.3862943611198906f * __builtin_amdgcn_logf(1.f - u[0]));   // sqrt(-2 ln(1 - u0))
-  return r * __builtin_amdgcn_cosf(u[1]);
-}
+// (aug_noise, the N(0,1) of the erasing noise, lives in common.h: csrc/attrib.hip draws the same field)
 
 // taps straight from global memory: pixel (r, col) of the record's rectangle in frame t -> its three bytes
 struct AugGlobalFetch {

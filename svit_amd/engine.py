@@ -251,12 +251,27 @@ class Engine:
         self.act_monitor = None
         # the attnmon.AttentionMonitor `model.attach_attention_monitor` hung behind it: two launches more
         self.attn_monitor = None
+        # an input-gradient-only backward (forward(..., input_grad="only")): the fused kernels that produce a data gradient
+        # and a parameter-gradient partial in one launch run unchanged, and their parameter side lands in these scratch
+        # tensors (one per parameter name, made at first use) instead of flat.grad
+        self._lean = False
+        self._sinks = {}
 
     # ------------------------------------------------------------------ helpers ----------
     def refresh_weights(self):
         self.flat.refresh_low_precision()
         ops.pad_cast_rows(self.flat.p("patch_embed.proj.weight").view(self.plan.embed_dim, 441),
                           self.patch_w16)
+
+    def _g(self, name):
+        """where the running backward accumulates the gradient of parameter `name`: its view of flat.grad, or -- in an
+        input-gradient-only pass -- a scratch tensor of its shape that nobody reads"""
+        if not self._lean:
+            return self.flat.g(name)
+        t = self._sinks.get(name)
+        if t is None:
+            t = self._sinks[name] = torch.zeros(self.flat.slots[name][2], device=self.dev, dtype=F32)
+        return t
 
     def _rel(self, blk, q_thw, k_thw):
         """index tables (+ resize matrices when needed) for a block at this resolution."""
@@ -350,7 +365,15 @@ class Engine:
         cut 0.  What a pass computes does not depend on what it keeps.
         input_grad: the backward of this pass also leaves d loss / d clip in st["dvideo"], f32 [B,3,Tx,S,S] in the
         coordinates of the S x S window the stem read (one launch more, svit_patch_embed_dgrad; needs save and cut 0).
+        "only" (svit_amd/attribution.py): the same, and the backward computes NO parameter gradient -- it queues no
+        weight-gradient GEMM, runs no rel-pos table GEMM, no special-token gradients and no stem weight gradient, calls
+        no gradient-ready hook and leaves every bit of flat.grad as it was (the parameter halves of the fused
+        LayerNorm / pooling kernels land in scratch); the attached monitors are not pushed.  The pass ignores frozen
+        parameters: the caller passes cut 0.
         False: the same launches as ever."""
+        only = isinstance(input_grad, str)
+        if only and input_grad != "only":
+            raise ValueError("input_grad is False, True or \"only\", got %r" % (input_grad,))
         if input_grad:
             if cut > 0:
                 raise ValueError("input_grad=True under a frozen cut (cut %d): the backward stops above the frozen "
@@ -386,7 +409,7 @@ class Engine:
         st = {"B": B, "Tx": Tx, "n_obj": n_obj, "L0": L, "cols": cols if save and cut == 0 else None,
               "blocks": [], "cut": cut}
         if input_grad:
-            st["input_grad"] = True
+            st["input_grad"] = "only" if only else True
             st["video_hw"] = tuple(video.shape[3:5])
         thw = (T, Ho, Wo)
         self._interp_tables(thw, save)
@@ -406,9 +429,9 @@ class Engine:
         y16, y32, mean, rstd = ops.layernorm_fwd(x, f.p("norm.weight"), f.p("norm.bias"),
                                                  want_f32=True, want_bf16=False, save_stats=save)
         st.update(x_last=x if save else None, mean=mean, rstd=rstd, thw=thw, thw0=(T, Ho, Wo))
-        if save and self.act_monitor is not None:
+        if save and not only and self.act_monitor is not None:
             self.act_monitor.enqueue(st)
-        if save and self.attn_monitor is not None:
+        if save and not only and self.attn_monitor is not None:
             self.attn_monitor.enqueue(st)
         # the batched interpolation results belong to THIS pass: a stand-alone _block_fwd afterwards (tests, tools) interpolates
         # its own tables.  The fp32 / bf16 buffers are cached per (geometry, save) and the saved `tabs` of a pass are views of
@@ -512,7 +535,17 @@ class Engine:
         `rank` (arch.readiness_rank) are final -- the data-parallel wrapper launches the
         all-reduce of that slice there, overlapping it with the remaining backward.
         ready_ranks: the ranks at which on_ready really consumes gradients (None = every rank);
-        side-stream wgrad work is joined only there and at the end."""
+        side-stream wgrad work is joined only there and at the end.
+        A pass saved with input_grad="only" runs the data-gradient chain alone (forward()): on_ready is never called."""
+        if st.get("input_grad") == "only":
+            self._lean = True
+            try:
+                return self._backward(st, dy, None, None)
+            finally:
+                self._lean = False
+        return self._backward(st, dy, on_ready, ready_ranks)
+
+    def _backward(self, st, dy, on_ready, ready_ranks):
         def ready(rank):
             if on_ready is not None:
                 if ready_ranks is None or rank in ready_ranks:
@@ -535,7 +568,7 @@ class Engine:
             return
         last = st["blocks"][depth - 1]
         dx, dx16 = ops.layernorm_bwd(dy.contiguous(), st["x_last"], f.p("norm.weight"), st["mean"],
-                                     st["rstd"], f.g("norm.weight"), f.g("norm.bias"),
+                                     st["rstd"], self._g("norm.weight"), self._g("norm.bias"),
                                      want_bf16=True, row_scale=last["dpm"],
                                      rows_per_sample=st["x_last"].shape[1])
         ready(0)
@@ -573,12 +606,15 @@ class Engine:
             return
         # block-0 input: [cls | patches | objects]
         B, Tx, L, O, C = st["B"], st["Tx"], st["L0"], plan.objects, plan.embed_dim
-        ops.special_token_grads(dx, f.g("cls_token"), f.g("object_queries"),
-                                f.g("pos_embed_temporal") if Tx > 1 else None, L, Tx, O, Tx > 1)
+        if not self._lean:
+            ops.special_token_grads(dx, f.g("cls_token"), f.g("object_queries"),
+                                    f.g("pos_embed_temporal") if Tx > 1 else None, L, Tx, O, Tx > 1)
         dtok = ops.scale_cast(dx, gather=(L, 1))       # patch rows of every clip -> bf16 [B*L, C]
         if st.get("input_grad"):    # d loss / d clip from the same operand, while it is certainly still this pass's
             H, W = st["video_hw"]
             st["dvideo"] = ops.patch_embed_dgrad(dtok, self.patch_w16, B, Tx, H, W)
+        if self._lean:      # (nothing was queued or forked: no flush, no join)
+            return
         self._gemm_tn(dtok, st["cols"], f.g("patch_embed.proj.weight").view(C, 441), f.g("patch_embed.proj.bias"))
         self._flush_tn()
         self._join()
@@ -665,7 +701,8 @@ class Engine:
     def _linear_bwd(self, dy16, x16, wname, bname, need_dx, out=None, accumulate=False,
                     epilogue=hip.EPI_F32, aux=None):
         f = self.flat
-        self._tn.append((dy16, x16, f.g(wname), f.g(bname)))     # flushed per block, grouped
+        if not self._lean:      # (an input-gradient-only pass: the data gradient alone)
+            self._tn.append((dy16, x16, f.g(wname), f.g(bname)))     # flushed per block, grouped
         if not need_dx:
             return None
         return ops.gemm_nt(dy16, f.wt(wname), None, epilogue, out=out, aux=aux, accumulate=accumulate)
@@ -694,7 +731,7 @@ class Engine:
         dxn2 = self._linear_bwd(dh, sv["xn2"].view(Mq, Co), pre + "mlp.fc1.weight",
                                 pre + "mlp.fc1.bias", True, epilogue=hip.EPI_BF16)   # bf16 like autocast
         dx1, dy = ops.layernorm_bwd(dxn2, sv["x1"], f.p(pre + "norm2.weight"), sv["mean2"],
-                                    sv["rstd2"], f.g(pre + "norm2.weight"), f.g(pre + "norm2.bias"),
+                                    sv["rstd2"], self._g(pre + "norm2.weight"), self._g(pre + "norm2.bias"),
                                     dres=dx2, want_bf16=True, row_scale=sv["dpa"], rows_per_sample=Nq,
                                     ws=self._rws("ln2"))
         dy = dy.view(Mq, Co)
@@ -728,6 +765,8 @@ class Engine:
             dq_extra = None
         qa2 = qa.view(B * h * Nq, qa.shape[-1])
         for n, m, t, o in zip(names, mats, tabs, offs):
+            if self._lean:      # (no table gradient; D stays: dq_extra below reads it)
+                break
             rows = t.shape[0]
             if m is None:
                 self._tn.append((D[:, o:o + rows], qa2[:, :HD], f.g(n), None))
@@ -750,15 +789,15 @@ class Engine:
                 ("k", prek, mk, rk, Nk, dict(d_main=dk, ld_main=HD)),
                 ("v", prev, mv, rv, Nk, dict(d_main=dv, ld_main=HD))):
             entries.append(((pre_t, mean, rstd, f.p(pre + "attn.norm_%s.weight" % r),
-                             f.g(pre + "attn.norm_%s.weight" % r),
-                             f.g(pre + "attn.norm_%s.bias" % r), B, h, nout), kw))
+                             self._g(pre + "attn.norm_%s.weight" % r),
+                             self._g(pre + "attn.norm_%s.bias" % r), B, h, nout), kw))
         dpres = ops.pool_ln_bwd_qkv(entries, ws=self._rws("pln"))   # q, k, v: one launch per stage
         strides = (sq, skv, skv)
         # conv dgrad + conv wgrad: one kernel with dpre in LDS for the small planes (blocks >= 4),
         # the two streaming launches otherwise (decided inside the library)
         ops.pool_conv_bwd_qkv(dpres, [f.p(pre + "attn.pool_%s.weight" % r).view(HD, 27) for r in "qkv"],
                               dqkv, sv["qkv"],
-                              [f.g(pre + "attn.pool_%s.weight" % r).view(HD, 27) for r in "qkv"],
+                              [self._g(pre + "attn.pool_%s.weight" % r).view(HD, 27) for r in "qkv"],
                               B, h, thw, n_obj, strides, ws=self._wgrad_ws(B, h, thw, n_obj, strides))
         # (bf16 unless the dim-change projection accumulates into it below)
         dxn = self._linear_bwd(dqkv, sv["xn"], pre + "attn.qkv.weight", pre + "attn.qkv.bias", True,
@@ -773,7 +812,7 @@ class Engine:
                              accumulate=True)
             dskip = None
         res = ops.layernorm_bwd(dxn, x, f.p(pre + "norm1.weight"), sv["mean1"], sv["rstd1"],
-                                f.g(pre + "norm1.weight"), f.g(pre + "norm1.bias"), dres=dskip,
+                                self._g(pre + "norm1.weight"), self._g(pre + "norm1.bias"), dres=dskip,
                                 want_bf16=below is not None,
                                 row_scale=below["dpm"] if below is not None else None,
                                 rows_per_sample=N, ws=self._rws("ln1"))

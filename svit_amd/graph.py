@@ -85,9 +85,26 @@ class GraphedTrainStep:
         input_grad: the captured backward also computes d loss / d clip (one launch behind the stem's cast,
         svit_patch_embed_dgrad) into `step.input_grad`, a static f32 [B,3,T,S,S] every replay refills -- for an fp32
         clip, a U8Clips or an AugClips (in the coordinates of the S x S window; under `mixup`, with respect to the mixed
-        clip).  Refused under a frozen cut.  False: the same segments and launches as ever."""
+        clip).  Refused under a frozen cut.  False: the same segments and launches as ever.
+        input_grad="only" (svit_amd/attribution.py): the step is an ATTRIBUTION pass, not a training step -- its captured
+        body is forward, `loss_fun`, and the backward that computes the input gradient and NO parameter gradient
+        (Engine.forward): ONE graph, no gradient memset and no bf16 weight refresh inside (the constructor refreshes once,
+        `refresh()` after the weights moved, as GraphedEvalStep has it), no draw launch -- DropPath and the head's
+        dropout are off whatever the cfg's rates.  A replay leaves flat.grad, every param.grad, weights, moments, meters,
+        monitors and the draw counter as they are, and does not read the requires_grad flags: it works under a frozen
+        cut.  `optimizer=`, `accumulate=True`, `frames_pass`, `meter=` and `mixup=` are refused."""
         self.accumulate = bool(accumulate)
         self.want_input_grad = bool(input_grad)
+        self.only = isinstance(input_grad, str)
+        if self.only:
+            if input_grad != "only":
+                raise hip.SvitHipError("input_grad is False, True or \"only\", got %r" % (input_grad,))
+            for name, given in (("optimizer=", optimizer is not None), ("accumulate=True", accumulate),
+                                ("frames_pass", frames_pass), ("meter=", meter is not None), ("mixup=", mixup is not None)):
+                if given:
+                    raise hip.SvitHipError("GraphedTrainStep(input_grad=\"only\") refuses %s: the step computes the "
+                                           "input gradient of one clip forward and nothing else -- no parameter "
+                                           "gradient exists for an optimizer, an accumulation or a meter to use" % name)
         self.input_grad = None
         if self.accumulate and (optimizer is not None or meter is not None):
             raise hip.SvitHipError("GraphedTrainStep(accumulate=True) is a micro-step: the optimizer tail and the meter "
@@ -117,10 +134,11 @@ class GraphedTrainStep:
             raise RuntimeError("GraphedTrainStep captures the training step: call model.train() first")
         # frozen parameters (svit_amd/freeze.py): the flags are read HERE; the capture saves, back-propagates, exchanges and
         # steps for this cut only, so `__call__` refuses a replay once a flag has changed
-        self.cut = self.core.frozen_cut()
+        # (an input-gradient-only pass saves and back-propagates through every block whatever the flags say: not read)
+        self.cut = 0 if self.only else self.core.frozen_cut()
         self._flag_params = list(self.core.parameters())
         self._flags = [p.requires_grad for p in self._flag_params]
-        if self.want_input_grad:
+        if self.want_input_grad and not self.only:
             _check_input_grad(self.cut)
         if optimizer is not None and optimizer.cut != self.cut:
             raise hip.SvitHipError("GraphedTrainStep(optimizer=...): the optimizer was built when the parameters' "
@@ -189,7 +207,37 @@ class GraphedTrainStep:
         self.loss_dict = {k: v.detach() for k, v in logged.items() if torch.is_tensor(v)}
         return loss
 
+    def refresh(self):
+        """input_grad="only": the bf16 copies of the weights, eagerly on the current stream -- call it after the weights
+        moved (the captured body holds no refresh)"""
+        with torch.no_grad():
+            self.core.engine.refresh_weights()
+
+    def _body_only(self):
+        """the body of an input_grad="only" step: forward, loss_fun, the backward without parameter gradients"""
+        core = self.core
+        eng, x = core.engine, self.x
+        Tx = x.shape[2] if x.dim() == 5 else 1
+        with torch.no_grad():
+            y, st = eng.forward(x, None, save=True, cut=0, input_grad="only")
+        yt = y.detach().requires_grad_(True)
+        with torch.enable_grad():
+            if core.fused_head:
+                preds, extra = core.head_train(yt, Tx, lean=True)
+            else:
+                from .model import _lean_head
+                n_obj = Tx * core.O
+                preds, extra = _lean_head(core.head, torch.cat((yt[:, :1], yt[:, -n_obj:]), dim=1), Tx, None)
+            loss = self._loss(preds, extra, self.labels, False)
+        dy, = torch.autograd.grad(loss, [yt])
+        with torch.no_grad():
+            eng.backward(st, dy)
+        return (loss.detach(), preds.detach(),
+                {k: v.detach() for k, v in extra.items() if torch.is_tensor(v)}, (st, yt, dy))
+
     def _body(self, boundary, tail=False):
+        if self.only:
+            return self._body_only()
         core = self.core
         eng, flat = core.engine, core.flat
         x = self.x
@@ -270,9 +318,10 @@ class GraphedTrainStep:
     def _capture(self, warmup):
         core = self.core
         eng = core.engine
-        core._attach_grads()                      # .grad views of the flat buffer, host side only
-        if self.accumulate:                       # (what the owner's prologue does in front of every step)
-            eng.refresh_weights()
+        if not self.only:
+            core._attach_grads()                  # .grad views of the flat buffer, host side only
+        if self.accumulate or self.only:          # (what the owner's prologue does in front of every step)
+            self.refresh()
         dev = self.x.device
         cap = torch.cuda.Stream(device=dev)
         cap.wait_stream(torch.cuda.current_stream(dev))
@@ -334,6 +383,8 @@ class GraphedTrainStep:
     # ------------------------------------------------------------------------------------------
     def check_flags(self):
         """refuse a replay after a `requires_grad` flag has changed: the capture holds the old cut's launches"""
+        if self.only:       # (reads no flag and pushes no monitor)
+            return
         if [p.requires_grad for p in self._flag_params] != self._flags:
             raise hip.SvitHipError("a parameter's requires_grad changed after this GraphedTrainStep was captured (it "
                                    "froze everything below position %d): rebuild the optimizer and the step" % self.cut)

@@ -148,6 +148,12 @@ class AttnProbe(C.Structure):
                 ("reserved", i32)]
 
 
+class AttrPass(C.Structure):
+    """svit_attr_pass: the 32-byte record of one attribution pass (flags bit 0: squared)"""
+    _fields_ = [("alpha", f32), ("weight", f32), ("seed", C.c_uint32), ("npass", C.c_uint32), ("flags", C.c_uint32),
+                ("pad", C.c_uint32 * 3)]
+
+
 class StepHost(C.Structure):
     """svit_step_host: the part of the guarded optimiser's step record the host uploads before every step"""
     _fields_ = [("lr", f32 * 2), ("weight_decay", f32 * 2), ("max_norm", f32), ("clip_value", f32),
@@ -186,6 +192,8 @@ _SIGS = {
                                  i64, vp]),
     "svit_im2col_patch": (i32, [vp, vp, i32, i32, i32, i32, vp]),
     "svit_patch_embed_dgrad": (i32, [vp, vp, vp, i32, i32, i32, i32, vp]),
+    "svit_attr_perturb": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
+    "svit_attr_accumulate": (i32, [vp, vp, vp, vp, vp, i32, i64, i32, vp]),
     "svit_im2col_patch_u8": (i32, [vp, i64, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     "svit_im2col_patch_u8_mix": (i32, [vp, i64, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     "svit_im2col_patch_u8_aug": (i32, [vp, i64, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),

@@ -62,9 +62,11 @@ class _Backbone(torch.autograd.Function):
     @staticmethod
     def forward(ctx, model, video, drop_scales, need_grad, anchor, cut, input_grad):
         wanted = bool(need_grad and cut == 0 and ctx.needs_input_grad[1] and video.dtype == torch.float32)
+        lean = input_grad == "only"     # the input gradient and no parameter gradient (Engine.forward)
         with torch.no_grad():
-            y, st = model.engine.forward(video, drop_scales, save=need_grad, cut=cut, input_grad=wanted or input_grad)
-        ctx.model, ctx.st, ctx.cut = model, (st if need_grad else None), cut
+            y, st = model.engine.forward(video, drop_scales, save=need_grad, cut=cut,
+                                         input_grad="only" if lean else (wanted or input_grad))
+        ctx.model, ctx.st, ctx.cut, ctx.lean = model, (st if need_grad else None), cut, lean
         ctx.video_shape, ctx.keep_input_grad = (video.shape if wanted else None), bool(input_grad)
         return y
 
@@ -73,10 +75,14 @@ class _Backbone(torch.autograd.Function):
         model = ctx.model
         if ctx.st is None:
             raise RuntimeError("backward through an SViT forward that was run without grad")
-        model._attach_grads(ctx.cut)
-        with torch.no_grad():
-            model.engine.backward(ctx.st, dy, on_ready=model._grad_ready_hook,
-                                  ready_ranks=model._grad_ready_ranks)
+        if ctx.lean:        # no parameter gradient: flat.grad, every param.grad and the data-parallel exchange stay as they are
+            with torch.no_grad():
+                model.engine.backward(ctx.st, dy)
+        else:
+            model._attach_grads(ctx.cut)
+            with torch.no_grad():
+                model.engine.backward(ctx.st, dy, on_ready=model._grad_ready_hook,
+                                      ready_ranks=model._grad_ready_ranks)
         dvideo = ctx.st.get("dvideo")
         ctx.st = None
         if ctx.keep_input_grad:
@@ -115,12 +121,12 @@ class _HeadFn(torch.autograd.Function):
     buffer's views (like the backbone's node does) and returns d(tokens) whole."""
 
     @staticmethod
-    def forward(ctx, model, tokens, T, O, keep):
+    def forward(ctx, model, tokens, T, O, keep, lean):
         head = model.head
         tokens = tokens.contiguous()
         with torch.no_grad():
             outs = ops.head_fwd(tokens, T, O, keep, [(w.data, b.data) for w, b in head.param_pairs()])
-        ctx.model, ctx.T, ctx.O = model, T, O
+        ctx.model, ctx.T, ctx.O, ctx.lean = model, T, O, lean
         ctx.save_for_backward(tokens, keep, outs[1])
         ctx.set_materialize_grads(False)
         return outs
@@ -129,13 +135,22 @@ class _HeadFn(torch.autograd.Function):
     def backward(ctx, dlogits, dboxes, dcontact, dxobj):
         tokens, keep, boxes = ctx.saved_tensors
         model = ctx.model
-        model._attach_grads()      # (zeroes the flat buffer first if zero_grad() dropped the views)
         pairs = model.head.param_pairs()
+        if ctx.lean:       # an input-gradient-only pass: the same launch, its eight parameter gradients into scratch
+            sink = model.engine._sinks
+            grads = []
+            for i, (w, b) in enumerate(pairs):
+                for j, p in enumerate((w, b)):
+                    if ("head", i, j) not in sink:
+                        sink["head", i, j] = torch.zeros_like(p.data)
+                grads.append((sink["head", i, 0], sink["head", i, 1]))
+        else:
+            model._attach_grads()      # (zeroes the flat buffer first if zero_grad() dropped the views)
+            grads = [(w.grad, b.grad) for w, b in pairs]
         with torch.no_grad():
             dtok = ops.head_bwd(tokens, ctx.T, ctx.O, keep, [(w.data, b.data) for w, b in pairs], boxes,
-                                (dlogits, dboxes, dcontact, dxobj), [(w.grad, b.grad) for w, b in pairs],
-                                ordered=model.engine.reproducible)
-        return None, dtok, None, None, None
+                                (dlogits, dboxes, dcontact, dxobj), grads, ordered=model.engine.reproducible)
+        return None, dtok, None, None, None, None
 
 
 class SViTHead(nn.Module):
@@ -426,14 +441,17 @@ class SViT(nn.Module):
                 self._head_keep = drop.view(shp)
         return [(m[i, 0], m[i, 1]) if b.drop_path > 0.0 else None for i, b in enumerate(blocks)]
 
-    def head_train(self, tokens, Tx, dropout_keep=None):
+    def head_train(self, tokens, Tx, dropout_keep=None, lean=False):
         """Training-mode head on the final norm's output tokens f32 [B,N,C] as one launch each way
         (csrc/head.hip through _HeadFn); eval keeps the ATen ops (softmax / sigmoid outputs).  Also what
-        graph.GraphedTrainStep calls."""
+        graph.GraphedTrainStep calls.  lean (an input-gradient-only pass): no dropout unless `dropout_keep` is given,
+        nothing drawn, and the backward leaves the head's parameter gradients alone."""
         n_obj = Tx * self.O
         keep = dropout_keep
         shp = (tokens.shape[0], 1 + n_obj, tokens.shape[2])
-        if keep is None and self._head_keep is not None and tuple(self._head_keep.shape) == shp:
+        if lean and keep is None:
+            pass
+        elif keep is None and self._head_keep is not None and tuple(self._head_keep.shape) == shp:
             keep, self._head_keep = self._head_keep, None          # drawn with this pass's stochastic-depth factors
         elif keep is None and self.head.dropout_rate > 0.0:
             if self._head_ones is None or tuple(self._head_ones.shape) != shp:
@@ -441,7 +459,7 @@ class SViT(nn.Module):
             keep = F.dropout(self._head_ones, self.head.dropout_rate, True)     # mask / (1 - p), one launch
         elif keep is not None:
             keep = keep.to(torch.float32).expand(tokens.shape[0], 1 + n_obj, tokens.shape[2]).contiguous()
-        logits, boxes, contact, xobj = _HeadFn.apply(self, tokens, Tx, self.O, keep)
+        logits, boxes, contact, xobj = _HeadFn.apply(self, tokens, Tx, self.O, keep, bool(lean))
         return logits, {"obj_desc": xobj, "pred_bboxes": boxes, "pred_contact_state": contact}
 
     @torch.no_grad()
@@ -460,7 +478,12 @@ class SViT(nn.Module):
         """input_grad: also compute d loss / d clip in the backward of this pass and leave it in
         `self.last_input_grad` -- f32 [B,3,T,S,S] in the coordinates of the S x S window, i.e. with respect to
         `clips.render()` for a U8Clips / AugClips (under cfg.MIXUP: to the mixed clip).  An fp32 clip tensor that
-        requires grad needs no request: its `.grad` is filled as by any torch module (svit_amd/saliency.py)."""
+        requires grad needs no request: its `.grad` is filled as by any torch module (svit_amd/saliency.py).
+        input_grad="only": the same result, bit for bit, from a backward that computes NO parameter gradient
+        (Engine.forward): flat.grad and every `param.grad` stay what they were, no gradient-ready hook runs, attached
+        monitors are not pushed, and the `requires_grad` flags are not read, so it works under a frozen cut.  It is a
+        diagnostic pass: unless `drop_scales` / `dropout_keep` are given, DropPath and the head's dropout are OFF
+        whatever the cfg's rates and nothing is drawn (`_rng_state` and torch's generator do not advance)."""
         if self.engine is None:
             raise hip.SvitHipError("SViT (svit_amd) has no CPU path: build it with "
                                    "build_model(cfg) / call .cuda() on an MI355X first")
@@ -473,6 +496,8 @@ class SViT(nn.Module):
             x = x.unsqueeze(2)
         Tx = x.shape[2]
         self.engine.refresh_weights()
+        if isinstance(input_grad, str):
+            return self._forward_only(x, Tx, drop_scales, dropout_keep, input_grad)
         if drop_scales is None:
             drop_scales = self.sample_drop_scales(x.shape[0], x.device, Tx=Tx)
         need_grad = torch.is_grad_enabled()
@@ -493,6 +518,27 @@ class SViT(nn.Module):
             return self.head_train(tokens, Tx, dropout_keep)
         feat = torch.cat((tokens[:, :1], tokens[:, -n_obj:]), dim=1)
         return self.head(feat, T=Tx, dropout_keep=dropout_keep)
+
+    def _forward_only(self, x, Tx, drop_scales, dropout_keep, input_grad):
+        """forward(..., input_grad="only"): every block saved (cut 0, whatever the flags say), drops off, lean heads"""
+        if input_grad != "only":
+            raise ValueError("input_grad is False, True or \"only\", got %r" % (input_grad,))
+        if drop_scales is None:
+            drop_scales = [None] * len(self.plan.blocks)
+        tokens = _Backbone.apply(self, x, drop_scales, True, self._anchor, 0, "only")
+        if self.training and self.fused_head:
+            return self.head_train(tokens, Tx, dropout_keep, lean=True)
+        n_obj = Tx * self.O
+        feat = torch.cat((tokens[:, :1], tokens[:, -n_obj:]), dim=1)
+        return _lean_head(self.head, feat, Tx, dropout_keep)
+
+
+def _lean_head(head, feat, Tx, dropout_keep):
+    """the ATen head on detached aliases of its parameters: autograd reaches `feat` and leaves no `.grad` on them"""
+    alias = {n: p.detach() for n, p in head.named_parameters()}
+    if dropout_keep is None and head.dropout_rate > 0.0 and head.training:
+        dropout_keep = 1.0      # (no draw)
+    return torch.func.functional_call(head, alias, (feat,), {"T": Tx, "dropout_keep": dropout_keep})
 
 
 def build_model(cfg, gpu_id=None):

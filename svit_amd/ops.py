@@ -565,6 +565,66 @@ def mixup_clips(x, mix):
     return x
 
 
+def _chk_attr_rec(rec, device):
+    """the 32-byte pass record (include/svit_hip.h, svit_attr_pass): int32 [8] on the device of the data"""
+    _chk_dev(rec)
+    if rec.dtype != torch.int32 or rec.numel() != 8 or rec.device != device:
+        raise hip.SvitHipError("the pass record must be int32 [8] on %s (got %s %s on %s)"
+                               % (device, rec.dtype, tuple(rec.shape), rec.device))
+
+
+def _chk_f32(what, t, shape, device):
+    if t.dtype != F32 or tuple(t.shape) != tuple(shape) or t.device != device:
+        raise hip.SvitHipError("%s must be f32 %s on %s, got %s %s on %s"
+                               % (what, tuple(shape), device, t.dtype, tuple(t.shape), t.device))
+
+
+def attr_perturb(x, rec, base=None, sigma=None, out=None):
+    """svit_attr_perturb: out = base + alpha * (x - base) + sigma[b] * noise, every operation rounded once; x f32
+    [B,3,T,H,W], base the same or None (zeros), sigma f32 [B] or None (no noise term), alpha and the seed of the noise
+    field from the device record `rec`.  -> out (a fresh tensor unless given; it may not be x or base)."""
+    _chk_dev(x, base, sigma, out)
+    _chk_attr_rec(rec, x.device)
+    if x.dtype != F32 or x.dim() != 5 or x.shape[1] != 3:
+        raise hip.SvitHipError("attr_perturb takes an fp32 clip [B,3,T,H,W], got %s %s" % (x.dtype, tuple(x.shape)))
+    B, _, T, H, W = x.shape
+    if base is not None:
+        _chk_f32("attr_perturb: base", base, x.shape, x.device)
+    if sigma is not None:
+        _chk_f32("attr_perturb: sigma", sigma, (B,), x.device)
+    if out is None:
+        out = torch.empty_like(x)
+    else:
+        _chk_f32("attr_perturb: out", out, x.shape, x.device)
+        if out.data_ptr() == x.data_ptr() or (base is not None and out.data_ptr() == base.data_ptr()):
+            raise hip.SvitHipError("attr_perturb: out may not be x or base")
+    hip.call("svit_attr_perturb", ptr(x), ptr(base), ptr(sigma), ptr(rec), ptr(out), B, T, H, W)
+    return out
+
+
+def attr_accumulate(g, acc, rec, scores_in=None, scores=None):
+    """svit_attr_accumulate: acc = (pass 0 ? 0 : acc) + weight * (g or g*g) as the device record `rec` says, g and acc
+    f32 of one shape; with `scores` f32 [rows, B] the pass's scores `scores_in` f32 [B] are copied into row `pass`."""
+    _chk_dev(g, acc, scores_in, scores)
+    _chk_attr_rec(rec, g.device)
+    if g.dtype != F32 or g.numel() < 1:
+        raise hip.SvitHipError("attr_accumulate takes a non-empty fp32 gradient, got %s %s" % (g.dtype, tuple(g.shape)))
+    _chk_f32("attr_accumulate: acc", acc, g.shape, g.device)
+    rows, B = 0, g.shape[0]
+    if scores is not None:
+        if scores_in is None:
+            raise hip.SvitHipError("attr_accumulate: a score table needs the pass's scores")
+        B = scores_in.numel()
+        _chk_f32("attr_accumulate: scores_in", scores_in, (B,), g.device)
+        if scores.dim() != 2:
+            raise hip.SvitHipError("attr_accumulate: the score table must be f32 [rows, %d]" % B)
+        _chk_f32("attr_accumulate: scores", scores, (scores.shape[0], B), g.device)
+        rows = scores.shape[0]
+    hip.call("svit_attr_accumulate", ptr(g), ptr(acc), ptr(rec), ptr(scores_in if scores is not None else None),
+             ptr(scores), rows, g.numel(), B)
+    return acc
+
+
 def fill_special_tokens(x, cls, objq, pos_t, L, Tx, O, add_pos):
     B, N, C_ = x.shape
     hip.call("svit_fill_special_tokens", ptr(x), ptr(cls), ptr(objq), ptr(pos_t), B, N, L, Tx, O,

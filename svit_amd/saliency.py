@@ -11,7 +11,9 @@ respect to the clip, f32 [B,3,T,S,S].  Three ways to ask:
 and `input_gradient` below does the first two for a scalar of choice.  For a U8Clips / AugClips the gradient is in the
 coordinates of the S x S window the stem reads: d loss / d clips.render() (under cfg.MIXUP: d / d the mixed clip), not
 with respect to the uint8 source pixels or through the resampling taps.  Nothing here works under a frozen cut
-(svit_amd/freeze.py): the frozen blocks keep no activations.  A saliency pass costs a full backward.
+(svit_amd/freeze.py): the frozen blocks keep no activations -- except the pass that computes no parameter gradient
+(`input_gradient(..., param_grads=False)`, `forward(..., input_grad="only")`), which saves every block and leaves the
+training state alone; svit_amd/attribution.py builds SmoothGrad and integrated gradients on it.
 
 `dgrad_host` is the float64 yardstick the kernel is held to (tests/test_input_grad_*.py).
 """
@@ -59,7 +61,7 @@ def _default_scalar(preds, extra_preds):
     return preds.max(dim=1).values.sum()
 
 
-def input_gradient(model, clips, labels=None, meta=None, scalar=None):
+def input_gradient(model, clips, labels=None, meta=None, scalar=None, param_grads=True):
     """d scalar / d clip, f32 [B,3,T,S,S] (T = 1 for stills), from ONE saving forward and ONE full backward in the
     model's current mode (call model.eval() first for a checkpoint: no DropPath, no dropout, the head's softmax).
     clips: the fp32 clip tensor [B,3,T,S,S] (or stills [B,3,S,S]), an input.U8Clips or an augment.AugClips -- for those
@@ -68,8 +70,14 @@ def input_gradient(model, clips, labels=None, meta=None, scalar=None):
     over the model's cfg (cross entropy on a video rank, the HAOG losses with `meta`); otherwise
     `scalar(preds, extra_preds)`, by default the sum of each sample's largest logit.
     The backward accumulates parameter gradients like any other: `flat.grad` IS ZEROED ON EXIT, so call this between
-    steps, not between a backward and its optimizer step.  Raises ValueError under a frozen cut."""
+    steps, not between a backward and its optimizer step.  Raises ValueError under a frozen cut.
+    param_grads=False: the pass that computes the input gradient and NO parameter gradient (forward(...,
+    input_grad="only")) -- the same gradient bit for bit where both routes run, but flat.grad and every param.grad are
+    left as they are (nothing is zeroed on exit: it may be called between a backward and its optimizer step), frozen
+    parameters do not matter, and in train mode DropPath and dropout are off and nothing is drawn."""
     core = _core(model)
+    if not param_grads:
+        return _input_gradient_only(model, core, clips, labels, meta, scalar)
     cut = core.frozen_cut()
     if cut > 0:
         raise ValueError("input_gradient under a frozen cut (the parameters' requires_grad flags freeze everything "
@@ -101,6 +109,30 @@ def input_gradient(model, clips, labels=None, meta=None, scalar=None):
         core.last_input_grad = None
         if core.flat is not None:
             core.flat.grad.zero_()
+
+
+def _input_gradient_only(model, core, clips, labels, meta, scalar):
+    x = clips[0] if isinstance(clips, (list, tuple)) else clips
+    image = meta is not None and "haog_bboxes" in meta
+    try:
+        with torch.enable_grad():
+            if torch.is_tensor(x):
+                x = x.detach().to(torch.float32)
+            preds, extra = model([x], meta, input_grad="only")
+            if labels is not None or image:
+                from .losses import VideoImageLoss
+                fn = VideoImageLoss(core.cfg, is_video_rank=not image)
+                s = fn.total(fn(preds, extra, labels, meta))
+            else:
+                s = (scalar or _default_scalar)(preds, extra)
+            s.backward()
+        grad = core.last_input_grad
+        if grad is None:
+            raise RuntimeError("input_gradient: the backward left no input gradient (does the scalar depend on the "
+                               "model's outputs?)")
+        return grad.unsqueeze(2) if grad.dim() == 4 else grad
+    finally:
+        core.last_input_grad = None
 
 
 def saliency_map(grad):
